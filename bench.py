@@ -22,6 +22,8 @@ Arithmetic: fp32 results everywhere; since round 6 the detector's 1x1 convolutio
 products on the fp16 matrix instruction (the default; VIDO_CONV1X1_ARITH=bf16x3: three bf16 planes, six products) — with fp32 accumulators (config.net_arith;
 csrc/conv1x1.hip), with a measured error against float64 below the fp32 instruction's.
 The per-frame path does not shard (frame k depends on frame k-1): --gpus N runs N independent replicas, no data-path collective.
+--dump-outputs DIR writes what the chain computed for the last timed frame as .npy files (inputs, weights and frames are seeded: the same arguments give the same inputs),
+so that two builds can be compared output for output.
 
 Extra objects on the same JSON line:
   stage_ms       per-frame breakdown of the chain (networks alone, tracker stages, local BA)
@@ -50,6 +52,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: fp32 vector = fp32 matrix peak
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def newest_profile(name):
@@ -84,6 +87,22 @@ def write_settings(path, K, w, h):
         fh.write("Camera.bf: 387.57\nCamera.fps: 30.0\nCamera.RGB: 0\nChooseData: 1\nDepthMapFactor: 1.0\nThDepthBG: 40.0\nThDepthOBJ: 25.0\n")
         fh.write("MaxTrackPointBG: 3000\nMaxTrackPointOBJ: 800\nSFMgThres: 0.12\nSFDsThres: 0.3\nWINDOW_SIZE: 20\nOVERLAP_SIZE: 4\nUseSampleFeature: 0\n")
         fh.write("ORBextractor.nFeatures: 2000\nORBextractor.scaleFactor: 1.2\nORBextractor.nLevels: 8\nORBextractor.iniThFAST: 20\nORBextractor.minThFAST: 7\n")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float64 where it is float64 and float32 otherwise.  When they would pass DUMP_LIMIT_BYTES together, each
+    array of more than 4096 elements is replaced by the same fixed, seeded sample of its flattened elements (sorted indices) in every run with the same shapes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - (4096 * 8 + 1024) * len(arrays)          # (room for the small arrays and the .npy headers)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.size > 4096:
+            n = max(4096, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _split_pmc(name):
@@ -125,7 +144,11 @@ def main():
                                                                  "have executed end to end before an 8-GPU node sees them (tests/test_e2e_gpu.py)")
     ap.add_argument("--gba-cams", type=int, default=500)
     ap.add_argument("--gba-points", type=int, default=100000)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the chain handed its caller for the last timed frame as DIR/<name>.npy (rank 0): the tracker's "
+                                                          "Tcw and point / object counts, the networks' flow / depth / label image and the detector's labels and counts; float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -215,6 +238,18 @@ def main():
         t = torch.tensor([dt], device="cpu" if args.oversubscribe else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed frame, read after the clock: the tracker's pose and counts, and the networks' maps as parked in the frame's hand-over slot (the next push() reuses
+        # the slot; with feed=given the tracker is handed the renderer's maps, the networks' are computed and parked all the same)
+        slot = (e2e.k - 1) % e2e.RING
+        db, hb = e2e.dev[slot], e2e.host[slot]
+        outs = {"flow": db["flow"].cpu().numpy(), "depth": db["depth"].cpu().numpy(), "mask": db["mask"].cpu().numpy(), "det_labels": e2e._alive[3].cpu().numpy()}
+        if nodes.last_counts is not None:
+            outs["det_counts"] = hb["counts"].numpy().copy()                     # (labels kept, detections)
+        if e2e.poses[-1] is not None:
+            outs["pose_Tcw"] = e2e.poses[-1]
+            outs["track_counts"] = np.array([e2e.stats[-1][k] for k in ("n_keypoints", "n_static", "n_static_inliers", "n_objects", "n_object_points", "ba_window")])
+        dump_outputs(args.dump_outputs, outs)
     fps = args.steps * world / dt
     st = e2e.stats[n0:]
     mean = lambda key: float(np.mean([s.get(key, 0.0) for s in st])) if st else 0.0

@@ -139,7 +139,8 @@ def test_pack_gconv3x3_is_the_operand_order_of_the_kernel():
 
 def test_miopen_find_db_is_offered_only_to_its_own_miopen_build(monkeypatch, tmp_path):
     """pipeline._offer_miopen_db: the shipped find-db (file names carry the MIOpen version it was recorded with) is put into MIOPEN_USER_DB_PATH only when torch reports that
-    version; an explicit setting and VIDO_NO_MIOPEN_DB win; a read-only package directory gets a private copy."""
+    version; an explicit setting and VIDO_NO_MIOPEN_DB win; MIOpen is handed a private copy (it writes into the directory it is given), never the shipped directory:
+    build/miopen_db in the package, or the temp directory when the package is read-only."""
     import os
     from vido_slam_amd import pipeline
     files = [f for f in os.listdir(pipeline._MIOPEN_DB) if ".HIP." in f]
@@ -148,7 +149,8 @@ def test_miopen_find_db_is_offered_only_to_its_own_miopen_build(monkeypatch, tmp
     ver = int(tag[0]) * 1000000 + int(tag[1]) * 1000 + int(tag[2])
     monkeypatch.delenv("MIOPEN_USER_DB_PATH", raising=False); monkeypatch.delenv("VIDO_NO_MIOPEN_DB", raising=False)
     monkeypatch.setattr(torch.backends.cudnn, "version", lambda: ver)
-    assert pipeline._offer_miopen_db() == pipeline._MIOPEN_DB and os.environ["MIOPEN_USER_DB_PATH"] == pipeline._MIOPEN_DB
+    got = pipeline._offer_miopen_db()
+    assert got == pipeline._MIOPEN_DB_COPY != pipeline._MIOPEN_DB and os.environ["MIOPEN_USER_DB_PATH"] == got and set(files) <= set(os.listdir(got))
     monkeypatch.delenv("MIOPEN_USER_DB_PATH")
     monkeypatch.setattr(torch.backends.cudnn, "version", lambda: ver + 1000)          # another minor version: not offered
     assert pipeline._offer_miopen_db() is None and "MIOPEN_USER_DB_PATH" not in os.environ
@@ -160,7 +162,7 @@ def test_miopen_find_db_is_offered_only_to_its_own_miopen_build(monkeypatch, tmp
     monkeypatch.delenv("MIOPEN_USER_DB_PATH")
     monkeypatch.setattr(os, "access", lambda p, m: False)                               # read-only installation
     got = pipeline._offer_miopen_db()
-    assert got is not None and got != pipeline._MIOPEN_DB and sorted(os.listdir(got)) >= sorted(files)
+    assert got is not None and got not in (pipeline._MIOPEN_DB, pipeline._MIOPEN_DB_COPY) and sorted(os.listdir(got)) >= sorted(files)
 
 
 def test_pack_conv1x1_is_the_operand_order_of_the_kernel():

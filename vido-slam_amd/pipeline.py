@@ -80,8 +80,10 @@ import os as _os
 # three nodes at their feed sizes.  With it the default immediate-mode path picks those solvers without searching (the search costs ~3.5 minutes of start-up; the
 # heuristic pick without the db is 0.7 ms per frame slower).  Read by MIOpen when its handle is created, i.e. at the first convolution; an explicit setting wins.
 # The db is keyed to one MIOpen build (file name gfx950100.HIP.<major>_<minor>_<patch>_...): it is offered only when this process' MIOpen has that version, MIOpen
-# writes new entries into the directory it is given, so a read-only installation gets a private copy under the temp directory; VIDO_NO_MIOPEN_DB=1 opts out.
+# writes new entries into the directory it is given, so it is given a private copy (build/miopen_db next to the library's objects, or under the temp directory when the
+# package is read-only) and the shipped files stay as committed; a shipped file newer than its copy replaces it.  VIDO_NO_MIOPEN_DB=1 opts out.
 _MIOPEN_DB = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "miopen_db")
+_MIOPEN_DB_COPY = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "build", "miopen_db")
 
 
 def _offer_miopen_db():
@@ -96,14 +98,19 @@ def _offer_miopen_db():
     files = [f for f in _os.listdir(_MIOPEN_DB) if tag in f]
     if not files:
         return None
-    path = _MIOPEN_DB
-    if not _os.access(path, _os.W_OK):
-        import shutil, tempfile
+    import shutil, tempfile
+    path = _MIOPEN_DB_COPY
+    try:
+        _os.makedirs(path, exist_ok=True)
+    except OSError:
+        pass
+    if not (_os.path.isdir(path) and _os.access(path, _os.W_OK)):
         path = _os.path.join(tempfile.gettempdir(), "vido_slam_miopen_db_%d" % _os.getuid())
         _os.makedirs(path, exist_ok=True)
-        for f in files:
-            if not _os.path.exists(_os.path.join(path, f)):
-                shutil.copy(_os.path.join(_MIOPEN_DB, f), path)
+    for f in files:
+        src, dst = _os.path.join(_MIOPEN_DB, f), _os.path.join(path, f)
+        if not _os.path.exists(dst) or _os.path.getmtime(dst) < _os.path.getmtime(src):
+            shutil.copy2(src, dst)
     _os.environ["MIOPEN_USER_DB_PATH"] = path
     return path
 
