@@ -328,14 +328,15 @@ int vido_conv1x1_layout(int cin, int cout, int hw);
  *       w_h x_h, w_h x_l', w_l' x_h run on v_mfma_f32_32x32x16_f16 with fp32 accumulators.  vido_conv1x1_layout answers 3 =
  *       [co / 32][k / 16][plane 2][32 ((k % 16) / 8) + co % 32][k % 8] fp16 of the weight scaled per OUTPUT CHANNEL by the power of two that puts the channel's largest |w| into
  *       [2^14, 2^15), followed by [cout] floats: the inverse scales (4 bytes per weight + 4 per channel).  Activations: full precision for 2.5e-4 <= |x| < 65504 (smaller ones: an absolute error <= 1.5e-11); a launch
- *       that meets |x| >= 65504 raises vido_conv1x1_range_flag (its outputs are not valid then).
+ *       that meets |x| >= 65504, an infinity or a NaN raises vido_conv1x1_range_flag (its outputs are not valid then).
  *   2 = split-bf16: three bf16 planes, the six plane products with i + j <= 2 on v_mfma_f32_32x32x16_bf16; fp32's range, twice the matrix work; layout 2 =
  *       [co / 32][k / 16][plane 3][32 ((k % 16) / 8) + co % 32][k % 8] bf16 (6 bytes per weight).
  *   1 = the fp32 matrix instruction (layouts 0 / 1 above).
  * Also selected by VIDO_CONV1X1_ARITH = f16x2 | bf16x3 | f32 in the environment.  Returns the previous setting; process-wide — set it before weights are packed (a packed
  * weight carries its layout, a mismatch is refused by the caller's shape check). */
 int vido_conv1x1_set_arith(int arith);
-/* non-zero when a split-fp16 launch on this context met an activation outside fp16's range since the last reset; read after the stream has been waited for */
+/* non-zero when a split-fp16 launch on this context (1x1, 3x3, fully connected, 2x2 transposed) met an activation outside fp16's range, an infinity or a NaN since the last
+ * reset; read after the stream has been waited for.  reset != 0: read and clear in one atomic exchange. */
 int vido_conv1x1_range_flag(vido_ctx* ctx, int reset);
 int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope);
 /* 2 x 2 stride-2 transposed convolution + bias + leaky-ReLU of a batch as one split-fp16 GEMM with a scatter epilogue (the mask head's conv5_mask,
@@ -391,7 +392,8 @@ int vido_fc_h(vido_ctx* ctx, const float* x, const void* w_packed, const float* 
  * the detector's chip-filling 256 -> 256 layers (FPN outputs and RPN head on P2 / P3: backbone/fpn.py:55-66, rpn/rpn.py:74-107; the mask head: roi_mask_feature_extractors.py).
  * x [n][cin][h][w], y [n][cout][h][w] f32 DEVICE; w_packed: two fp16 planes of the output channels scaled by powers of two, plane p of element (co, ci, dy, dx) at
  * [co / 32][ci / 16][dy][dx][p][32 ((ci % 16) / 8) + co % 32][ci % 8], then [cout] floats: the inverse scales (vido_slam_amd/nets/ops.py::pack_conv3x3_h).
- * vido_conv3x3_h_supported: cout 32, 64 or a multiple of 128 (input channels are padded to a multiple of 16 with zero weights), tensors below 1 GB.  Activations must stay below 65504 in magnitude (vido_conv1x1_range_flag otherwise). */
+ * vido_conv3x3_h_supported: cout 32, 64 or a multiple of 128 (input channels are padded to a multiple of 16 with zero weights), tensors below 1 GB.  Activations must be finite and below 65504 in magnitude (vido_conv1x1_range_flag otherwise); the padded channels never read
+ * the next image's activations. */
 int vido_conv3x3_h_supported(int n, int cin, int cout, int h, int w);
 int vido_conv3x3_h_workgroups(int n, int cout, int h, int w);
 int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope);

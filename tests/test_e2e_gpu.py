@@ -115,7 +115,9 @@ def test_static_detector_head_equals_the_dynamic_one(vido):
             assert torch.equal(sta["labels"][:n], dyn["labels"]) and torch.equal(sta["scores"][:n], dyn["scores"]) and torch.equal(sta["boxes"][:n], dyn["boxes"])
             # the mask head sees batch 100 instead of a bucket: its four 3x3 layers take different kernels (direct split-fp16 with 16-row or 8-row blocks, Winograd below 128
             # workgroups), the tail computes one class channel with float64 sums instead of 81 with fp32: probabilities equal to 1.5e-4 (measured: 1.0e-4 .. 1.5e-4 box to box;
-            # they are thresholded at 0.5 — the label images below differ in isolated pixels only)
+            # they are thresholded at 0.5 — the label images below differ in isolated pixels only).  Kept at 5e-4, not 1e-4: against a float64 evaluation of the mask head on
+            # the same pooled features the static head is 4.1e-4 off, the dynamic one 4.4e-4 and the plain fp32 library chain 3.9e-4 (tests/test_fullsize_gpu.py::
+            # test_mask_head_against_float64) — the fp32 rounding of large, cancelling logits, not the split-fp16 kernels — so 1e-4 would sit below the measured 1.5e-4
             assert float((sta["masks"][:n] - dyn["masks"]).abs().max()) < 5e-4
             assert bool((sta["labels"][n:] == 0).all()) and bool((sta["boxes"][n:] == 0).all())
             img_s, lab_s, n_lab, n_det = nets.analyse_image_static(net, feats, logits, deltas, (480, 640), feed=nodes.mask_feed, confidence=nodes.confidence)

@@ -296,8 +296,9 @@ __global__ __launch_bounds__(256) void k_conv1x1_n112(C1Args A)
 //   * weights: every output channel is scaled at pack time by the power of two that puts its largest |w| into [2^14, 2^15) (pack_conv1x1 layout 3; the inverse scales, one
 //     float per channel, follow the planes); the epilogue multiplies the sum by it — exact;
 //   * activations are taken as they are: full precision for 2.5e-4 <= |x| < 65504 (28 binades; a smaller |x| keeps an ABSOLUTE error <= 2^-36 = 1.5e-11, far below the
-//     rounding of the sum it enters), and a value past the range would turn into an infinity — so the split tracks max |x| beside its conversions (one v_max3 per pair) and a wave that met
-//     |x| >= 65504 raises the context's range flag (vido_conv1x1_range_flag: the caller of the network checks it where it reads the detections back and can repeat the frame
+//     rounding of the sum it enters), and a value past the range would turn into an infinity — so the split tracks max |x| beside its conversions (one v_maximum3 per pair) and a wave that met
+//     |x| >= 65504 or a NaN raises the context's range flag (the IEEE maximum v_maximum3_f32, not fmaxf: fmaxf returns the operand that is not a NaN)
+//     (vido_conv1x1_range_flag: the caller of the network checks it where it reads the detections back and can repeat the frame
 //     with vido_conv1x1_set_arith(2), the bf16 form, which has fp32's range).  The detector's activations stay below a few hundred.
 // Error against float64, both forms and the fp32 instruction: tests/test_maskrcnn_gpu.py (the bar: <= 1.5x the fp32 instruction's; measured 0.4 - 1.0x).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -409,7 +410,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
                 asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r.y) : "v"(h), "s"(-2048.f), "v"(vs.y));
                 const f16x2 l = __builtin_convertvector(r, f16x2);
                 bp[buf][0][pr] = __builtin_bit_cast(unsigned, h); bp[buf][1][pr] = __builtin_bit_cast(unsigned, l);
-                xmax = __builtin_fmaxf(__builtin_fmaxf(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));      // one v_max3_f32 with |.| operand modifiers
+                xmax = __builtin_elementwise_maximum(__builtin_elementwise_maximum(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));      // one v_maximum3_f32 with |.| modifiers (a NaN sticks; fmaxf would drop it)
             }
         } else {
 #pragma unroll
@@ -487,7 +488,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");           // (the last, unused copies)
 #pragma unroll
     for (int rb = 0; rb < 4; rb++) acc[rb] += NP == 2 ? acl[rb] * 0x1p-11f : acl[rb];
-    if (NP == 2 && !(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);      // (also a NaN)
+    if (NP == 2 && !(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);      // (also a NaN: the IEEE maximum propagates it into xmax)
     const float* wsc = (const float*)((const char*)A.wp + (size_t)4 * A.K * A.M);      // (NP == 2) the inverse channel scales behind the planes
     // D[i][j] as above: register r of a lane = output channel 8 (r / 4) + 4 (lane >> 5) + (r & 3) of the row block, position lane & 31
     // Epilogue in two phases per row block — the loads (bias, channel scale, residual), then sum + activation + stores — with the loads of the NEXT block issued before
@@ -577,14 +578,14 @@ static std::atomic<int>& c1_arith()          // 0 = split-fp16 (two planes, thre
 
 int vido_conv1x1_set_arith(int arith) { return c1_arith().exchange(arith == 1 ? 1 : arith == 2 ? 2 : 0); }
 
-/* The range flag of the split-fp16 form: non-zero when a launch since the last reset met an activation with |x| >= 65504 (or a NaN) — its outputs are then not valid.
+/* The range flag of the split-fp16 kernels (1x1, 3x3, fully connected, 2x2 transposed): non-zero when a launch since the last reset met an activation with |x| >= 65504, an
+ * infinity or a NaN — its outputs are then not valid.
  * Host-visible memory written by the kernels: read it after the stream has been waited for.  reset != 0 clears it. */
 int vido_conv1x1_range_flag(vido_ctx* ctx, int reset)
 {
     if (!ctx || !ctx->c1_range_flag) return 0;
-    const int v = (int)__atomic_load_n(ctx->c1_range_flag, __ATOMIC_ACQUIRE);
-    if (reset) __atomic_store_n(ctx->c1_range_flag, 0u, __ATOMIC_RELEASE);
-    return v;
+    // read and reset in ONE atomic step: a flag raised between a load and a store would be lost
+    return reset ? (int)__atomic_exchange_n(ctx->c1_range_flag, 0u, __ATOMIC_ACQ_REL) : (int)__atomic_load_n(ctx->c1_range_flag, __ATOMIC_ACQUIRE);
 }
 
 int vido_conv1x1_layout(int cin, int cout, int hw)

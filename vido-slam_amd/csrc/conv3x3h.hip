@@ -5,7 +5,7 @@
 // (roi_heads/mask_head/roi_mask_feature_extractors.py).  The arithmetic is csrc/conv1x1.hip's split-fp16 form: every fp32 operand is h + 2^-11 l' with h = rne16(x),
 // l' = rne16(2^11 (x - h)); the three products w_h x_h (-> acc), w_h x_l' and w_l' x_h (-> acl) run on v_mfma_f32_32x32x16_f16 with fp32 accumulators, the result is
 // acc + 2^-11 acl times the output channel's inverse weight scale (a power of two chosen at pack time so that the channel's largest |w| sits in [2^14, 2^15)).  Activations
-// are taken as they are (|x| < 65504; a workgroup that meets a larger one raises the context's range flag, vido_conv1x1_range_flag).  The 16-bit instruction does 16x the
+// are taken as they are (|x| < 65504; a workgroup that meets a larger one, an infinity or a NaN raises the context's range flag, vido_conv1x1_range_flag).  The 16-bit instruction does 16x the
 // fp32 instruction's multiply-adds per cycle, so the DIRECT form's 9 x 3 = 27 products per output and input channel cost less matrix time than Winograd's 4 on the fp32
 // instruction — and a direct tile streams 36 bytes of weight planes per (input, output) channel pair where a Winograd tile streams 64 - 96: with these kernels bound by the
 // operand stream L2 -> LDS, bytes per tile are what counts.
@@ -45,7 +45,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define C3_PBUF(BR) (2 * C3_PLANE(BR))
 #define C3_LDS(BR) (C3_RBW * C3_WSLOT + C3_RAW(BR) + 2 * C3_PBUF(BR))
 
-struct C3Args { const float* x; const void* wp; const float* bias; float* y; int N, Cin, Cout, H, W, nby, nbx, mt, total, nchunk; float slope; unsigned xbytes, wbytes; unsigned* range_flag; };
+struct C3Args { const float* x; const void* wp; const float* bias; float* y; int N, Cin, Cout, H, W, nby, nbx, mt, total, nchunk; float slope; unsigned wbytes; unsigned* range_flag; };
 
 template <int RPW, int CG>
 __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
         const int e = 64 * (8 * j + w) + lane, ch = e / WPIX, rem = e - ch * WPIX, row = rem / 18, col = rem - row * 18, gy = Y0 - 1 + row, gx = X0 - 1 + col;
         xvo[j] = (e < 16 * WPIX && gy >= 0 && gy < A.H && gx >= 0 && gx < A.W) ? 4u * (unsigned)(ch * hw + gy * A.W + gx) : C3_OOB;
     }
-    const unsigned ximg = 4u * (unsigned)n * (unsigned)A.Cin * (unsigned)hw, xchunk = 64u * (unsigned)hw;
+    const unsigned ximg = 4u * (unsigned)n * (unsigned)A.Cin * (unsigned)hw, ximg_end = ximg + 4u * (unsigned)A.Cin * (unsigned)hw, xchunk = 64u * (unsigned)hw;
     char* const RAW = L + C3_RBW * C3_WSLOT;
     char* const PL = RAW + RAWB;
     auto issue_w = [&](int s, int slot) {                                  // this wave's three pieces of step s (clamped by the caller)
@@ -84,10 +84,11 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
         for (int q = 0; q < 3; q++) __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (__attribute__((address_space(3))) void*)(S + q * 8192), 16, avq[q], abase[q] + so, 0, 0);
     };
     auto issue_x = [&](int c) {                                            // this wave's XP pieces of chunk c's window
-        // The chunk rides in the DESCRIPTOR (base = first channel of the chunk, num_records = the bytes of the tensor behind it), not in the scalar offset: the hardware's
-        // range check looks at the per-lane offset alone, and the channels a last chunk reads past Cin (their weights are zero) must not leave the tensor behind the last image.
+        // The chunk rides in the DESCRIPTOR (base = first channel of the chunk, num_records = the bytes of THIS IMAGE behind it), not in the scalar offset: the hardware's
+        // range check looks at the per-lane offset alone, so the channels a last chunk reads past Cin (their weights are zero) come back as zeros — not as the next image's
+        // first channels, where an infinity or a NaN would turn this image's sums into NaNs (inf x 0) and a large value would raise the range flag for it.
         const unsigned so = ximg + xchunk * (unsigned)c;
-        const __amdgpu_buffer_rsrc_t xc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A.x + so), 0, A.xbytes - so, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A.x + so), 0, ximg_end - so, 0x00020000);
 #pragma unroll
         for (int j = 0; j < XP; j++) __builtin_amdgcn_raw_ptr_buffer_load_lds(xc, (__attribute__((address_space(3))) void*)(RAW + (8 * j + w) * 256), 4, xvo[j], 0, 0, 0);
     };
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
                 asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r.y) : "v"(h), "s"(-2048.f), "v"(vs.y));
                 const f16x2 l = __builtin_convertvector(r, f16x2);
                 P[pix * 8 + q] = __builtin_bit_cast(unsigned, h); P[PLANE / 4 + pix * 8 + q] = __builtin_bit_cast(unsigned, l);
-                xmax = __builtin_fmaxf(__builtin_fmaxf(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));
+                xmax = __builtin_elementwise_maximum(__builtin_elementwise_maximum(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));      // (v_maximum3_f32: a NaN sticks)
             }
         }
     };
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");           // (the last, unused copies)
 #pragma unroll
     for (int rb = 0; rb < RPW; rb++) acc[rb] += acl[rb] * 0x1p-11f;
-    if (!(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);     // (also a NaN)
+    if (!(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);     // (also a NaN: the IEEE maximum propagates it into xmax)
 
     // ---- epilogue: register r of a lane = output channel 8 (r / 4) + 4 (lane >> 5) + (r & 3) of the row block, position lane & 31 of the wave's two rows
     const float* wsc = (const float*)((const char*)A.wp + (size_t)A.nchunk * 16 * 18 * A.Cout * 2);      // the inverse channel scales behind the planes (36 bytes per weight)
@@ -217,8 +218,8 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
 extern "C" {
 
 /* 1 when vido_conv3x3_h_bias_act takes the shape: output channels 32, 64 or a multiple of 128, tensors below 1 GB.  Input channels are padded to a multiple of 16 with ZERO
- * WEIGHTS (pack_conv3x3_h): the last chunk's window reads past the image's channels — the next image's (finite) activations times zero, or, past the tensor, the zeros of an
- * out-of-range copy. */
+ * WEIGHTS (pack_conv3x3_h): the last chunk's window reaches past the image's channels, where its copies are out of range (the descriptor ends with the image) and
+ * give zeros. */
 int vido_conv3x3_h_supported(int n, int cin, int cout, int h, int w)
 {
     const long long cp = (cin + 15) / 16 * 16;
@@ -244,7 +245,7 @@ int vido_conv3x3_h_workgroups(int n, int cout, int h, int w) { const int br = c3
  * w_packed: the weight [cout][cin][3][3] as two fp16 planes of its output channels scaled by powers of two, plane p of element (co, ci, dy, dx) at
  * [co / 32][ci / 16][dy][dx][p][32 ((ci % 16) / 8) + co % 32][ci % 8] (input channels padded to a multiple of 16 with zeros), followed by [cout] floats: the inverse scales
  * (vido_slam_amd/nets/ops.py::pack_conv3x3_h).
- * slope: 0 = ReLU, 1 = none (0 <= slope <= 1).  Activations must stay below 65504 in magnitude (else: vido_conv1x1_range_flag).  Enqueues on the adopted stream; capturable. */
+ * slope: 0 = ReLU, 1 = none (0 <= slope <= 1).  Activations must be finite and below 65504 in magnitude (else: vido_conv1x1_range_flag).  Enqueues on the adopted stream; capturable. */
 int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope)
 {
     if (!ctx) return VIDO_E_INVALID;
@@ -255,7 +256,7 @@ int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed,
     const int br = c3_block_rows(n, cout, h, w);
     const int nby = (h + br - 1) / br, nbx = (w + 15) / 16, mt = cout >= 128 ? cout / 128 : 1, total = n * nby * nbx * mt;
     const int nchunk = (cin + 15) / 16;
-    C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(4ll * n * cin * h * w), (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag};
+    C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag};
     static bool attr[64] = {};
     if (!attr[ctx->device & 63]) {
 #define C3_ATTR(RPW_, CG_) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h<RPW_, CG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3_LDS(16 / CG_)))

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void k_fc_h(FcArgs A)
             asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r.y) : "v"(h), "s"(-2048.f), "v"(vs.y));
             const f16x2 l = __builtin_convertvector(r, f16x2);
             bp[buf][0][pr] = __builtin_bit_cast(unsigned, h); bp[buf][1][pr] = __builtin_bit_cast(unsigned, l);
-            xmax = __builtin_fmaxf(__builtin_fmaxf(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));
+            xmax = __builtin_elementwise_maximum(__builtin_elementwise_maximum(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));      // (v_maximum3_f32: a NaN sticks)
         }
     };
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(FC_PW * (FC_RB - 2)) : "memory");      // slot 0 has landed
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void k_fc_h(FcArgs A)
         }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (!(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);
+    if (!(xmax < 65504.f) && A.range_flag) atomicOr(A.range_flag, 1u);    // (also a NaN)
     // scaled partial sums: register r of a lane = output 8 (r / 4) + 4 (lane >> 5) + (r & 3) of the row block, row lane & 31 -> four consecutive outputs per 16-byte store
     const float* wsc = (const float*)((const char*)A.wp + (size_t)4 * A.K * A.O);
     const int row = r0 + 32 * w + (lane & 31);
@@ -175,7 +175,7 @@ int vido_fc_h_splitk(int rows, int k, int outs)
 
 /* y[rows][outs] = leaky_relu(x[rows][k] w[outs][k]^T + bias, slope): x, y, bias f32 DEVICE (16-byte aligned); w_packed = pack_conv1x1(w viewed as [outs][k][1][1], layout 3)
  * (vido_slam_amd/nets/ops.py); part: scratch of vido_fc_h_splitk(rows, k, outs) x rows x outs floats (the caller's: a launch inside a stream capture cannot allocate).
- * Activations must stay below 65504 in magnitude (vido_conv1x1_range_flag otherwise).  Enqueues two launches on the adopted stream; capturable. */
+ * Activations must be finite and below 65504 in magnitude (vido_conv1x1_range_flag otherwise).  Enqueues two launches on the adopted stream; capturable. */
 int vido_fc_h(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* part, float* y, int rows, int k, int outs, float slope)
 {
     if (!ctx) return VIDO_E_INVALID;

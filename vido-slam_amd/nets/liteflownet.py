@@ -231,10 +231,10 @@ class LiteFlowNet(nn.Module):
 @torch.no_grad()
 def analyse_flow(net, previous_bgr, current_bgr):
     """run_flow_net.py:66-110: HxWx3 u8 BGR pair -> HxWx2 f32 flow (BGR->RGB, /255, bilinear resize to x32, forward,
-    bilinear resize back, rescale u by W/W', v by H/H')."""
-    dev = next(net.parameters()).device
+    bilinear resize back, rescale u by W/W', v by H/H').  The images enter in the network's own dtype (float64 for a .double() reference)."""
+    dev, dt = next(net.parameters()).device, next(net.parameters()).dtype
     def prep(img):
-        t = (img.to(dev).flip(-1) if torch.is_tensor(img) else torch.as_tensor(img[:, :, ::-1].copy(), device=dev)).permute(2, 0, 1).float().div(255.0).unsqueeze(0)   # a device tensor stays on the device
+        t = (img.to(dev).flip(-1) if torch.is_tensor(img) else torch.as_tensor(img[:, :, ::-1].copy(), device=dev)).permute(2, 0, 1).to(dt).div(255.0).unsqueeze(0)   # a device tensor stays on the device
         return t
     a, b = prep(previous_bgr), prep(current_bgr)
     H, W = a.shape[2], a.shape[3]

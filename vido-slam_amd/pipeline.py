@@ -247,11 +247,16 @@ class NetNodes:
         return flow, depth, mask, labels, (e0, e1, e2)
 
     def check_conv1x1_range(self):
-        """The split-fp16 1x1 convolutions (csrc/conv1x1.hip, the default arithmetic) take activations below 65504; a launch that met a larger one raised the context's range
-        flag and its outputs are not valid.  Called where a frame's networks are known to be complete; never seen with the detector's weights (activations of a few hundred)."""
-        if hasattr(self.ops, "conv1x1_range_flag") and self.ops.conv1x1_range_flag(reset=True):
-            raise RuntimeError("conv1x1: an activation left the range of the split-fp16 arithmetic (|x| >= 65504); the frame's detections are not valid — "
-                               "run with VIDO_CONV1X1_ARITH=bf16x3 (fp32's range, twice the matrix work)")
+        """The split-fp16 kernels (csrc/conv1x1.hip 1x1 and 2x2 transposed, conv3x3h.hip, fch.hip: the default arithmetic) take finite activations below 65504; a launch that
+        met a larger one, an infinity or a NaN raised its context's range flag and its outputs are not valid.  Both contexts are read (and reset): the detector's (ops) and
+        LiteFlowNet's (ops_flow: its 3x3 layers on conv3x3h.hip).  Called where a frame's networks are known to be complete; never seen with the networks' weights
+        (activations of a few hundred)."""
+        hit = [name for name, o in (("detector / depth", self.ops), ("flow", getattr(self, "ops_flow", None)))
+               if o is not None and hasattr(o, "conv1x1_range_flag") and o.conv1x1_range_flag(reset=True)]      # (every flag read, so that every one is reset)
+        if hit:
+            raise RuntimeError("split-fp16: an activation left the range of the arithmetic (|x| >= 65504, an infinity or a NaN) on the %s context; the frame's outputs are not "
+                               "valid — run with VIDO_CONV3X3_H=0 VIDO_NO_FC_H=1 VIDO_CONV1X1_ARITH=bf16x3 (fp32's range: the 3x3 and fully connected layers back on fp32 "
+                               "kernels, the 1x1 ones on split-bf16)" % " and ".join(hit))
 
     @torch.no_grad()
     def redo_detector_if_overflowed(self, cur_bgr, n_det_host):
