@@ -25,8 +25,12 @@ The per-frame path does not shard (frame k depends on frame k-1)
 --dump-outputs DIR writes what the chain computed for the last timed frame as .npy files (inputs, weights and frames are seeded: the same arguments give the same inputs),
 so that two builds can be compared output for output.
 
-Extra objects on the same JSON line:
-  stage_ms       per-frame breakdown of the chain (networks alone, tracker stages, local BA)
+A plain run does only what the headline needs: set-up (the frames are rendered on a pool of host threads), prologue, warm-up, the timed steps, --dump-outputs, and the
+JSON line with the headline, stage_ms of the timed frames (tracker stages, local BA, the hand-over waits), per_frame_counts, the pose error and the configuration.
+--full adds every other measurement below, each a run of its own after the headline (what --no-extra, --cpu-baseline, --batch and --gba-* select applies there).
+
+Extra objects on the same JSON line with --full:
+  stage_ms       adds the networks alone (one graph replay each, *_ms) to the per-frame breakdown of the chain
   roofline       dominant hand-written kernel of the tracker front end (FAST): algorithmic bytes / live HIP-event time vs the 8 TB/s HBM peak,
                  measured on BASELINE configs[1] batched (64 frames in flight, the only regime where an HBM roofline of a <1 MB/frame stage means anything)
   roofline_ba    k_ba_linearize at configs[3] (local window) and configs[4] (1 M edges) size: 288 B per edge
@@ -144,6 +148,8 @@ def main():
                                                                  "have executed end to end before an 8-GPU node sees them (tests/test_e2e_gpu.py)")
     ap.add_argument("--gba-cams", type=int, default=500)
     ap.add_argument("--gba-points", type=int, default=100000)
+    ap.add_argument("--full", action="store_true", help="after the headline, run every side measurement as well: the chain without the detector and with the networks' maps, the "
+                                                        "networks alone with their FLOP/s, the rooflines and kernel figures, the optimisers / BA / matcher extras and the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the chain handed its caller for the last timed frame as DIR/<name>.npy (rank 0): the tracker's "
                                                           "Tcw and point / object counts, the networks' flow / depth / label image and the detector's labels and counts; float32, at most 64 MB")
     args = ap.parse_args()
@@ -203,10 +209,16 @@ def main():
     # HEADLINE: the chained, pipelined end-to-end frame rate
     n_total = args.prologue + args.warmup + args.steps
     scene = synth.convoy_scene(n_total + 1, w=W, h=H, seed=5 + 100 * rank)
-    frames = []
-    for k in range(n_total):
+
+    def render(k):
         g, d, f, m = scene.frame(k)
-        frames.append((synth.gray_to_bgr(g), np.ascontiguousarray(d, np.float32), np.ascontiguousarray(f, np.float32), np.ascontiguousarray(m, np.int32)))
+        return synth.gray_to_bgr(g), np.ascontiguousarray(d, np.float32), np.ascontiguousarray(f, np.float32), np.ascontiguousarray(m, np.int32)
+    # Scene3D.frame(k) only reads the scene and numpy releases the GIL inside its array operations: a pool of host threads renders the same frames (~0.25 s each on
+    # one core) several times faster than one loop.  At most 16 threads, shared by the ranks of one node.
+    from concurrent.futures import ThreadPoolExecutor
+    n_threads = max(1, min(16, len(os.sched_getaffinity(0))) // int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    with ThreadPoolExecutor(max_workers=n_threads) as pool:
+        frames = list(pool.map(render, range(n_total)))
     tmp = tempfile.mkdtemp(prefix="vido_bench_")
     cfg_path = os.path.join(tmp, "settings.yaml")
     write_settings(cfg_path, scene.K, W, H)
@@ -273,7 +285,7 @@ def main():
     # ---- the chain exactly as BASELINE's metric text words it ("flow+depth+track+local-BA"): the same pipeline with the detector left out (the tracker is handed the
     # renderer's mask either way, feed=given).  Reported next to the headline, which keeps the harder chain (the tracker needs a mask: configs[2] names Mask R-CNN).
     e2e_nodet = None
-    if world == 1 and not args.no_extra and not args.no_pipeline and args.feed == "given":
+    if args.full and world == 1 and not args.no_extra and not args.no_pipeline and args.feed == "given":
         try:
             slam.close()                                         # (one System per process at a time: the facade keeps its context in statics, as the reference's Frame does)
             slam2 = System(); slam2.Init(cfg_path, System.RGBD)
@@ -304,7 +316,7 @@ def main():
     # ---- the same chain with the tracker consuming the NETWORKS' maps (--feed nets): with random-init weights they carry no geometry, so the tracker's point counts differ
     # (reported); what the number shows is that the data dependency costs nothing beyond the completion event the headline already waits for
     e2e_feed_nets = None
-    if world == 1 and not args.no_extra and not args.no_pipeline and args.feed == "given" and slam is not None:
+    if args.full and world == 1 and not args.no_extra and not args.no_pipeline and args.feed == "given" and slam is not None:
         try:
             slam.close()
             slam3 = System(); slam3.Init(cfg_path, System.RGBD)
@@ -332,50 +344,51 @@ def main():
 
     # ---- the three networks alone (sequential, one stream each in turn): ms per forward and fp32 FLOP/s against the 157.3 TFLOP/s peak
     roofline_nets = {}
-    try:
-        ex = torch.as_tensor(frames[-1][0], device="cuda"); ex0 = torch.as_tensor(frames[-2][0], device="cuda")
-        def timed(fn, reps=5):
-            fn(); torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                fn()
-            b.record(); torch.cuda.synchronize()
-            return a.elapsed_time(b) / reps
-        from torch.utils.flop_counter import FlopCounterMode
-        def flops(fn):
-            hops = [o for o in (nodes.ops, getattr(nodes, "ops_flow", None)) if o is not None]
-            for o in hops:
-                o.gconv_flops = 0.0                                       # convolutions run by csrc/gconv.hip / conv1x1.hip / wino.hip are not torch ops: counted by the wrappers
-            with FlopCounterMode(display=False) as fc:                    # (as the direct convolutions they replace)
-                fn()
-            return float(fc.get_total_flops()) + sum(float(getattr(o, "gconv_flops", 0.0)) for o in hops)
-        legs = {"liteflownet": (lambda: (nodes.g_flow or nodes._flow_fn)(ex0, ex), lambda: nodes._flow_fn(ex0, ex)),
-                "monodepth2": (lambda: (nodes.g_depth or nodes._depth_fn)(ex), lambda: nodes._depth_fn(ex)),
-                "maskrcnn_x101_fpn": ((lambda: nodes.g_det(ex)) if nodes.g_det is not None else
-                                      (lambda: V.nets.analyse_image(nodes.mask_net, ex, feed=nodes.mask_feed, confidence=nodes.confidence, trunk=nodes.g_trunk)),
-                                      lambda: V.nets.analyse_image(nodes.mask_net, ex, feed=nodes.mask_feed, confidence=nodes.confidence))}
-        for name, (fast, eager) in legs.items():
-            ms = timed(fast); fl = flops(eager)
-            stage[name + "_ms"] = round(ms, 3)
-            roofline_nets[name] = {"bound": "mfma", "achieved": round(fl / (ms * 1e-3) / 1e12, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                   "frac": round(fl / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4), "gflop_per_frame": round(fl / 1e9, 1), "ms": round(ms, 3), "dtype": "fp32",
-                                   "note": "fp32-equivalent FLOPs of the node / its graph's replay time against the fp32 matrix instruction's peak; layers that compute their fp32 results on the 16-bit matrix instructions (config.net_arith) can take the fraction past 1"}
-        stage["nets_sum_ms"] = round(sum(stage[k + "_ms"] for k in legs), 3)
-        # the largest hand-written network kernel, alone: csrc/wino.hip on the detector's FPN / RPN convolution at P2 (256 -> 256 on 200 x 272), bias + ReLU included.
-        # `achieved` counts the multiply-adds the kernel ISSUES to the matrix pipe (Winograd domain: 16 per 2x2 output tile and channel pair instead of 36); `direct_equivalent`
-        # is the same launch priced as the direct convolution it replaces (what roofline_nets and the library's kernels are priced as).
-        if hasattr(nodes.ops, "wino3x3_bias_act"):
-            from vido_slam_amd.nets.ops import pack_wino3x3
-            wx = torch.randn(1, 256, 200, 272, device="cuda"); ww = torch.randn(256, 256, 3, 3) / 48.0; wb = torch.randn(256, device="cuda"); wu = pack_wino3x3(ww).cuda()
-            wms = timed(lambda: nodes.ops.wino3x3_bias_act(wx, wu, wb, 256, 0.0), reps=20)
-            direct = 2.0 * 9 * 256 * 256 * 200 * 272
-            roofline_nets["wino3x3_fpn_p2"] = {"kernel": "k_wino3x3<2,2,8>", "bound": "mfma", "achieved": round(direct * 16.0 / 36.0 / (wms * 1e-3) / 1e12, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                               "frac": round(direct * 16.0 / 36.0 / (wms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4), "direct_equivalent_tflops": round(direct / (wms * 1e-3) / 1e12, 1),
-                                               "avg_launch_ms": round(wms, 4), "workgroups": 852, "dtype": "fp32"}
-            del wx, ww, wb, wu
-    except Exception as e:
-        roofline_nets["error"] = "%s: %s" % (type(e).__name__, e)
+    if args.full:
+        try:
+            ex = torch.as_tensor(frames[-1][0], device="cuda"); ex0 = torch.as_tensor(frames[-2][0], device="cuda")
+            def timed(fn, reps=5):
+                fn(); torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    fn()
+                b.record(); torch.cuda.synchronize()
+                return a.elapsed_time(b) / reps
+            from torch.utils.flop_counter import FlopCounterMode
+            def flops(fn):
+                hops = [o for o in (nodes.ops, getattr(nodes, "ops_flow", None)) if o is not None]
+                for o in hops:
+                    o.gconv_flops = 0.0                                       # convolutions run by csrc/gconv.hip / conv1x1.hip / wino.hip are not torch ops: counted by the wrappers
+                with FlopCounterMode(display=False) as fc:                    # (as the direct convolutions they replace)
+                    fn()
+                return float(fc.get_total_flops()) + sum(float(getattr(o, "gconv_flops", 0.0)) for o in hops)
+            legs = {"liteflownet": (lambda: (nodes.g_flow or nodes._flow_fn)(ex0, ex), lambda: nodes._flow_fn(ex0, ex)),
+                    "monodepth2": (lambda: (nodes.g_depth or nodes._depth_fn)(ex), lambda: nodes._depth_fn(ex)),
+                    "maskrcnn_x101_fpn": ((lambda: nodes.g_det(ex)) if nodes.g_det is not None else
+                                          (lambda: V.nets.analyse_image(nodes.mask_net, ex, feed=nodes.mask_feed, confidence=nodes.confidence, trunk=nodes.g_trunk)),
+                                          lambda: V.nets.analyse_image(nodes.mask_net, ex, feed=nodes.mask_feed, confidence=nodes.confidence))}
+            for name, (fast, eager) in legs.items():
+                ms = timed(fast); fl = flops(eager)
+                stage[name + "_ms"] = round(ms, 3)
+                roofline_nets[name] = {"bound": "mfma", "achieved": round(fl / (ms * 1e-3) / 1e12, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                       "frac": round(fl / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4), "gflop_per_frame": round(fl / 1e9, 1), "ms": round(ms, 3), "dtype": "fp32",
+                                       "note": "fp32-equivalent FLOPs of the node / its graph's replay time against the fp32 matrix instruction's peak; layers that compute their fp32 results on the 16-bit matrix instructions (config.net_arith) can take the fraction past 1"}
+            stage["nets_sum_ms"] = round(sum(stage[k + "_ms"] for k in legs), 3)
+            # the largest hand-written network kernel, alone: csrc/wino.hip on the detector's FPN / RPN convolution at P2 (256 -> 256 on 200 x 272), bias + ReLU included.
+            # `achieved` counts the multiply-adds the kernel ISSUES to the matrix pipe (Winograd domain: 16 per 2x2 output tile and channel pair instead of 36); `direct_equivalent`
+            # is the same launch priced as the direct convolution it replaces (what roofline_nets and the library's kernels are priced as).
+            if hasattr(nodes.ops, "wino3x3_bias_act"):
+                from vido_slam_amd.nets.ops import pack_wino3x3
+                wx = torch.randn(1, 256, 200, 272, device="cuda"); ww = torch.randn(256, 256, 3, 3) / 48.0; wb = torch.randn(256, device="cuda"); wu = pack_wino3x3(ww).cuda()
+                wms = timed(lambda: nodes.ops.wino3x3_bias_act(wx, wu, wb, 256, 0.0), reps=20)
+                direct = 2.0 * 9 * 256 * 256 * 200 * 272
+                roofline_nets["wino3x3_fpn_p2"] = {"kernel": "k_wino3x3<2,2,8>", "bound": "mfma", "achieved": round(direct * 16.0 / 36.0 / (wms * 1e-3) / 1e12, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                                   "frac": round(direct * 16.0 / 36.0 / (wms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4), "direct_equivalent_tflops": round(direct / (wms * 1e-3) / 1e12, 1),
+                                                   "avg_launch_ms": round(wms, 4), "workgroups": 852, "dtype": "fp32"}
+                del wx, ww, wb, wu
+        except Exception as e:
+            roofline_nets["error"] = "%s: %s" % (type(e).__name__, e)
 
     out = {
         "metric": "frames/sec end-to-end (flow+depth+track+local-BA) at 640x480; BA iters/sec",
@@ -404,7 +417,6 @@ def main():
         "per_frame_counts": {k: round(v, 1) for k, v in counts.items()},
         "pose_translation_error_m": {"mean": round(float(np.mean(t_err[1:])), 4), "max": round(float(np.max(t_err[1:])), 4), "path_length_m": round(0.25 * (len(t_err) - 1), 2)},
         "net_setup_s": round(t_setup, 1),
-        "roofline_nets": roofline_nets,
         "parity_pin": "nets pinned by reference fixtures (LiteFlowNet, MonoDepth2 decoder, Mask R-CNN stage by stage; NMS / box decode by the reference's own KATs; ROI-Align and the "
                       "ResNet-18 encoder by independent float64 implementations written from the reference text); ORB / tracker / RANSAC / BA UNPINNED: the reference's OpenCV + g2o "
                       "core cannot be built in this image (no OpenCV / Eigen / CXSparse) and has no tests or fixtures of its own",
@@ -413,6 +425,13 @@ def main():
                             "the split-fp16 form of the 1x1 layers (round 6) is the first step under that floor"},
     }
     del e2e, slam
+    if not args.full:                                        # a plain run ends with its headline
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    out["roofline_nets"] = roofline_nets
 
     # =============================================================================================================================
     # roofline of the dominant hand-written front-end kernel, on configs[1] batched (64 frames in flight)

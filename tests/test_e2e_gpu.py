@@ -211,13 +211,13 @@ def test_two_chain_schedule_returns_the_same_maps(vido):
 
 
 def test_bench_two_ranks_on_one_gpu_prints_the_n2_line():
-    """`python bench.py --gpus 2 --oversubscribe`: the self-spawn through torch.distributed.run (the driver's launcher), two ranks (both on GPU 0, gloo), the replicated
+    """`python bench.py --gpus 2 --oversubscribe --full`: the self-spawn through torch.distributed.run (the driver's launcher), two ranks (both on GPU 0, gloo), the replicated
     per-frame chain with barrier + max-over-ranks timing, the landmark-sharded global BA with an all-reduce per LM trial, ONE JSON line from rank 0 with n_gpus = 2.
     The numbers mean nothing on one GPU; the point is that the N > 1 path has executed end to end before a multi-GPU node runs it (round-3 review, item 3c)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "3", "--warmup", "1", "--prologue", "3", "--cpu-baseline", "0",
-           "--gba-cams", "80", "--gba-points", "6000"]
+           "--gba-cams", "80", "--gba-points", "6000", "--full"]
     env = dict(os.environ); env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -228,3 +228,22 @@ def test_bench_two_ranks_on_one_gpu_prints_the_n2_line():
     g = d["extra"]["global_ba"]
     assert g["n_gpus"] == 2 and "gloo" in g["collective"] and g["lm_iterations"] >= 1 and g["chi2"][1] < g["chi2"][0]
     assert d["global_ba_iters_per_s"]["n_gpus"] == 2
+
+
+def test_plain_bench_run_prints_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: the headline chain, its stage breakdown and --dump-outputs, and none of the side measurements (each of those is a run of
+    its own behind --full)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prologue", "3", "--dump-outputs", str(tmp_path / "dump")]
+    env = dict(os.environ); env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
+    p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) < 0.01 * d["ms_per_step"] + 0.01
+    assert d["stage_ms"]["track_total_ms"] > 0 and d["per_frame_counts"]["keypoints"] > 0
+    assert not {"extra", "roofline", "roofline_nets", "cpu_baseline", "global_ba_iters_per_s"} & set(d), sorted(d)
+    assert {"flow", "depth", "mask", "pose_Tcw"} <= {f[:-4] for f in os.listdir(tmp_path / "dump")}

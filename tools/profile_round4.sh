@@ -14,8 +14,8 @@ has() { case " $WHAT " in *" $1 "*) return 0;; *) return 1;; esac; }
 stats() { f=$(find $1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -40 "$f" > $2; }
 if has tests; then timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_full.txt 2>&1; grep -E "passed|failed|error" $OUT/pytest_full.txt | tail -5 > $OUT/pytest_gpu.txt; tail -3 $OUT/pytest_gpu.txt; fi
 if has bench; then
-  timeout 900 python bench.py > $OUT/bench_e2e.json 2> $OUT/bench_e2e.err; echo "bench rc $?"
-  timeout 900 python bench.py --steps 200 --warmup 10 --no-extra --cpu-baseline 0 > $OUT/bench_e2e_200.json 2> $OUT/bench_e2e_200.err; echo "bench200 rc $?"
+  timeout 900 python bench.py --full > $OUT/bench_e2e.json 2> $OUT/bench_e2e.err; echo "bench rc $?"
+  timeout 900 python bench.py --full --steps 200 --warmup 10 --no-extra --cpu-baseline 0 > $OUT/bench_e2e_200.json 2> $OUT/bench_e2e_200.err; echo "bench200 rc $?"
 fi
 export TMPDIR=/tmp; cd /tmp
 if has e2e; then

@@ -18,8 +18,8 @@ WHAT="${*:-tests bench e2e fe pmc sq nets ba nodet c1}"
 has() { case " $WHAT " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has tests; then timeout 2400 python -m pytest tests -m gpu -q > $OUT/pytest_full.txt 2>&1; grep -E "passed|failed|error" $OUT/pytest_full.txt | tail -5 > $OUT/pytest_gpu.txt; tail -3 $OUT/pytest_gpu.txt; fi
 if has bench; then
-  timeout 900 python bench.py > $OUT/bench_e2e.json 2> $OUT/bench_e2e.err; echo "bench rc $?"
-  timeout 900 python bench.py --steps 200 --warmup 10 --no-extra --cpu-baseline 0 > $OUT/bench_e2e_200.json 2> $OUT/bench_e2e_200.err; echo "bench200 rc $?"
+  timeout 900 python bench.py --full > $OUT/bench_e2e.json 2> $OUT/bench_e2e.err; echo "bench rc $?"
+  timeout 900 python bench.py --full --steps 200 --warmup 10 --no-extra --cpu-baseline 0 > $OUT/bench_e2e_200.json 2> $OUT/bench_e2e_200.err; echo "bench200 rc $?"
 fi
 if has c1; then
   : > $OUT/conv1x1_microbench.txt

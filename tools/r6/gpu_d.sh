@@ -1,8 +1,9 @@
 #!/bin/bash
 # headline A/B (60 steps each)
-run() { tag=$1; shift; env "$@" timeout 400 python bench.py --steps 60 --no-extra --cpu-baseline 0 > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err; python - $tag <<'PY'
+OUT=${OUT:-bench_ab}; mkdir -p $OUT
+run() { tag=$1; shift; env "$@" timeout 400 python bench.py --full --steps 60 --no-extra --cpu-baseline 0 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err; python - $tag $OUT <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/bench_%s.json" % sys.argv[1]).read().strip().splitlines()[-1])
+d = json.loads(open("%s/bench_%s.json" % (sys.argv[2], sys.argv[1])).read().strip().splitlines()[-1])
 s = d["stage_ms"]
 print(sys.argv[1], d["value"], "ms/step", d["ms_per_step"], "det", s["maskrcnn_x101_fpn_ms"], "lfn", s["liteflownet_ms"], "trk", s["tracker_thread_ms"], "lba", s["local_ba_ms"], "wait_nets", s["tracker_wait_for_nets_ms"])
 PY
