@@ -338,6 +338,11 @@ int vido_conv1x1_set_arith(int arith);
 /* non-zero when a split-fp16 launch on this context (1x1, 3x3, fully connected, 2x2 transposed) met an activation outside fp16's range, an infinity or a NaN since the last
  * reset; read after the stream has been waited for.  reset != 0: read and clear in one atomic exchange. */
 int vido_conv1x1_range_flag(vido_ctx* ctx, int reset);
+/* Per-frame latch of that flag (csrc/rangelatch.hip): enqueues on the context's adopted stream (vido_set_stream) a one-lane launch that exchanges the flag with 0 and ORs
+ * the old value into *dst (a pinned host word or a device word, system-scope atomics).  In stream order *dst then holds the trips of the split-fp16 launches enqueued before
+ * the latch, and launches after it raise the flag afresh: a frame's latch names that frame even while the next frame's networks are already queued.  dst is not cleared:
+ * the caller zeroes it before the launches it is to cover.  Capturable. */
+int vido_range_latch(vido_ctx* ctx, unsigned* dst);
 int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope);
 /* 2 x 2 stride-2 transposed convolution + bias + leaky-ReLU of a batch as one split-fp16 GEMM with a scatter epilogue (the mask head's conv5_mask,
  * roi_heads/mask_head/roi_mask_predictors.py:17-31): x [n][cin][h][w] -> y [n][cout][2 h][2 w]; w_packed: pack_conv1x1 layout 3 of [(2 a + b) cout + co][ci] = w[ci][co][a][b]

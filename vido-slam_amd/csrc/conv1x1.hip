@@ -298,8 +298,9 @@ __global__ __launch_bounds__(256) void k_conv1x1_n112(C1Args A)
 //   * activations are taken as they are: full precision for 2.5e-4 <= |x| < 65504 (28 binades; a smaller |x| keeps an ABSOLUTE error <= 2^-36 = 1.5e-11, far below the
 //     rounding of the sum it enters), and a value past the range would turn into an infinity — so the split tracks max |x| beside its conversions (one v_maximum3 per pair) and a wave that met
 //     |x| >= 65504 or a NaN raises the context's range flag (the IEEE maximum v_maximum3_f32, not fmaxf: fmaxf returns the operand that is not a NaN)
-//     (vido_conv1x1_range_flag: the caller of the network checks it where it reads the detections back and can repeat the frame
-//     with vido_conv1x1_set_arith(2), the bf16 form, which has fp32's range).  The detector's activations stay below a few hundred.
+//     (vido_conv1x1_range_flag; per frame: vido_range_latch, csrc/rangelatch.hip, moves the flag into the frame's own word in stream order, and
+//     NetNodes(on_range="recompute") repeats a tripped frame's networks eagerly inside nets.range_safe — library / fp32 Winograd routes, fp32's range).
+//     The detector's activations stay below a few hundred.
 // Error against float64, both forms and the fp32 instruction: tests/test_maskrcnn_gpu.py (the bar: <= 1.5x the fp32 instruction's; measured 0.4 - 1.0x).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

@@ -229,9 +229,13 @@ class LiteFlowNet(nn.Module):
 
 
 @torch.no_grad()
-def analyse_flow(net, previous_bgr, current_bgr):
+def analyse_flow(net, previous_bgr, current_bgr, on_range=None):
     """run_flow_net.py:66-110: HxWx3 u8 BGR pair -> HxWx2 f32 flow (BGR->RGB, /255, bilinear resize to x32, forward,
-    bilinear resize back, rescale u by W/W', v by H/H').  The images enter in the network's own dtype (float64 for a .double() reference)."""
+    bilinear resize back, rescale u by W/W', v by H/H').  The images enter in the network's own dtype (float64 for a .double() reference).
+    on_range: None = unchecked; "raise" / "recompute" = the split-fp16 range check of this call alone (ops.range_checked: raise, or repeat the call in fp32's range)."""
+    if on_range is not None:
+        from .ops import range_checked
+        return range_checked(lambda safe: analyse_flow(net, previous_bgr, current_bgr), (net,), on_range, "LiteFlowNet")
     dev, dt = next(net.parameters()).device, next(net.parameters()).dtype
     def prep(img):
         t = (img.to(dev).flip(-1) if torch.is_tensor(img) else torch.as_tensor(img[:, :, ::-1].copy(), device=dev)).permute(2, 0, 1).to(dt).div(255.0).unsqueeze(0)   # a device tensor stays on the device

@@ -79,7 +79,7 @@ class _Bottleneck(nn.Module):              # resnet.py:277-372 (BottleneckWithFi
     def forward(self, x):
         if self._ep is not None and x.is_cuda:
             ep = self._ep; c1, c2 = self.conv1, self.conv2; ops = self._ops
-            b1x = x.shape[0] == 1
+            b1x = x.shape[0] == 1 and not getattr(ops, "_range_safe", 0)     # (ops.range_safe: the 1x1 layers on the library convolution)
             hw_in = x.shape[2] * x.shape[3]
             b1_done = False
             from .ops import conv1x1_fills_chip as fills
@@ -108,7 +108,7 @@ class _Bottleneck(nn.Module):              # resnet.py:277-372 (BottleneckWithFi
                 sc = ops.conv1x1_bias_act(x[:, :, ::2, ::2].contiguous(), self._wdp, self._bd, None, 1.0)
             else:
                 sc = ep(F.conv2d(x, self._wd, None, self.downsample[0].stride), self._bd, None, 1.0)
-            if (self._w3p is not None and y.shape[0] == 1 and ops.conv1x1_supported(y.shape[1], self._w3.shape[0], y.shape[2] * y.shape[3])
+            if (self._w3p is not None and b1x and y.shape[0] == 1 and ops.conv1x1_supported(y.shape[1], self._w3.shape[0], y.shape[2] * y.shape[3])
                     and (fills(self._w3.shape[0], y.shape[2] * y.shape[3]) or self._c1x1_min_tiles < 0)):
                 return ops.conv1x1_bias_act(y.contiguous(), self._w3p, self._b3, sc, 0.0)      # bias + shortcut + ReLU leave through the GEMM's accumulators: no pass over the output
             return ep(F.conv2d(y, self._w3), self._b3, sc.contiguous(), 0.0)
@@ -752,10 +752,15 @@ def image_to_feed(bgr, dev, feed=(1088, 800), ops=None):
 
 
 @torch.no_grad()
-def analyse_image(net, bgr, feed=(1088, 800), confidence=0.8, trunk=None):
+def analyse_image(net, bgr, feed=(1088, 800), confidence=0.8, trunk=None, on_range=None):
     """predictor.py:compute_prediction + select_top_predictions (:215-283) and run_mask_rcnn.py:create_pixel_masks (:83-123):
     HxWx3 u8 BGR -> (label image HxW u8 = sum of mask * class index, label indices).  The frame is area-resized to 800x1088
-    (W x H, cv2.INTER_AREA; third-party, restated with torch's area interpolation), flipped to RGB, NOT normalised."""
+    (W x H, cv2.INTER_AREA; third-party, restated with torch's area interpolation), flipped to RGB, NOT normalised.
+    on_range: None = unchecked; "raise" / "recompute" = the split-fp16 range check of this call alone (ops.range_checked; the recomputation runs the whole detector eagerly,
+    without `trunk`, whose captured launches are split-fp16)."""
+    if on_range is not None:
+        from .ops import range_checked
+        return range_checked(lambda safe: analyse_image(net, bgr, feed, confidence, None if safe else trunk), (net,), on_range, "the detector")
     dev = next(net.parameters()).device
     H, W = bgr.shape[:2]
     if trunk is not None:                                    # hipGraph-captured static part (pipeline.NetNodes): u8 HxWx3 BGR in -> (feats, logits, deltas)

@@ -1,6 +1,7 @@
 """torch <-> C-ABI glue for the network ops.  Device tensors are handed to the library as raw pointers
 (on_device=1); the ctx adopts torch's current stream (vido_set_stream) so launches are ordered with the
 surrounding torch kernels without any synchronisation."""
+import contextlib
 import ctypes as C
 import os
 import torch
@@ -29,8 +30,15 @@ def correlation_torch_reference(first, second, stride):
 class HipOps:
     """FunctionCorrelation / ROIAlign / nms / box decode on device tensors through libvido_slam_hip.so."""
 
+    _range_safe = 0                        # range_safe(): > 0 while a scope holds this object — every split-fp16 entry point declines (the callers' fp32 fallbacks run)
+
     def __init__(self, ctx):
         self.ctx = ctx
+
+    @property
+    def range_safe_active(self):
+        """True inside range_safe(): conv1x1_conv / conv1x1_bias_act callers, the direct 3x3, fc_h_linear and deconv2x2_conv take their fp32 routes."""
+        return self._range_safe > 0
 
     def _adopt_stream(self):
         st = torch.cuda.current_stream().cuda_stream
@@ -60,7 +68,7 @@ class HipOps:
         None; the packed weight is cached on the module."""
         w = conv.weight
         if (tuple(w.shape[2:]) != (2, 2) or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (0, 0) or tuple(conv.output_padding) != (0, 0) or tuple(conv.dilation) != (1, 1)
-                or conv.groups != 1 or not x.is_cuda or x.dtype != torch.float32 or os.environ.get("VIDO_NO_DECONV_H")):
+                or conv.groups != 1 or not x.is_cuda or x.dtype != torch.float32 or os.environ.get("VIDO_NO_DECONV_H") or self._range_safe):
             return None
         n, cin, H, W = (int(v) for v in x.shape); cout = int(w.shape[1])
         if not self.ctx.lib.vido_deconv2x2_supported(n, cin, cout, H, W):
@@ -217,6 +225,14 @@ class HipOps:
         returns the previous setting (vido_conv1x1_set_arith, process-wide)."""
         return int(self.ctx.lib.vido_conv1x1_set_arith(int(arith)))
 
+    def range_latch(self, dst):
+        """Enqueue on the current stream: dst |= this context's range flag, flag = 0 (vido_range_latch).  dst: an int32 tensor of one element or more (its first word), on the
+        device or pinned on the host; zero it before the launches it is to cover.  In stream order dst then holds the trips of the split-fp16 launches enqueued before the latch."""
+        assert dst.dtype == torch.int32 and dst.numel() >= 1 and dst.is_contiguous() and (dst.is_cuda or dst.is_pinned()), "range_latch: an int32 word on the device or pinned"
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_range_latch(self.ctx.h, C.c_void_p(dst.data_ptr())))
+        return dst
+
     def conv1x1_range_flag(self, reset=True):
         """non-zero when a split-fp16 launch met |x| >= 65504 since the last reset (its outputs are not valid); read after the stream has been waited for"""
         return int(self.ctx.lib.vido_conv1x1_range_flag(self.ctx.h, int(bool(reset))))
@@ -258,8 +274,8 @@ class HipOps:
         is cached on the module (per tile form) and rebuilt when the weight tensor changes."""
         w = conv.weight
         if (tuple(w.shape[2:]) != (1, 1) or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (0, 0) or conv.groups != 1 or not x.is_cuda or x.shape[0] != 1
-                or not self.conv1x1_supported(w.shape[1], w.shape[0], x.shape[2] * x.shape[3])):
-            return None
+                or self._range_safe or not self.conv1x1_supported(w.shape[1], w.shape[0], x.shape[2] * x.shape[3])):
+            return None                                                       # (range_safe: the library convolution, not the fp32 form, whose layout follows vido_conv1x1_set_arith)
         if not conv1x1_fills_chip(w.shape[0], x.shape[2] * x.shape[3]):
             return None
         layout = self.conv1x1_layout(w.shape[1], w.shape[0], x.shape[2] * x.shape[3])
@@ -348,7 +364,7 @@ class HipOps:
         # (round 6) chip-filling launches of >= 128-channel layers take the DIRECT kernel in split-fp16 arithmetic (csrc/conv3x3h.hip): 256 -> 256 on 200 x 272 in 216 us
         # against the Winograd kernel's 325, the mask head's 100 x 14 x 14 in 97 against 156; below ~128 workgroups one workgroup's
         # K loop is the launch's time and Winograd (its K-split form) stays faster.  VIDO_CONV3X3_H=0 keeps Winograd everywhere; VIDO_CONV3X3_H_MIN_WGS moves the threshold.
-        if (_CONV3X3_H_MIN_WGS > 0 and x.dtype == torch.float32 and self.ctx.lib.vido_conv3x3_h_supported(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3]))
+        if (_CONV3X3_H_MIN_WGS > 0 and x.dtype == torch.float32 and not self._range_safe and self.ctx.lib.vido_conv3x3_h_supported(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3]))
                 and self.ctx.lib.vido_conv3x3_h_workgroups(int(x.shape[0]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3])) >= (1 if int(w.shape[0]) == 64 else _CONV3X3_H_MIN_WGS)):
             # (64-channel layers: the direct kernel wins at every size — 128 -> 64 on 30 x 40: 18 us against the K-split Winograd form's 26; profiles/r6/conv3x3_h_direct.txt)
             key = (w.data_ptr(), w._version, str(x.device))
@@ -395,7 +411,7 @@ class HipOps:
         """nn.Linear `lin` + activation through fc_h when the layer has that form (outputs a multiple of 128, inputs a multiple of 32 S), else None; the packed weight is cached
         on the module and rebuilt when the weight tensor changes."""
         w = lin.weight
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or os.environ.get("VIDO_NO_FC_H") or int(self.ctx.lib.vido_fc_h_splitk(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]))) <= 0:
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or os.environ.get("VIDO_NO_FC_H") or self._range_safe or int(self.ctx.lib.vido_fc_h_splitk(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]))) <= 0:
             return None
         key = (w.data_ptr(), w._version, str(x.device))
         if getattr(lin, "_fch_key", None) != key:
@@ -621,6 +637,69 @@ class HipOps:
                                                            C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
                                                            C.c_void_p(out.data_ptr())))
         return out
+
+
+def _ops_of(obj, out):
+    """The HipOps objects `obj` launches through: itself, or those held by a module's sub-modules (attributes such as _ops / wino / fused, and the objects behind bound
+    methods such as LiteFlowNet's correlation / epilogue)."""
+    if isinstance(obj, HipOps):
+        out.setdefault(id(obj), obj)
+    elif isinstance(obj, torch.nn.Module):
+        for m in obj.modules():
+            for v in vars(m).values():
+                v = getattr(v, "__self__", v)
+                if isinstance(v, HipOps):
+                    out.setdefault(id(v), v)
+    else:
+        raise TypeError("range_safe: a HipOps or an nn.Module, not %s" % type(obj).__name__)
+    return out
+
+
+@contextlib.contextmanager
+def range_safe(*targets):
+    """Scope in which every split-fp16 entry point of the HipOps objects behind `targets` (HipOps objects or modules) declines, so that their callers take the fp32 routes they
+    already have: the 1x1 convolutions (conv1x1_conv, the fused bottleneck's conv1 / conv3 / shortcut, the FPN laterals) the library convolution, the direct 3x3 (wino3x3_conv)
+    the fp32 Winograd kernel, fc_h_linear F.linear, deconv2x2_conv F.conv_transpose2d.  The fp32 matrix kernels (gconv, convdirect, convsmall, correlation, Winograd) stay.
+    Results then have fp32's range: any finite activation is legal.  Only EAGER calls see the scope (a captured graph replays what it captured).  Nothing process-wide is read or
+    changed, and no cached packed weight is replaced or freed (a captured graph reads them): a layer that normally runs on the direct 3x3 gains a Winograd pack on first use."""
+    ops = list(_ops_of_all(targets))
+    for o in ops:
+        o._range_safe += 1
+    try:
+        yield ops
+    finally:
+        for o in ops:
+            o._range_safe -= 1
+
+
+def range_checked(run, targets, on_range, what):
+    """run(safe) under the per-call range check of the standalone node functions (analyse_flow / analyse_image, on_range="raise" | "recompute"): a latch of every context
+    behind `targets` before the call (it takes the trips of earlier launches away from this call's) and one after it, then a wait for the current stream.  A call that tripped
+    raises ("raise") or is repeated as run(True) inside range_safe(*targets) ("recompute": fp32's range, no split-fp16 launch)."""
+    if on_range not in ("raise", "recompute"):
+        raise ValueError("on_range: None, 'raise' or 'recompute', not %r" % (on_range,))
+    ops = list(_ops_of_all(targets))
+    words = torch.zeros((2, max(len(ops), 1)), dtype=torch.int32).pin_memory()
+    for i, o in enumerate(ops):
+        o.range_latch(words[0, i:i + 1])
+    out = run(False)
+    for i, o in enumerate(ops):
+        o.range_latch(words[1, i:i + 1])
+    torch.cuda.current_stream().synchronize()
+    if not bool(words[1].any()):
+        return out
+    if on_range == "raise":
+        raise RuntimeError("split-fp16: an activation of %s left the range of the arithmetic (|x| >= 65504, an infinity or a NaN); its outputs are not valid — "
+                           "on_range=\"recompute\" repeats the call in fp32's range" % what)
+    with range_safe(*targets):
+        return run(True)
+
+
+def _ops_of_all(targets):
+    out = {}
+    for t in targets:
+        _ops_of(t, out)
+    return out.values()
 
 
 _C1X1_MIN_TILES = int(os.environ.get("VIDO_CONV1X1_MIN_TILES", "100"))      # (160 through round 5: the fp32-instruction kernel lost to the library at layer4's 112 tiles; the split-bf16 one wins there)

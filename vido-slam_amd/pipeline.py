@@ -126,10 +126,23 @@ class NetNodes:
     round 2 had measured any overlap slower because its detector head still ran eagerly); the tracker of the previous frame overlaps with all of it (EndToEnd) — and returns device tensors in the tracker's input types (run_vido.cc:28-37: depth MONO16 -> CV_32F,
     mask MONO8 -> CV_32SC1, flow 32FC2).  optimize: frozen batch norms folded into the convolutions + fused HIP epilogues
     (nets/fuse.py); graphs: the static-shape parts (all of LiteFlowNet and MonoDepth2 incl. their resize wrappers, Mask R-CNN's backbone +
-    FPN + RPN head) are captured into hipGraphs."""
+    FPN + RPN head) are captured into hipGraphs.
+
+    on_range: what a frame whose split-fp16 launches left fp16's range (|x| >= 65504, an infinity or a NaN: its outputs are not valid) gets.  "raise" (default): the caller's
+    check_conv1x1_range raises, the sequence stops.  "recompute": infer() ends each frame with a latch of both contexts' range flags into that frame's own words
+    (vido_range_latch, in stream order), and the caller recomputes a tripped frame's networks in fp32's range (recompute(); infer_checked() does it all; EndToEnd does it
+    before the frame is tracked).  Only LiteFlowNet (its context) and the detector launch split-fp16 kernels; MonoDepth2 shares the detector's context and launches none."""
+
+    RANGE_MODES = ("raise", "recompute")
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
-                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True):
+                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise"):
+        if on_range not in self.RANGE_MODES:
+            raise ValueError("on_range: one of %s, not %r" % (self.RANGE_MODES, on_range))
+        self.on_range = on_range
+        self.range_recomputes = {"flow": 0, "detector": 0}           # networks recomputed in fp32's range (on_range="recompute")
+        self._range_words = None                                      # infer()'s words when the caller passes none (pinned int32 [flow context, detector context])
+        self.last_range = None
         self.ctx, self.h, self.w = ctx, height, width
         self.mask_feed, self.depth_feed, self.confidence = mask_feed, depth_feed, confidence
         if miopen_find:
@@ -213,9 +226,12 @@ class NetNodes:
                         torch.cuda.synchronize()
 
     @torch.no_grad()
-    def infer(self, prev_bgr, cur_bgr):
+    def infer(self, prev_bgr, cur_bgr, range_words=None):
         """prev_bgr / cur_bgr: u8 HxWx3 device tensors.  Returns (flow HxWx2 f32, depth HxW f32, mask HxW i32, labels, events): work enqueued on the caller's stream after
-        this call sees the complete outputs (the caller's stream waits for the side stream's events); another stream or the host waits for the three events."""
+        this call sees the complete outputs (the caller's stream waits for the side stream's events); another stream or the host waits for the three events.
+        range_words (pinned int32 [2], or on_range="recompute": NetNodes' own, valid until the next call; self.last_range names them): zeroed, then the frame's range flags
+        of the flow context / the detector context are latched into words 0 / 1 on the caller's stream after the three events — they hold this frame's trips alone,
+        readable on the host once the caller's stream has passed this point."""
         cur = torch.cuda.current_stream()
         ss = [s or cur for s in self.streams] if self.streams else [cur, cur, cur]
         for s in ss:
@@ -244,7 +260,60 @@ class NetNodes:
         for s, e in zip(ss, (e0, e1, e2)):                          # the outputs are valid in stream order on the CALLER's stream, whatever queue produced them
             if s is not cur:
                 cur.wait_event(e)
+        if range_words is None and self.on_range == "recompute":
+            if self._range_words is None:
+                self._range_words = torch.zeros((2,), dtype=torch.int32).pin_memory()
+            range_words = self._range_words
+        self.last_range = range_words
+        if range_words is not None:                                   # (the words' previous frame has been read: the caller's contract)
+            range_words.zero_()
+            self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
+
+    @torch.no_grad()
+    def recompute(self, prev_bgr, cur_bgr, flow=True, detector=True):
+        """The networks of a frame whose split-fp16 launches left the range, again in fp32's range: eager forwards inside nets.range_safe (no split-fp16 launch; nothing a
+        captured graph reads is replaced) on the caller's stream.  Returns {"flow": HxWx2 f32 or None, "detector": (mask HxW i32, labels, n_lab, n_det) or None}; n_lab /
+        n_det are None after the dynamic head (no static detector).  The caller serialises it with infer() (the nodes' host-side state has one user at a time)."""
+        out = {"flow": None, "detector": None}
+        if flow:
+            with _nets.range_safe(self.flow_net):
+                out["flow"] = self._flow_fn(prev_bgr, cur_bgr).contiguous()
+            self.range_recomputes["flow"] += 1
+        if detector and not getattr(self, "skip_detector", False):
+            with _nets.range_safe(self.mask_net):
+                if self.g_det is not None:                              # the static head, eagerly (its trunk without the captured graph): the graph's output form
+                    mask, labels, n_lab, n_det = self._det_fn(cur_bgr)
+                    out["detector"] = (mask, labels, n_lab, n_det)
+                else:
+                    mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence)
+                    out["detector"] = (mask_u8.to(torch.int32), labels, None, None)
+            self.range_recomputes["detector"] += 1
+        return out
+
+    @torch.no_grad()
+    def infer_checked(self, prev_bgr, cur_bgr):
+        """infer() for callers outside EndToEnd, with this frame's range check: infer, wait for the caller's stream, and when a context tripped raise (on_range="raise") or
+        recompute the tripped networks (on_range="recompute", see recompute()).  Returns infer()'s tuple; its events are recorded after any recomputation."""
+        if self._range_words is None:
+            self._range_words = torch.zeros((2,), dtype=torch.int32).pin_memory()
+        flow, depth, mask, labels, evs = self.infer(prev_bgr, cur_bgr, range_words=self._range_words)
+        torch.cuda.current_stream().synchronize()
+        hit_flow, hit_det = bool(self._range_words[0]), bool(self._range_words[1])
+        if not (hit_flow or hit_det):
+            return flow, depth, mask, labels, evs
+        if self.on_range == "raise":
+            raise RuntimeError("split-fp16: an activation of the frame left the range of the arithmetic (|x| >= 65504, an infinity or a NaN) on the %s context; the frame's "
+                               "outputs are not valid — NetNodes(on_range=\"recompute\") recomputes such frames in fp32's range"
+                               % " and ".join(n for n, h in (("flow", hit_flow), ("detector / depth", hit_det)) if h))
+        r = self.recompute(prev_bgr, cur_bgr, flow=hit_flow, detector=hit_det)
+        if r["flow"] is not None:
+            flow = r["flow"]
+        if r["detector"] is not None:
+            mask, labels, n_lab, n_det = r["detector"]
+            self.last_counts = None if n_lab is None else (n_lab, n_det)
+        e = torch.cuda.Event(); e.record()
+        return flow, depth, mask, labels, (e, e, e)
 
     def check_conv1x1_range(self):
         """The split-fp16 kernels (csrc/conv1x1.hip 1x1 and 2x2 transposed, conv3x3h.hip, fch.hip: the default arithmetic) take finite activations below 65504; a launch that
@@ -259,13 +328,18 @@ class NetNodes:
                                "kernels, the 1x1 ones on split-bf16)" % " and ".join(hit))
 
     @torch.no_grad()
-    def redo_detector_if_overflowed(self, cur_bgr, n_det_host):
+    def redo_detector_if_overflowed(self, cur_bgr, n_det_host, range_safe=False):
         """The static head stores detections_per_img slots; score ties at the reference's kthvalue cut (box_head/inference.py:131-137) can leave more.  The caller reads
-        n_det with the frame's hand-over and, in that (rare) case, recomputes the label image through the dynamic head."""
+        n_det with the frame's hand-over and, in that (rare) case, recomputes the label image through the dynamic head (range_safe: a frame recomputed in fp32's range —
+        eagerly inside nets.range_safe, without the trunk's graph)."""
         cap = self.mask_net.config.detections_per_img
         if n_det_host <= cap:
             return None
         self.det_overflows += 1
+        if range_safe:
+            with _nets.range_safe(self.mask_net):
+                mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence)
+            return mask_u8.to(torch.int32), labels
         mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk)
         return mask_u8.to(torch.int32), labels
 
@@ -284,7 +358,11 @@ class EndToEnd:
 
     feed = "nets": the tracker consumes the networks' outputs.  feed = "given": the networks run at full cost and their outputs are parked exactly as above, but the
     tracker is handed caller-supplied depth / flow / mask maps of the frame (uploaded next to the BGR frame) — for synthetic benchmarks, where random-weight networks
-    produce maps without any geometry for the tracker to work on.  Frame k is still tracked only after its three forwards have completed (same event)."""
+    produce maps without any geometry for the tracker to work on.  Frame k is still tracked only after its three forwards have completed (same event).
+
+    nodes.on_range = "recompute": each ring slot carries the frame's two range words (NetNodes.infer latches both contexts into them); before frame k is tracked the worker
+    waits for the frame, reads ITS words (not the live flags, which may already hold frame k + 1's trips) and, when one is set, recomputes that network in fp32's range
+    (NetNodes.recompute, on the network stream under net_lock) into the frame's ring buffers.  range_frames lists the frames recomputed, nodes.range_recomputes counts per network."""
 
     RING = 4                                  # buffer sets: the tracker keeps the maps of the previous frame in use (mask / flow of frame k-1 during frame k)
 
@@ -298,7 +376,8 @@ class EndToEnd:
         h, w = nodes.h, nodes.w; dev = nodes.dev
         pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()
         self.host = [dict(bgr=pin((h, w, 3), torch.uint8), flow=pin((h, w, 2), torch.float32), depth=pin((h, w), torch.float32), mask=pin((h, w), torch.int32),
-                          counts=pin((2,), torch.int32)) for _ in range(self.RING)]
+                          counts=pin((2,), torch.int32), range=pin((2,), torch.int32)) for _ in range(self.RING)]
+        self.range_frames = []                # frames whose networks were recomputed in fp32's range (nodes.on_range == "recompute")
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         self.dev = [dict(bgr=mk((h, w, 3), torch.uint8), flow=mk((h, w, 2), torch.float32), depth=mk((h, w), torch.float32), mask=mk((h, w), torch.int32),
                          gflow=mk((h, w, 2), torch.float32), gdepth=mk((h, w), torch.float32), gmask=mk((h, w), torch.int32)) for _ in range(self.RING)]
@@ -327,10 +406,15 @@ class EndToEnd:
                     # tail, instead of starting — as the frame's first heavy tracker work — against the just-enqueued networks of frame k + 1 (VIDO_TRACK_NO_PREFETCH=1: as before)
                     if self._prefetch and not _os.environ.get("VIDO_E2E_SKIP_TRACK"):
                         self.system.PrefetchImageDevice(db["bgr"].data_ptr(), 3, self.nodes.w, self.nodes.h, img_ev.cuda_event)
+                    safe = False
+                    if self.nodes.on_range == "recompute":               # the frame's own range words: a host wait for its event, with or without the static head
+                        ev.synchronize()
+                        safe = self._recompute_if_tripped(k, slot)
                     if self.nodes.g_det is not None:                     # the static head's overflow flag (rare): needs the frame's counts, i.e. a host wait for this one event
                         ev.synchronize()
-                        self._redo_if_overflowed(slot)
-                        self.nodes.check_conv1x1_range()                 # (the frame's networks are complete: ev)
+                        self._redo_if_overflowed(slot, range_safe=safe)
+                        if self.nodes.on_range == "raise":
+                            self.nodes.check_conv1x1_range()             # (the frame's networks are complete: ev)
                     t1 = _time.perf_counter()
                     if not _os.environ.get("VIDO_E2E_SKIP_TRACK"):
                         d, f, m = (db["depth"], db["flow"], db["mask"]) if self.feed == "nets" else (db["gdepth"], db["gflow"], db["gmask"])
@@ -338,7 +422,10 @@ class EndToEnd:
                                                         float(k), self.n_image)
                 else:
                     ev.synchronize()                                     # networks + hand-over copies of frame k are complete
-                    self.nodes.check_conv1x1_range()
+                    if self.nodes.on_range == "recompute":
+                        self._recompute_if_tripped(k, slot)
+                    else:
+                        self.nodes.check_conv1x1_range()
                     t1 = _time.perf_counter()
                     if self.feed == "nets":
                         d, f, m = hb["depth"].numpy(), hb["flow"].numpy(), hb["mask"].numpy()
@@ -356,14 +443,38 @@ class EndToEnd:
                 self.q.task_done()
 
     @torch.no_grad()
-    def _redo_if_overflowed(self, slot):
+    def _recompute_if_tripped(self, k, slot):
+        """Frame k's range words (its networks are complete) -> recompute what tripped into the frame's ring buffers (device, and the host maps in the host hand-over) and
+        counts.  True when the detector was recomputed (an overflow redo of that frame must stay in fp32's range too)."""
+        hb, db = self.host[slot], self.dev[slot]
+        hit_flow, hit_det = bool(hb["range"][0]), bool(hb["range"][1])
+        if not (hit_flow or hit_det):
+            return False
+        prev = self.dev[(slot - 1) % self.RING]["bgr"] if k > 0 else db["bgr"]          # (frame k - 1's slot is not reused before frame k has been tracked)
+        # as in _redo_if_overflowed: on the network stream (stream order protects the contexts' scratch) and under the lock push() holds around infer()
+        with self.net_lock, torch.cuda.stream(self.net_stream):
+            r = self.nodes.recompute(prev, db["bgr"], flow=hit_flow, detector=hit_det)
+            if r["flow"] is not None:
+                db["flow"].copy_(r["flow"])
+            if r["detector"] is not None:
+                db["mask"].copy_(r["detector"][0])
+            self.net_stream.synchronize()
+        if r["detector"] is not None and r["detector"][2] is not None:
+            hb["counts"][0] = int(r["detector"][2]); hb["counts"][1] = int(r["detector"][3])
+        if self.handover != "device" and self.feed == "nets":
+            hb["flow"].copy_(db["flow"]); hb["mask"].copy_(db["mask"])
+        self.range_frames.append(k)
+        return r["detector"] is not None
+
+    @torch.no_grad()
+    def _redo_if_overflowed(self, slot, range_safe=False):
         n_det = int(self.host[slot]["counts"][1])
         if n_det <= self.nodes.mask_net.config.detections_per_img:
             return
         # on the NETWORK stream (the detector's HIP ops share one device scratch, which stream order protects) and under the lock push() holds around infer():
         # the host-side state of the nodes (adopted stream, ctx scratch pointers, static trunk buffers) is not protected by stream order (ADVICE r3)
         with self.net_lock, torch.cuda.stream(self.net_stream):
-            r = self.nodes.redo_detector_if_overflowed(self.dev[slot]["bgr"], n_det)
+            r = self.nodes.redo_detector_if_overflowed(self.dev[slot]["bgr"], n_det, range_safe=range_safe)
             if r is not None:
                 self.dev[slot]["mask"].copy_(r[0])
             self.net_stream.synchronize()
@@ -390,7 +501,7 @@ class EndToEnd:
                 hb["given"] = (hb["depth"].numpy().copy(), hb["flow"].numpy().copy(), hb["mask"].numpy().copy())
         prev = cur if self.prev is None else self.prev                   # first frame: RunNet has no previous image yet; the tracker ignores the flow of frame 0's predecessor
         with self.net_lock:
-            flow, depth, mask, labels, evs = self.nodes.infer(prev, cur)
+            flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None)
         # graph outputs are static buffers that the next replay overwrites: park them in this slot's device buffers (three device-to-device copies of 4.8 MB in stream order)
         if self.nodes.streams is not None:
             for e in evs:
