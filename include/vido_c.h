@@ -99,6 +99,17 @@ int vido_orb_read_candidates(vido_ctx* ctx, int frame, int level, uint32_t* out,
  * [5] total wall [6] scan+gather [7] number of FAST candidates in the batch */
 int vido_orb_last_timing(const vido_ctx* ctx, float ms[8]);
 
+/* Orientation, rBRIEF descriptor and Hamming distance at CALLER-GIVEN points (not detected keypoints) of pyramid slab `frame`: the slab of the most recent extraction or
+ * prefetch of that frame index of the context (no reference call site: the reference never evaluates a descriptor away from a keypoint; defined by the oracle's per-point
+ * vo_ic_angle / vo_brief on the build's own pyramid).  xyl [n*3]: x, y in LEVEL coordinates (integer pixels of that pyramid level), level.  For point i: angle_out[i] is the
+ * intensity-centroid angle over the radius-15 disc of the unblurred level and desc_out[32 i ..] the steered rBRIEF on the blurred level, both exactly what the extractor
+ * computes for a keypoint at that pixel; dist_out[i] = Hamming distance between that descriptor and ref_desc[32 i ..], computed in the same launch.  Any output may be NULL
+ * (dist_out needs ref_desc: VIDO_E_INVALID without).  A point closer than 19 px (the extractor's edge margin) to a border of its level, or with a level outside
+ * [0, n_levels), is INVALID: angle -1, zero descriptor, distance -1, and nothing is read for it.  n == 0 is a successful no-op.  on_device != 0: every pointer is a device
+ * pointer (descriptors 4-byte aligned) and the call only enqueues on the ctx stream; otherwise it returns when the results are in the caller's arrays.  Results depend
+ * neither on n nor on the order of the points.  Needs compute_descriptors != 0 for desc_out / dist_out (the blurred pyramid). */
+int vido_orb_describe_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, const uint8_t* ref_desc, float* angle_out, uint8_t* desc_out, int32_t* dist_out, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device
@@ -585,6 +596,14 @@ int         vido_system_prefetch_image_device(vido_system* sys, const void* im_d
 int         vido_system_track_rgbd_device(vido_system* sys, const void* im_dev, int channels, int width, int height, float* depth_dev, const float* flow_dev,
                                           const int32_t* mask_dev, void* ready_event, double timestamp, int n_image, float Tcw_out[16]);
 int         vido_system_get_stats(const vido_system* sys, vido_system_stats* out);
+/* Verify.Descriptor: 1: static points of the last frame whose seed descriptor was compared with the frame at the flow-predicted position
+ * (n_checked: those with a distance, i.e. a seed and a position outside the extractor's edge margin) and how many of them exceeded Verify.MaxHamming (n_rejected).
+ * Both 0 with the option off.  (A call of its own: vido_system_stats keeps the layout existing callers see.) */
+int         vido_system_get_verify_stats(const vido_system* sys, int* n_checked, int* n_rejected);
+/* Debug read of the same frame's per-point state, index-aligned with the frame's static list (any array may be NULL): xy [2n] the position that was checked, prev_xy [2n]
+ * the last frame's point it came from, xyl [3n] = lrintf(xy / scale[level]) and the seed's level (-1 x 3: no seed), dist [n] (-1: no evidence), rejected [n], seed_desc [32n].
+ * *n_out = n (0 with the option off or before the second frame); VIDO_E_CAPACITY if n > cap. */
+int         vido_system_get_verify_points(const vido_system* sys, float* xy, float* prev_xy, int32_t* xyl, int32_t* dist, uint8_t* rejected, uint8_t* seed_desc, int cap, int* n_out);
 int         vido_system_save_results(vido_system* sys, const char* prefix);
 /* the vido_ctx the system's tracker runs on (NULL before the first frame): lets a caller share the device / query timings */
 vido_ctx*   vido_system_context(vido_system* sys);

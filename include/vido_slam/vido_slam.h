@@ -96,6 +96,13 @@ public:
     std::vector<int> nModLabel, nSemPosition, nStaInlierID, nDynInlierID; std::vector<bool> bObjStat;
     std::vector<cv::Mat> vObjMod, vObjCentre3D; std::vector<cv::Point2f> vSpeed;
     std::vector<std::vector<int> > vnObjID, vnObjInlierID;
+    /* extension (Verify.Descriptor: 1): the ORB keypoint that SEEDED each static point — its pyramid level (-1: no keypoint behind the point, UseSampleFeature = 1) and
+       its 256-bit descriptor (32 bytes per point) — index-aligned with mvStatKeysTmp / mvCorres (…Tmp) and with mvStatKeys (after the hand-over); kept for the life of the
+       track.  mvStatVerifyXYL (x, y in level coordinates, level) / mvStatVerifyDist: where this frame's static points were evaluated and the Hamming distance to the seed
+       (-1: no evidence — no seed, or the point is inside the extractor's edge margin); mvStatVerifyRejected[i] != 0: left out of the camera pose and not propagated. */
+    std::vector<int> mvStatSeedLevelTmp, mvStatSeedLevel; std::vector<unsigned char> mvStatSeedDescTmp, mvStatSeedDesc;
+    std::vector<int> mvStatVerifyXYL, mvStatVerifyDist; std::vector<unsigned char> mvStatVerifyRejected;
+    std::vector<float> mvStatVerifyXY;      /* per point: its position when it was checked (x, y) and the last frame's point it came from (x, y) */
     Frame *mpPrevFrame = nullptr, *mpNextFrame = nullptr;
 };
 
@@ -176,6 +183,11 @@ public:
     std::vector<std::vector<std::pair<int, int> > > GetDynamicTrackNew();
     void RenewFrameInfo(const std::vector<int>& TM_sta);
     void UpdateMask();
+    /* extension (Verify.Descriptor: 1): compares every static point's seed descriptor with the rBRIEF of the current frame at its flow-predicted position
+       (vido_orb_describe_points, one launch per frame) and marks the points whose distance exceeds Verify.MaxHamming; GetVerifyStats: counts of the last frame */
+    void VerifyStaticDescriptors();
+    void GetVerifyStats(int* n_checked, int* n_rejected) const { if (n_checked) *n_checked = nVerifyChecked; if (n_rejected) *n_rejected = nVerifyRejected; }
+    bool bVerifyDescriptor = false; int nVerifyMaxHamming = 64, nVerifyChecked = 0, nVerifyRejected = 0;
 
     enum eTrackingState { NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2 };
     enum eDataState { OMD = 1, KITTI = 2, KAIST = 3 };

@@ -213,6 +213,14 @@ void ORBextractor::operator()(cv::InputArray image_, cv::InputArray, std::vector
 // ---- Frame ----------------------------------------------------------------------------------------------------------
 long unsigned int Frame::nNextId = 0;
 static float g_ms_orb = 0, g_ms_lists = 0;      // wall time of the last Frame's extractor call / list stage (vido_system_stats.ms_orb / ms_lists)
+static bool g_verify_desc = false;              // Verify.Descriptor of the live Tracking: Frame keeps the seed descriptor / level of every static point (off: no seed vectors at all)
+// seed of static point k of a list under construction: the ORB keypoint `key` of F (level + descriptor row), or "none" (key < 0: a sampled point without a keypoint behind it)
+static void push_seed(const Frame& F, int key, std::vector<int>& level, std::vector<unsigned char>& desc)
+{
+    const size_t o = desc.size(); desc.resize(o + 32, 0);
+    if (key < 0 || key >= F.mDescriptors.rows) { level.push_back(-1); return; }
+    level.push_back(F.mvKeys[key].octave); memcpy(&desc[o], F.mDescriptors.ptr<uint8_t>(key), 32);
+}
 
 Frame::Frame(const cv::Mat& imGray, const cv::Mat& imDepth, const cv::Mat& imFlow, const cv::Mat& maskSEM, const double& timeStamp,
              ORBextractor* extractor, cv::Mat& K, cv::Mat& distCoef, const float& bf, const float& thDepth, const float& thDepthObj, const int& UseSampleFea)
@@ -250,6 +258,7 @@ Frame::Frame(const cv::Mat& imGray, const cv::Mat& imDepth, const cv::Mat& imFlo
         mvCorres.push_back(cv::KeyPoint(scorr[2 * i], scorr[2 * i + 1], 0, 0, 0, kp.octave, -1));
         mvFlowNext.push_back(cv::Point2f(sflow[2 * i], sflow[2 * i + 1]));
         mvStatDepthTmp.push_back(sdep[i]);
+        if (g_verify_desc) push_seed(*this, UseSampleFea != 0 ? -1 : sidx[i], mvStatSeedLevelTmp, mvStatSeedDescTmp);
     }
     N_s_tmp = (int)mvStatKeysTmp.size();
     for (int i = 0; i < no; i++) {                                                 // Frame.cc:184-211
@@ -872,6 +881,8 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
     nWINDOW_SIZE = (int)num(kv, "WINDOW_SIZE", 20); nOVERLAP_SIZE = (int)num(kv, "OVERLAP_SIZE", 4); nUseSampleFea = (int)num(kv, "UseSampleFeature", 0);
     if (kv.count("Joint")) bJoint = num(kv, "Joint") != 0;
     if (kv.count("RansacSeed")) ransac_seed = (unsigned)num(kv, "RansacSeed");
+    bVerifyDescriptor = num(kv, "Verify.Descriptor", 0) != 0; nVerifyMaxHamming = (int)num(kv, "Verify.MaxHamming", 70);      // (70: profiles/r8/descriptor_verify.txt)
+    g_verify_desc = bVerifyDescriptor;
     all_timing.assign(5, 0.f);
 }
 Tracking::~Tracking() { delete mpORBextractorLeft; }
@@ -967,6 +978,11 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
         for (int i = 0; i < no; i++) { oxy[2 * i] = F->mvObjKeys[i].pt.x; oxy[2 * i + 1] = F->mvObjKeys[i].pt.y; }
         if (no) check(vido_gather_object_depth_label(c, slot_cur_, oxy.data(), no, mThDepthObj, F->mvObjDepth.data(), F->vSemObjLabel.data()), "gather_object");
         TemperalMatch.assign(F->N_s, -1);
+        nVerifyChecked = nVerifyRejected = 0;
+        if (bVerifyDescriptor) {                               // the seeds travel with the points (last.mvCorres is index-aligned with last.mvStatKeysTmp); then one launch for the frame
+            F->mvStatSeedLevel = mpLastFrame->mvStatSeedLevelTmp; F->mvStatSeedDesc = mpLastFrame->mvStatSeedDescTmp;
+            VerifyStaticDescriptors();
+        }
     }
     mpCurrentFrame->vObjLabel.assign(mpCurrentFrame->mvObjKeys.size(), -2);
     ms_frame = ms_since(t_st);
@@ -975,6 +991,41 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
     mImGrayLast = mImGray; mSegMapLast = mSegMap; mFlowMapLast = mFlowMap;      // :777-780
     ms_total = ms_since(t_grab);
     return mpCurrentFrame->mTcw.clone();
+}
+
+// Verify.Descriptor (no reference counterpart: the reference believes every flow vector).  The extraction of the current frame has just been collected,
+// so its pyramid and blurred pyramid are resident in slab 0 of the tracker's context: every static point that carries a seed is evaluated at lrintf(p / scale[level]) of the
+// seed's level, the distances alone come back (4 bytes per point), and dist > Verify.MaxHamming marks the point.  -1 (inside the edge margin) keeps it: no evidence is not
+// evidence against.  Points without a seed (UseSampleFeature = 1) are not sent at all.
+void Tracking::VerifyStaticDescriptors()
+{
+    Frame* F = mpCurrentFrame; const int n = F->N_s;
+    F->mvStatVerifyXYL.assign(3 * (size_t)n, -1); F->mvStatVerifyDist.assign(n, -1); F->mvStatVerifyRejected.assign(n, 0);
+    F->mvStatVerifyXY.resize(4 * (size_t)n);                   // (the pose optimisation moves mvStatKeys afterwards: the read-back wants the positions that were checked)
+    for (int i = 0; i < n; i++) { F->mvStatVerifyXY[4 * (size_t)i] = F->mvStatKeys[i].pt.x; F->mvStatVerifyXY[4 * (size_t)i + 1] = F->mvStatKeys[i].pt.y;
+                                  F->mvStatVerifyXY[4 * (size_t)i + 2] = mpLastFrame->mvStatKeys[i].pt.x; F->mvStatVerifyXY[4 * (size_t)i + 3] = mpLastFrame->mvStatKeys[i].pt.y; }
+    if ((int)F->mvStatSeedLevel.size() != n || (int)F->mvStatSeedDesc.size() != 32 * n) { F->mvStatSeedLevel.assign(n, -1); F->mvStatSeedDesc.assign(32 * (size_t)n, 0); return; }
+    const std::vector<float> scale = mpORBextractorLeft->GetScaleFactors();
+    std::vector<int32_t> xyl, dist, which; std::vector<uint8_t> ref;
+    for (int i = 0; i < n; i++) {
+        const int l = F->mvStatSeedLevel[i];
+        if (l < 0 || l >= (int)scale.size()) continue;
+        const int x = (int)lrintf(F->mvStatKeys[i].pt.x / scale[l]), y = (int)lrintf(F->mvStatKeys[i].pt.y / scale[l]);
+        F->mvStatVerifyXYL[3 * (size_t)i] = x; F->mvStatVerifyXYL[3 * (size_t)i + 1] = y; F->mvStatVerifyXYL[3 * (size_t)i + 2] = l;
+        xyl.push_back(x); xyl.push_back(y); xyl.push_back(l); which.push_back(i);
+        ref.insert(ref.end(), F->mvStatSeedDesc.begin() + 32 * (size_t)i, F->mvStatSeedDesc.begin() + 32 * (size_t)i + 32);
+    }
+    const int m = (int)which.size();
+    if (m == 0) return;
+    dist.resize(m);
+    vido_ctx* c = g_ctx;
+    if (timed_call([&]() -> int { return vido_orb_describe_points(c, 0, xyl.data(), m, ref.data(), nullptr, nullptr, dist.data(), 0); }, "orb_describe_points") != VIDO_OK) throw std::runtime_error(vido_last_error(c));
+    for (int k = 0; k < m; k++) {
+        F->mvStatVerifyDist[which[k]] = dist[k];
+        if (dist[k] < 0) continue;
+        nVerifyChecked++;
+        if (dist[k] > nVerifyMaxHamming) { F->mvStatVerifyRejected[which[k]] = 1; nVerifyRejected++; }
+    }
 }
 
 void Tracking::UpdateMask()                                   // Tracking.cc:3291-3357, device scatter
@@ -1190,6 +1241,16 @@ void Tracking::RenewFrameInfo(const std::vector<int>& TM_sta)  // Tracking.cc:29
         flows[k] = cv::Point2f(fl[2 * k], fl[2 * k + 1]); inlierID[k] = inl[k];
         corres[k] = cv::KeyPoint(keys[k].pt.x + fl[2 * k], keys[k].pt.y + fl[2 * k + 1], 0, 0, 0, -1);
     }
+    if (bVerifyDescriptor) {                                // a kept inlier keeps the seed it arrived with (never the descriptor of this frame: drift cannot accumulate); a top-up point is seeded by its keypoint
+        std::vector<int> slev; std::vector<unsigned char> sdesc; slev.reserve(n); sdesc.reserve(32 * (size_t)n);
+        const bool have = (int)C->mvStatSeedLevel.size() == ns && (int)C->mvStatSeedDesc.size() == 32 * ns;
+        for (int k = 0; k < n; k++) {
+            if (inl[k] < 0) { push_seed(*C, nUseSampleFea == 1 ? -1 : src[k], slev, sdesc); continue; }
+            if (!have) { push_seed(*C, -1, slev, sdesc); continue; }
+            slev.push_back(C->mvStatSeedLevel[src[k]]); sdesc.insert(sdesc.end(), C->mvStatSeedDesc.begin() + 32 * (size_t)src[k], C->mvStatSeedDesc.begin() + 32 * (size_t)src[k] + 32);
+        }
+        C->mvStatSeedLevelTmp = std::move(slev); C->mvStatSeedDescTmp = std::move(sdesc);
+    }
     C->N_s_tmp = n;
     std::vector<float> depth(n, -1.f); std::vector<cv::Mat> p3d; std::vector<float> xyz3(3 * (size_t)std::max(n, 1));
     const cv::Mat Twc = Converter::toInvMatrix(C->mTcw);
@@ -1239,6 +1300,10 @@ void Tracking::Track()                                        // Tracking.cc:108
     else {
         Frame* L = mpLastFrame;
         for (int i = 0; i < C->N_s; i++) TemperalMatch[i] = i;
+        if (bVerifyDescriptor && nVerifyRejected > 0) {    // a rejected point is in no list from here on: not in the RANSAC set, not in the pose optimisation, not among the inliers
+            TemperalMatch.clear();                         // RenewFrameInfo propagates (it tops the list up from the keypoints as it does for the optimiser's outliers); the per-point vectors stay as they are
+            for (int i = 0; i < C->N_s; i++) if (!C->mvStatVerifyRejected[i]) TemperalMatch.push_back(i);
+        }
         if (TemperalMatch.size() < 2) { C->SetPose(L->mTcw); return; }
         auto t0 = std::chrono::steady_clock::now();
         cv::Mat iniTcw = GetInitModelCam(TemperalMatch, TemperalMatch_subset);
@@ -1444,6 +1509,38 @@ int vido_system_get_stats(const vido_system* s, vido_system_stats* o)
     if (T->all_timing.size() >= 5) { o->ms_cam_pose = T->all_timing[1]; o->ms_obj_tracking = T->all_timing[2]; o->ms_renew = T->all_timing[4]; }
     o->ms_obj_motion = T->ms_obj_motion_sum;
     o->ms_local_ba = M && !M->fLBA_time.empty() && T->f_id > 1 ? M->fLBA_time.back() : 0.f;
+    return VIDO_OK;
+}
+
+int vido_system_get_verify_stats(const vido_system* s, int* n_checked, int* n_rejected)
+{
+    if (!s || !s->inited) return VIDO_E_INVALID;
+    if (n_checked) *n_checked = 0;
+    if (n_rejected) *n_rejected = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) T->GetVerifyStats(n_checked, n_rejected);
+    return VIDO_OK;
+}
+
+int vido_system_get_verify_points(const vido_system* s, float* xy, float* prev_xy, int32_t* xyl, int32_t* dist, uint8_t* rejected, uint8_t* seed_desc, int cap, int* n_out)
+{
+    if (!s || !s->inited || !n_out) return VIDO_E_INVALID;
+    *n_out = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (!T || !T->mpCurrentFrame || !T->bVerifyDescriptor) return VIDO_OK;
+    const VIDO_SLAM::Frame* F = T->mpCurrentFrame;
+    const int n = (int)F->mvStatVerifyDist.size();
+    *n_out = n;
+    if (n > cap) return VIDO_E_CAPACITY;
+    if ((int)F->mvStatVerifyXY.size() != 4 * n) return VIDO_E_INVALID;
+    for (int i = 0; i < n; i++) {
+        if (xy) { xy[2 * i] = F->mvStatVerifyXY[4 * (size_t)i]; xy[2 * i + 1] = F->mvStatVerifyXY[4 * (size_t)i + 1]; }
+        if (prev_xy) { prev_xy[2 * i] = F->mvStatVerifyXY[4 * (size_t)i + 2]; prev_xy[2 * i + 1] = F->mvStatVerifyXY[4 * (size_t)i + 3]; }
+        if (xyl) memcpy(xyl + 3 * (size_t)i, &F->mvStatVerifyXYL[3 * (size_t)i], 3 * sizeof(int32_t));
+        if (dist) dist[i] = F->mvStatVerifyDist[i];
+        if (rejected) rejected[i] = F->mvStatVerifyRejected[i];
+        if (seed_desc) memcpy(seed_desc + 32 * (size_t)i, &F->mvStatSeedDesc[32 * (size_t)i], 32);
+    }
     return VIDO_OK;
 }
 

@@ -1279,6 +1279,90 @@ __global__ __launch_bounds__(256) void k_orient_brief(const uint8_t* __restrict_
     if ((lane & 7) == 0) ((uint32_t*)(descf + o * 32))[lane >> 3] = w;
 }
 
+// K5b: k_orient_brief's arithmetic at caller-given points of one frame's slab (vido_orb_describe_points): orientation on the unblurred level, steered BRIEF on the blurred
+// one, and the Hamming distance to a caller-given descriptor in the same wave.  One wave per point, four points per workgroup, points in caller order; a wave reads nothing
+// but its own point's row of the inputs, so a result depends neither on n nor on the order.  A point outside the extractor's own edge margin (EDGE_THRESHOLD: there the
+// radius-15 disc, the 37 x 37 window and the aligned dwords that cover them are the same addresses the extractor reads for a keypoint) or with a level out of range is
+// invalid: angle -1, zero descriptor, distance -1, and no read of the slab at all.
+__global__ __launch_bounds__(256) void k_describe_points(const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur, PyrDev P, const int* __restrict__ xyl, int n,
+                                                         const uint32_t* __restrict__ ref, float* __restrict__ ang_out, uint32_t* __restrict__ desc_out, int* __restrict__ dist_out,
+                                                         unsigned long long umax_packed)
+{
+    const int kk = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (kk >= n) return;
+    const int x = xyl[3 * kk], y = xyl[3 * kk + 1], level = xyl[3 * kk + 2];
+    bool valid = level >= 0 && level < P.n_levels;
+    const int lc = valid ? level : 0;
+    valid = valid && x >= EDGE_THRESHOLD && x < P.w[lc] - EDGE_THRESHOLD && y >= EDGE_THRESHOLD && y < P.h[lc] - EDGE_THRESHOLD;
+    if (!valid) {                                                          // (wave-uniform)
+        if (lane == 0) { if (ang_out) ang_out[kk] = -1.f; if (dist_out) dist_out[kk] = -1; }
+        if (desc_out && lane < 8) desc_out[(size_t)kk * 8 + lane] = 0u;
+        return;
+    }
+    const int pitch = P.pitch[level];
+    int m10 = 0, m01 = 0;
+    const unsigned x_al = (unsigned)(x - 15) & ~3u;
+    const uint8_t* rows = pyr + P.off[level] + (size_t)y * pitch + x_al;
+    const int u0 = (int)x_al - x;
+#pragma unroll
+    for (int it = 0; it < 5; it++) {
+        const int q = lane + 64 * it;
+        if (q < 31 * 9) {
+            const int vy = (int)(__umul24((unsigned)q, 7282u) >> 16), d = q - vy * 9, v = vy - 15;
+            const int um = (int)((umax_packed >> (4 * abs(v))) & 15ull);
+            const uint32_t w = *(const uint32_t*)(rows + __mul24(v, pitch) + 4 * d);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int u = u0 + 4 * d + k;
+                if (abs(u) <= um) { const int val = (int)((w >> (8 * k)) & 255u); m10 += u * val; m01 += v * val; }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { m10 += __shfl_xor(m10, o, 64); m01 += __shfl_xor(m01, o, 64); }
+    const float ang = fast_atan2_deg((float)m01, (float)m10);
+    if (lane == 0 && ang_out) ang_out[kk] = ang;
+    if (!desc_out && !dist_out) return;
+    const float factorPI = (float)(3.14159265358979323846 / 180.f);
+    const float ar = ang * factorPI;
+    float a, b; sincos_0_2pi((double)ar, &b, &a);
+    constexpr int OB_R = 18, OB_DW = 10, OB_LD = 11;                        // as k_orient_brief: the 37-row window of the blurred level in the wave's own LDS slice
+    __shared__ uint32_t dp_lds[4][(2 * OB_R + 1) * OB_LD];
+    uint32_t* win = dp_lds[threadIdx.x >> 6];
+    const unsigned bx_al = (unsigned)(x - OB_R) & ~3u;
+    const uint8_t* brow = blur + P.off[level] + (size_t)(y - OB_R) * pitch + bx_al;
+#pragma unroll
+    for (int it = 0; it < 6; it++) {
+        const int q = lane + 64 * it;
+        if (q < (2 * OB_R + 1) * OB_DW) { const int r = (int)(__umul24((unsigned)q, 6554u) >> 16), d = q - r * OB_DW;
+                                              win[r * OB_LD + d] = *(const uint32_t*)(brow + __umul24((unsigned)r, (unsigned)pitch) + 4 * d); }
+    }
+    __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_wave_barrier();
+    const uint8_t* cb = (const uint8_t*)win + OB_R * (OB_LD * 4) + (x - (int)bx_al);
+    uint32_t nib = 0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const signed char* pt = c_pattern + (lane * 4 + t) * 4;
+        const float x0 = (float)pt[0], y0 = (float)pt[1], x1 = (float)pt[2], y1 = (float)pt[3];
+        const int t0 = cb[__mul24(__float2int_rn(x0 * b + y0 * a), OB_LD * 4) + __float2int_rn(x0 * a - y0 * b)];
+        const int t1 = cb[__mul24(__float2int_rn(x1 * b + y1 * a), OB_LD * 4) + __float2int_rn(x1 * a - y1 * b)];
+        nib |= (uint32_t)(t0 < t1) << t;
+    }
+    if (dist_out) {      // lane holds bits 4 lane .. 4 lane + 3 of the descriptor: xor with the same nibble of the reference, count, sum over the wave
+        const uint32_t rw = ref[(size_t)kk * 8 + (lane >> 3)];
+        int d = __popc(nib ^ ((rw >> (4 * (lane & 7))) & 15u));
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) d += __shfl_xor(d, o, 64);
+        if (lane == 0) dist_out[kk] = d;
+    }
+    if (desc_out) {
+        uint32_t w = nib | (__shfl_down(nib, 1, 64) << 4);
+        w |= __shfl_down(w, 2, 64) << 8;
+        w |= __shfl_down(w, 4, 64) << 16;
+        if ((lane & 7) == 0) desc_out[(size_t)kk * 8 + (lane >> 3)] = w;
+    }
+}
+
 // ================================================================================================
 // host side
 struct OrbState {
@@ -1318,6 +1402,8 @@ struct OrbState {
     KpLevels kpl{};
     // cvtColor fused ingest: staging for host colour frames / the gray copy handed back
     uint8_t *d_color = nullptr, *d_gray_out = nullptr; size_t color_cap = 0; int in_channels = 1, in_rgb = 0; uint8_t* gray_out = nullptr; int gray_out_on_device = 0;
+    // vido_orb_describe_points, host form: device + pinned staging of dp_cap points, each [xyl 12 B | reference 32 B] in and [angle 4 B | descriptor 32 B | distance 4 B] out
+    uint8_t *d_dp = nullptr, *h_dp = nullptr; int dp_cap = 0;
 };
 
 static inline int cv_round_f(float v) { return (int)lrintf(v); }
@@ -1673,6 +1759,7 @@ void orb_state_destroy(vido_ctx* ctx)
     hipFree(S->d_qt_slot); hipFree(S->d_sel); hipFree(S->d_selcnt); hipFree(S->d_kpoff); hipFree(S->d_frame_beg); hipFree(S->d_budget); hipFree(S->d_kpf); hipFree(S->d_descf); hipFree(S->d_nkp);
     hipHostFree(S->h_frame_beg); hipHostFree(S->h_kpf); hipHostFree(S->h_descf);
     hipFree(S->d_color); hipFree(S->d_gray_out);
+    hipFree(S->d_dp); hipHostFree(S->h_dp);
     delete S; ctx->orb = nullptr;
 }
 
@@ -2001,6 +2088,53 @@ int vido_orb_read_level(vido_ctx* ctx, int frame, int level, int blurred, uint8_
     const LevelInfo& v = S->lv[level];
     const uint8_t* src = (blurred ? S->d_blur : S->d_pyr) + (size_t)frame * S->slab + v.off;
     HIP_TRY(ctx, hipMemcpy2D(out, v.w, src, v.pitch, v.w, v.h, hipMemcpyDeviceToHost));
+    return VIDO_OK;
+}
+
+int vido_orb_describe_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, const uint8_t* ref_desc, float* angle_out, uint8_t* desc_out, int32_t* dist_out, int on_device)
+{
+    if (!ctx || !ctx->orb) return VIDO_E_INVALID;
+    OrbState* S = ctx->orb;
+    if (frame < 0 || frame >= S->B) return vido_set_error(ctx, VIDO_E_INVALID, "describe_points: frame %d outside the context's batch of %d", frame, S->B);
+    if (n < 0 || (n > 0 && !xyl)) return vido_set_error(ctx, VIDO_E_INVALID, "describe_points: bad point list");
+    if (dist_out && !ref_desc) return vido_set_error(ctx, VIDO_E_INVALID, "describe_points: distances need reference descriptors");
+    if ((desc_out || dist_out) && !ctx->cfg.compute_descriptors) return vido_set_error(ctx, VIDO_E_INVALID, "describe_points: the context keeps no blurred pyramid (compute_descriptors = 0)");
+    if (on_device && ((((uintptr_t)ref_desc | (uintptr_t)desc_out) & 3) != 0)) return vido_set_error(ctx, VIDO_E_INVALID, "describe_points: device descriptors must be 4-byte aligned");
+    if (n == 0 || (!angle_out && !desc_out && !dist_out)) return VIDO_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int* d_xyl = xyl; const uint32_t* d_ref = (const uint32_t*)ref_desc; float* d_ang = angle_out; uint32_t* d_desc = (uint32_t*)desc_out; int* d_dist = dist_out;
+    size_t o_ref = 0, o_ang = 0, o_desc = 0, o_dist = 0;
+    if (!on_device) {
+        if (n > S->dp_cap) {
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (S->d_dp) { HIP_TRY(ctx, hipFree(S->d_dp)); S->d_dp = nullptr; }
+            if (S->h_dp) { HIP_TRY(ctx, hipHostFree(S->h_dp)); S->h_dp = nullptr; }
+            S->dp_cap = 0;
+            const int cap = n + n / 2 + 64;
+            HIP_TRY(ctx, hipMalloc((void**)&S->d_dp, (size_t)cap * 84)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_dp, (size_t)cap * 84));
+            S->dp_cap = cap;
+        }
+        o_ref = (size_t)n * 12; o_ang = o_ref + (size_t)n * 32; o_desc = o_ang + (size_t)n * 4; o_dist = o_desc + (size_t)n * 32;
+        memcpy(S->h_dp, xyl, (size_t)n * 12);
+        if (ref_desc) memcpy(S->h_dp + o_ref, ref_desc, (size_t)n * 32);
+        HIP_TRY(ctx, hipMemcpyAsync(S->d_dp, S->h_dp, ref_desc ? o_ang : o_ref, hipMemcpyHostToDevice, st));
+        d_xyl = (const int*)S->d_dp; d_ref = ref_desc ? (const uint32_t*)(S->d_dp + o_ref) : nullptr;
+        d_ang = angle_out ? (float*)(S->d_dp + o_ang) : nullptr; d_desc = desc_out ? (uint32_t*)(S->d_dp + o_desc) : nullptr; d_dist = dist_out ? (int*)(S->d_dp + o_dist) : nullptr;
+    }
+    hipLaunchKernelGGL(k_describe_points, dim3((n + 3) / 4), dim3(256), 0, st, S->d_pyr + (size_t)frame * S->slab, S->d_blur + (size_t)frame * S->slab, S->P, d_xyl, n,
+                       d_ref, d_ang, d_desc, d_dist, S->umax_packed);
+    HIP_TRY(ctx, hipGetLastError());
+    if (!on_device) {
+        // only what was asked for comes back (the tracker's per-frame call wants the distances alone: 4 bytes per point)
+        if (angle_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_dp + o_ang, S->d_dp + o_ang, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (desc_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_dp + o_desc, S->d_dp + o_desc, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        if (dist_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_dp + o_dist, S->d_dp + o_dist, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (angle_out) memcpy(angle_out, S->h_dp + o_ang, (size_t)n * 4);
+        if (desc_out) memcpy(desc_out, S->h_dp + o_desc, (size_t)n * 32);
+        if (dist_out) memcpy(dist_out, S->h_dp + o_dist, (size_t)n * 4);
+    }
     return VIDO_OK;
 }
 

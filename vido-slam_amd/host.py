@@ -61,6 +61,7 @@ def load_library():
     lib.vido_orb_read_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.vido_orb_last_timing.argtypes = [C.c_void_p, C.c_void_p]
     lib.vido_hamming_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     _lib = lib
     return lib
@@ -177,6 +178,24 @@ class Context:
         self._check(self.lib.vido_orb_read_candidates(self.h, frame, level, _ptr(out), n))
         out = out[:n]
         return (out & 0xfff).astype(np.int32), ((out >> 12) & 0xfff).astype(np.int32), (out >> 24).astype(np.int32)
+
+    def orb_describe_points(self, frame, xyl, ref_desc=None):
+        """Orientation + rBRIEF at given points of pyramid slab `frame` (vido_orb_describe_points): xyl (n,3) i32 = x, y in level coordinates, level.
+        Returns (angle (n,) f32, desc (n,32) u8, dist (n,) i32 or None without ref_desc (n,32) u8); an invalid point has angle -1, a zero descriptor, distance -1."""
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3); n = len(xyl)
+        if ref_desc is not None:
+            ref_desc = np.ascontiguousarray(ref_desc, np.uint8).reshape(-1, 32)
+            if len(ref_desc) != n:
+                raise VidoError(-1, "orb_describe_points: %d reference descriptors for %d points" % (len(ref_desc), n))
+        ang = np.empty(n, np.float32); desc = np.empty((n, 32), np.uint8); dist = np.empty(n, np.int32) if ref_desc is not None else None
+        self._check(self.lib.vido_orb_describe_points(self.h, frame, _ptr(xyl), n, _ptr(ref_desc) if ref_desc is not None else None, _ptr(ang), _ptr(desc),
+                                                      _ptr(dist) if dist is not None else None, 0))
+        return ang, desc, dist
+
+    def orb_describe_points_device(self, frame, xyl_ptr, n, ref_ptr=None, angle_ptr=None, desc_ptr=None, dist_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_orb_describe_points(self.h, frame, vp(xyl_ptr), n, vp(ref_ptr), vp(angle_ptr), vp(desc_ptr), vp(dist_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

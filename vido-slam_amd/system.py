@@ -43,6 +43,8 @@ def _bind(lib):
     lib.vido_system_set_depth_noise_seed.argtypes = [C.c_void_p, C.c_uint]
     lib.vido_system_set_zero_copy_maps.argtypes = [C.c_void_p, C.c_int]
     lib.vido_system_prefetch_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.vido_system_get_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_get_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
 
@@ -126,6 +128,25 @@ class System:
         s = SystemStats()
         self.lib.vido_system_get_stats(self.h, C.byref(s))
         return s.as_dict()
+
+    def verify_stats(self):
+        """(n_checked, n_rejected) of the last frame's descriptor verification (Verify.Descriptor: 1; both 0 otherwise)."""
+        a, b = C.c_int(), C.c_int()
+        self.lib.vido_system_get_verify_stats(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def verify_points(self):
+        """Debug read of the last frame's per-point verification state (vido_system_get_verify_points), index-aligned with the frame's static list:
+        dict of xy (n,2) f32, prev_xy (n,2) f32, xyl (n,3) i32, dist (n,) i32, rejected (n,) bool, seed_desc (n,32) u8."""
+        n = C.c_int()
+        self.lib.vido_system_get_verify_points(self.h, None, None, None, None, None, None, 0, C.byref(n))
+        n = n.value; m = max(n, 1)
+        xy = np.empty((m, 2), np.float32); pxy = np.empty((m, 2), np.float32); xyl = np.empty((m, 3), np.int32); dist = np.empty(m, np.int32)
+        rej = np.empty(m, np.uint8); seed = np.empty((m, 32), np.uint8)
+        rc = self.lib.vido_system_get_verify_points(self.h, xy.ctypes.data, pxy.ctypes.data, xyl.ctypes.data, dist.ctypes.data, rej.ctypes.data, seed.ctypes.data, m, C.byref(C.c_int()))
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_get_verify_points")
+        return dict(xy=xy[:n], prev_xy=pxy[:n], xyl=xyl[:n], dist=dist[:n], rejected=rej[:n].astype(bool), seed_desc=seed[:n])
 
     def SaveResultsIJRR2020(self, filename=""):
         rc = self.lib.vido_system_save_results(self.h, os.fsencode(filename))
