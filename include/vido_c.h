@@ -487,6 +487,15 @@ int vido_det_select(vido_ctx* ctx, const float* prob, const float* seg_boxes, co
  * label image (src/run_mask_rcnn.py:112-118: blank_mask += mask * class_index): masks [n,1,M,M] f32, boxes [n,4] f32 in the output image, labels [n] i64,
  * all DEVICE, detections in the order the node adds them; out [H,W] u8 = (sum over detections of pasted mask * class index) mod 256. */
 int vido_mask_label_image(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W, uint8_t* out);
+/* Masker + INSTANCE image: same inputs as vido_mask_label_image (device pointers; detections in the caller's priority order, highest first).
+ * out[y,x] = id_base + 1 + (index of the FIRST detection with labels[i] != 0 whose pasted mask probability at (x,y) > thresh), 0 if none: the footprint of every
+ * detection is the one vido_mask_label_image adds its class to, overlaps go to the earlier detection instead of summing.  labels[i] == 0 (an unused slot of the
+ * static head) is skipped and still consumes its id, so id - id_base - 1 is the slot index.  area_out [n] i32 (may be NULL): pixels each detection owns in `out`
+ * (cleared by the call).  id_base_dev: DEVICE int32 word read by the kernel (NULL: 0), so a captured graph follows a base that changes per frame; its owner keeps
+ * n + id_base <= 255 (the sum is stored in u8).  n + id_base > 255 is refused (VIDO_E_CAPACITY) where the base is known to the host (NULL: n > 255; a device word:
+ * n > 255 as well, the largest n any base admits); n == 0 clears out.  Enqueues on the adopted stream, no host synchronisation. */
+int vido_mask_instance_image(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W,
+                             const int32_t* id_base_dev, uint8_t* out, int32_t* area_out);
 /* BoxCoder(weights).decode(deltas [n,4k], boxes [n,4]) — modeling/box_coder.py:52-95. */
 int vido_box_decode(vido_ctx* ctx, const float* deltas, const float* boxes, int n, int k, const float weights[4],
                     float* out, int on_device);

@@ -477,6 +477,73 @@ __global__ __launch_bounds__(256) void k_paste_label(const float* __restrict__ m
     if (x < W && y < H) out[(size_t)y * W + x] = (uint8_t)acc;
 }
 
+// ---- Masker + INSTANCE image: k_paste_label's walk with another reduction.  The coverage test (box window, bilinear sample of the padded mask, val > thresh) is the same
+// expression term for term, so a detection covers exactly the pixels k_paste_label adds its class to; here the FIRST detection of the list (the caller's priority order)
+// that covers a pixel owns it and the walk stops.  A slot with label 0 (unused slot of the static head) is skipped and keeps its id: id - base - 1 is always the slot index.
+// Each block first drops the detections whose window misses its tile.  area (may be null): pixels per slot, counted per block in LDS, then one vector atomicAdd per (block, slot present in the block).  n <= 255 (one id per slot in u8).
+__global__ void k_zero_i32(int32_t* __restrict__ p, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+__global__ __launch_bounds__(256) void k_paste_instance(const float* __restrict__ masks /*[n,1,M,M]*/, const PasteDet* __restrict__ det, int n, int M, int padding, float thresh,
+                                                        int H, int W, const int32_t* __restrict__ id_base, uint8_t* __restrict__ out, int32_t* __restrict__ area)
+{
+    __shared__ PasteDet sd[128];
+    __shared__ unsigned char slot[128];
+    __shared__ int cnt[256], nlive[2];
+    const int t = threadIdx.x, bx0 = blockIdx.x * 32, by0 = blockIdx.y * 8;
+    const int x = bx0 + (t & 31), y = by0 + (t >> 5);
+    const int Mp = M + 2 * padding;
+    const bool inside = x < W && y < H;
+    if (area) cnt[t] = 0;                                             // (ordered before the atomics below by the barriers of the chunk loop; n == 0: no atomics)
+    int hit = -1;
+    for (int d0 = 0; d0 < n; d0 += 128) {
+        // the chunk's detections that can own a pixel of this block's 32 x 8 tile (nonzero class, window over the tile), compacted IN LIST ORDER by the first two waves:
+        // a detection left out fails the window test of every pixel here, so the walk below visits the same hits in the same order
+        PasteDet mine; bool live = false; int pos = 0;
+        if (t < 128) {
+            if (t < n - d0) {
+                mine = det[d0 + t];
+                // u / v of the tile's first and last pixel, in the walk's own (wrapping) arithmetic: some pixel of the tile passes 0 <= u < w iff u_hi >= 0 && u_lo < w;
+                // a box whose saturated coordinates make the difference wrap inside the tile is kept (the walk decides)
+                const int u_lo = (int)((unsigned)bx0 - (unsigned)mine.x0), u_hi = (int)((unsigned)(bx0 + 31) - (unsigned)mine.x0);
+                const int v_lo = (int)((unsigned)by0 - (unsigned)mine.y0), v_hi = (int)((unsigned)(by0 + 7) - (unsigned)mine.y0);
+                live = mine.label != 0 && (u_lo > u_hi || (u_hi >= 0 && u_lo < mine.w)) && (v_lo > v_hi || (v_hi >= 0 && v_lo < mine.h));
+            }
+            const unsigned long long b = __ballot(live);
+            pos = __popcll(b & ((1ull << (t & 63)) - 1ull));
+            if ((t & 63) == 0) nlive[t >> 6] = __popcll(b);
+        }
+        __syncthreads();
+        if (live) { const int p = pos + (t >= 64 ? nlive[0] : 0); sd[p] = mine; slot[p] = (unsigned char)t; }
+        __syncthreads();
+        const int m = nlive[0] + nlive[1];
+        if (inside && hit < 0) {
+            for (int k = 0; k < m; k++) {
+                const PasteDet d = sd[k];
+                const int u = x - d.x0, v = y - d.y0;
+                if (u < 0 || v < 0 || u >= d.w || v >= d.h) continue;
+                float sy = d.rh * ((float)v + 0.5f) - 0.5f; if (sy < 0.f) sy = 0.f;
+                float sx = d.rw * ((float)u + 0.5f) - 0.5f; if (sx < 0.f) sx = 0.f;
+                const int iy = (int)sy, ix = (int)sx; const int iyp = iy < Mp - 1 ? 1 : 0, ixp = ix < Mp - 1 ? 1 : 0;
+                const float ly = sy - (float)iy, lx = sx - (float)ix, hy = 1.f - ly, hx = 1.f - lx;
+                const float* m_ = masks + (size_t)(d0 + slot[k]) * M * M;
+                auto at = [&](int yy, int xx) -> float { yy -= padding; xx -= padding; return (yy < 0 || xx < 0 || yy >= M || xx >= M) ? 0.f : m_[yy * M + xx]; };
+                const float val = hy * (hx * at(iy, ix) + lx * at(iy, ix + ixp)) + ly * (hx * at(iy + iyp, ix) + lx * at(iy + iyp, ix + ixp));
+                if (val > thresh) { hit = d0 + slot[k]; break; }
+            }
+        }
+        __syncthreads();                                              // (the next chunk rewrites sd / nlive)
+    }
+    if (inside) out[(size_t)y * W + x] = hit < 0 ? (uint8_t)0 : (uint8_t)((id_base ? *id_base : 0) + 1 + hit);
+    if (area) {
+        if (hit >= 0) atomicAdd(&cnt[hit], 1);
+        __syncthreads();
+        if (t < n && cnt[t]) atomicAdd(&area[t], cnt[t]);
+    }
+}
+
 // ---- box decode ------------------------------------------------------------------------------------------------
 __global__ void k_box_decode(const float* __restrict__ deltas, const float* __restrict__ boxes, int n, int k, float wx, float wy, float ww, float wh, float* __restrict__ out)
 {
@@ -1060,6 +1127,31 @@ int vido_mask_label_image(vido_ctx* ctx, const float* masks, const float* boxes,
     PasteDet* det = (PasteDet*)S->d;
     hipLaunchKernelGGL(k_paste_prepare, dim3((n + 255) / 256), dim3(256), 0, st, boxes, labels, n, M, padding, det);
     hipLaunchKernelGGL(k_paste_label, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, st, masks, det, n, M, padding, thresh, H, W, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return VIDO_OK;
+}
+
+/* Masker + instance image (include/vido_c.h): vido_mask_label_image's inputs; out = id_base + 1 + index of the first detection (list order, labels != 0) whose pasted mask
+ * covers the pixel, 0 if none; area_out [n] (may be NULL) = pixels per detection, cleared here in stream order.  No host synchronisation, static launch shape. */
+int vido_mask_instance_image(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W,
+                             const int32_t* id_base_dev, uint8_t* out, int32_t* area_out)
+{
+    if (!ctx) return VIDO_E_INVALID;
+    if (!out || H < 1 || W < 1 || n < 0 || M < 1 || padding < 0 || (n && (!masks || !boxes || !labels))) return vido_set_error(ctx, VIDO_E_INVALID, "mask_instance_image: bad arguments");
+    // the device word is not known here: its owner keeps n + id_base <= 255 (NetNodes: bases 0 / 127, at most 127 slots); without one the base is 0
+    if (n > 255) return vido_set_error(ctx, VIDO_E_CAPACITY, "mask_instance_image: %d detections, ids are u8 (n + id_base <= 255)", n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
+    // every clear is a kernel, not a memset node (the call is replayed inside captured graphs): n == 0 runs the paste kernel over an empty list, which writes 0 everywhere
+    PasteDet* det = nullptr;
+    if (n) {
+        NetState* S = nullptr;
+        int rc = net_scratch(ctx, al256((size_t)n * sizeof(PasteDet)), &S); if (rc) return rc;
+        det = (PasteDet*)S->d;
+        if (area_out) hipLaunchKernelGGL(k_zero_i32, dim3((n + 255) / 256), dim3(256), 0, st, area_out, n);
+        hipLaunchKernelGGL(k_paste_prepare, dim3((n + 255) / 256), dim3(256), 0, st, boxes, labels, n, M, padding, det);
+    }
+    hipLaunchKernelGGL(k_paste_instance, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, st, masks, det, n, M, padding, thresh, H, W, id_base_dev, out, area_out);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }

@@ -716,11 +716,51 @@ MaskRCNN.fpn_maps = _fpn_maps
 MaskRCNN.heads_static = _heads_static
 
 
+LABEL_MODES = ("class", "instance")
+
+
+def _check_label_mode(label_mode):
+    if label_mode not in LABEL_MODES:
+        raise ValueError("label_mode: one of %s, not %r" % (LABEL_MODES, label_mode))
+
+
+def label_image_torch(masks, boxes, scores, labels, H, W, confidence=0.8, label_mode="class", id_base=0, max_instances=None):
+    """The tail of analyse_image as torch expressions (any device; what runs when the ops object has no HIP paste op or the tensors are on the CPU): detections above
+    `confidence` in descending score order (select_top_predictions), pasted by paste_masks -> (label image [H,W] u8, labels in that order).
+    label_mode "class": the node's image, sum of mask * class index modulo 256 (run_mask_rcnn.py:112-118).  "instance": pixel = id_base + 1 + index (in the returned order)
+    of the FIRST detection with a nonzero class that covers it, 0 where none does; a class-0 entry is skipped and keeps its id, so labels[id - id_base - 1] is the
+    pixel's class.  id_base: int or a one-element integer tensor; n + id_base <= 255.  max_instances (instance mode): only that many detections, the highest scores,
+    get an id; the rest are left out of the image AND of the returned labels (a caller whose id range is shorter than the detector's list: NetNodes' 127)."""
+    _check_label_mode(label_mode)
+    keep = torch.nonzero(scores > confidence).squeeze(1)
+    keep = keep[scores[keep].sort(0, descending=True)[1]]
+    if label_mode == "instance" and max_instances is not None:
+        keep = keep[:max_instances]
+    labels = labels[keep]
+    n = int(keep.numel())
+    if n == 0:
+        return torch.zeros((H, W), dtype=torch.uint8, device=masks.device), labels
+    pasted = paste_masks(masks[keep], boxes[keep], H, W)                  # the reference pastes every detection and then selects; only the selected ones reach the output
+    if label_mode == "class":
+        # sum over detections of mask * class index, accumulated in u8 (wraps on overlap, like the reference's numpy loop); one reduction instead of a loop over the detections
+        return (pasted.to(torch.int32) * labels.view(-1, 1, 1).to(torch.int32)).sum(0).remainder(256).to(torch.uint8), labels
+    if not torch.is_tensor(id_base) and n + int(id_base) > 255:
+        raise ValueError("label_mode='instance': %d detections above id base %d, ids are u8 (n + id_base <= 255)" % (n, id_base))
+    slot = torch.arange(1, n + 1, dtype=torch.int32, device=masks.device).view(-1, 1, 1)
+    first = torch.where(pasted & (labels != 0).view(-1, 1, 1), slot, slot.new_full((), n + 1)).min(0)[0]      # smallest covering slot (1-based), n + 1 where none
+    base = id_base.reshape(()).to(torch.int32) if torch.is_tensor(id_base) else int(id_base)
+    return torch.where(first <= n, first + base, torch.zeros_like(first)).to(torch.uint8), labels
+
+
 @torch.no_grad()
-def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), confidence=0.8, cap=None):
+def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), confidence=0.8, cap=None, label_mode="class", id_base=None):
     """analyse_image's tail on the static head: (label image [H,W] u8, labels [cap] i64 in descending score order with 0 for unused slots, n_labels, n_det) — all device
     tensors, nothing synchronised.  Detections that fail the confidence test (and the padding slots) keep their slot with class index 0: they add nothing to the label image
-    (run_mask_rcnn.py:112-118 sums mask * class_index), which is what selecting them away does in the reference.  n_det > cap: the caller must redo the image with analyse_image()."""
+    (run_mask_rcnn.py:112-118 sums mask * class_index), which is what selecting them away does in the reference.  n_det > cap: the caller must redo the image with analyse_image().
+    label_mode="instance" (id_base: None or a DEVICE int32 word, read when the launch runs, i.e. at every replay of a captured graph): the image holds id_base + 1 + the slot
+    of the first live slot in descending score order that covers the pixel, instead of the class sum (vido_mask_instance_image: same launch shape, capturable);
+    labels[id - id_base - 1] is the pixel's class."""
+    _check_label_mode(label_mode)
     H, W = out_hw
     out = net.heads_static(feats, logits, deltas, feed, cap)
     cap = out["boxes"].shape[0]
@@ -739,7 +779,12 @@ def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), c
         order = torch.sort(torch.where(live, out["scores"], out["scores"].new_full((), -1.0)), descending=True, stable=True)[1]
         labels = torch.where(live, out["labels"], torch.zeros_like(out["labels"]))[order]
         n_live = live.sum()
-    img = ops.mask_label_image(out["masks"][order], boxes[order], labels, H, W)
+    if label_mode == "instance":
+        if cap > 255:
+            raise ValueError("label_mode='instance': %d slots, ids are u8" % cap)
+        img = ops.mask_instance_image(out["masks"][order], boxes[order], labels, H, W, id_base=id_base)
+    else:
+        img = ops.mask_label_image(out["masks"][order], boxes[order], labels, H, W)
     return img, labels, n_live, out["n_det"]
 
 
@@ -752,15 +797,19 @@ def image_to_feed(bgr, dev, feed=(1088, 800), ops=None):
 
 
 @torch.no_grad()
-def analyse_image(net, bgr, feed=(1088, 800), confidence=0.8, trunk=None, on_range=None):
+def analyse_image(net, bgr, feed=(1088, 800), confidence=0.8, trunk=None, on_range=None, label_mode="class", id_base=None, max_instances=None):
     """predictor.py:compute_prediction + select_top_predictions (:215-283) and run_mask_rcnn.py:create_pixel_masks (:83-123):
     HxWx3 u8 BGR -> (label image HxW u8 = sum of mask * class index, label indices).  The frame is area-resized to 800x1088
     (W x H, cv2.INTER_AREA; third-party, restated with torch's area interpolation), flipped to RGB, NOT normalised.
     on_range: None = unchecked; "raise" / "recompute" = the split-fp16 range check of this call alone (ops.range_checked; the recomputation runs the whole detector eagerly,
-    without `trunk`, whose captured launches are split-fp16)."""
+    without `trunk`, whose captured launches are split-fp16).
+    label_mode="instance": (instance image HxW u8, labels) — a pixel holds id_base + 1 + the rank (descending score, the order of the returned labels) of the first kept
+    detection that covers it, so labels[id - id_base - 1] is its class and overlaps never add up (label_image_torch / vido_mask_instance_image).  id_base: None (0), an int,
+    or a one-element int32 tensor on the detector's device.  max_instances: as in label_image_torch (the lowest scores past it get no id and no label)."""
+    _check_label_mode(label_mode)
     if on_range is not None:
         from .ops import range_checked
-        return range_checked(lambda safe: analyse_image(net, bgr, feed, confidence, None if safe else trunk), (net,), on_range, "the detector")
+        return range_checked(lambda safe: analyse_image(net, bgr, feed, confidence, None if safe else trunk, None, label_mode, id_base, max_instances), (net,), on_range, "the detector")
     dev = next(net.parameters()).device
     H, W = bgr.shape[:2]
     if trunk is not None:                                    # hipGraph-captured static part (pipeline.NetNodes): u8 HxWx3 BGR in -> (feats, logits, deltas)
@@ -770,17 +819,14 @@ def analyse_image(net, bgr, feed=(1088, 800), confidence=0.8, trunk=None, on_ran
         out = net(image_to_feed(bgr, dev, feed))
     rw, rh = float(W) / feed[1], float(H) / feed[0]
     boxes = out["boxes"] * out["boxes"].new_tensor([rw, rh, rw, rh]) if rw != rh else out["boxes"] * rw
-    keep = torch.nonzero(out["scores"] > confidence).squeeze(1)
-    keep = keep[out["scores"][keep].sort(0, descending=True)[1]]
-    labels = out["labels"][keep]
     ops = getattr(net.rpn, "ops", None)
     if hasattr(ops, "mask_label_image") and out["masks"].is_cuda:         # Masker + label image in one HIP pass (no per-detection host loop)
+        keep = torch.nonzero(out["scores"] > confidence).squeeze(1)
+        keep = keep[out["scores"][keep].sort(0, descending=True)[1]]
+        if label_mode == "instance" and max_instances is not None:
+            keep = keep[:max_instances]
+        labels = out["labels"][keep]
+        if label_mode == "instance":
+            return ops.mask_instance_image(out["masks"][keep], boxes[keep], labels, H, W, id_base=id_base), labels
         return ops.mask_label_image(out["masks"][keep], boxes[keep], labels, H, W), labels
-    pasted_kept = paste_masks(out["masks"][keep], boxes[keep], H, W)      # the reference pastes every detection and then selects; only the selected ones reach the output
-    # label image = sum over detections of mask * class index, accumulated in u8 (wraps on overlap, like the reference's numpy loop);
-    # one reduction on the device instead of a host-synchronising loop over the detections
-    if len(keep):
-        img = (pasted_kept.to(torch.int32) * labels.view(-1, 1, 1).to(torch.int32)).sum(0).remainder(256).to(torch.uint8)
-    else:
-        img = torch.zeros((H, W), dtype=torch.uint8, device=dev)
-    return img, labels
+    return label_image_torch(out["masks"], boxes, out["scores"], out["labels"], H, W, confidence, label_mode, 0 if id_base is None else id_base, max_instances)

@@ -638,6 +638,28 @@ class HipOps:
                                                            C.c_void_p(out.data_ptr())))
         return out
 
+    def mask_instance_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, id_base=None, areas=False):
+        """Masker + instance image (vido_mask_instance_image): mask_label_image's inputs in priority order (highest first) -> [H,W] u8 = id_base + 1 + index of the first
+        detection with a nonzero label whose pasted mask covers the pixel, 0 elsewhere.  id_base: None (0), an int, or a DEVICE int32 tensor of one element that the kernel
+        reads (a captured graph then follows the word's value at replay).  areas=True: also the pixels per detection, int32 [n]."""
+        from ..host import VidoError
+        out = torch.empty((H, W), device=masks.device, dtype=torch.uint8)
+        n = masks.shape[0]
+        masks = masks.contiguous().float(); boxes = boxes.contiguous().float(); labels = labels.contiguous().to(torch.int64)
+        if id_base is not None and not torch.is_tensor(id_base):
+            if id_base < 0 or n + int(id_base) > 255:
+                raise VidoError(-4, "mask_instance_image: %d detections above id base %d, ids are u8 (n + id_base <= 255)" % (n, id_base))
+            id_base = torch.full((1,), int(id_base), dtype=torch.int32, device=masks.device) if id_base else None
+        if id_base is not None:
+            assert id_base.is_cuda and id_base.dtype == torch.int32 and id_base.numel() == 1
+        area = torch.empty((n,), device=masks.device, dtype=torch.int32) if areas else None
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_mask_instance_image(self.ctx.h, C.c_void_p(masks.data_ptr()) if n else None, C.c_void_p(boxes.data_ptr()) if n else None,
+                                                              C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
+                                                              C.c_void_p(id_base.data_ptr()) if id_base is not None else None, C.c_void_p(out.data_ptr()),
+                                                              C.c_void_p(area.data_ptr()) if areas and n else None))
+        return (out, area) if areas else out
+
 
 def _ops_of(obj, out):
     """The HipOps objects `obj` launches through: itself, or those held by a module's sub-modules (attributes such as _ops / wino / fused, and the objects behind bound

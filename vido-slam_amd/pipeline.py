@@ -134,11 +134,15 @@ class NetNodes:
     before the frame is tracked).  Only LiteFlowNet (its context) and the detector launch split-fp16 kernels; MonoDepth2 shares the detector's context and launches none."""
 
     RANGE_MODES = ("raise", "recompute")
+    ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
-                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise"):
+                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class"):
         if on_range not in self.RANGE_MODES:
             raise ValueError("on_range: one of %s, not %r" % (self.RANGE_MODES, on_range))
+        if label_mode not in _nets.maskrcnn.LABEL_MODES:
+            raise ValueError("label_mode: one of %s, not %r" % (_nets.maskrcnn.LABEL_MODES, label_mode))
+        self.label_mode = label_mode
         self.on_range = on_range
         self.range_recomputes = {"flow": 0, "detector": 0}           # networks recomputed in fp32's range (on_range="recompute")
         self._range_words = None                                      # infer()'s words when the caller passes none (pinned int32 [flow context, detector context])
@@ -160,6 +164,12 @@ class NetNodes:
                                                                        pair_batch=not _os.environ.get("VIDO_LFN_NO_PAIR_BATCH")), seed).eval().to(dev)
         self.depth_net = _nets.fill_deterministic(_nets.MonoDepth2(), seed + 1).eval().to(dev)
         self.mask_net = _nets.fill_maskrcnn(_nets.MaskRCNN(ops), seed + 2).eval().to(dev)
+        if label_mode == "instance" and self.mask_net.config.detections_per_img > self.ID_BASES[1]:
+            raise ValueError("label_mode='instance': detections_per_img = %d, each id range holds %d" % (self.mask_net.config.detections_per_img, self.ID_BASES[1]))
+        # the instance ids' base: constants per parity, and the word the detector's graph reads (set from them in stream order before each replay); id_base: the frame in flight
+        self._id_bases = torch.tensor(self.ID_BASES, dtype=torch.int32, device=dev) if label_mode == "instance" else None
+        self._id_word = torch.zeros((1,), dtype=torch.int32, device=dev) if label_mode == "instance" else None
+        self.id_base = 0; self._frames = 0
         # random-init detector: un-saturate the class scores so that the reference's detections_per_img cap binds (see nets/weights.py); a synthetic textured frame
         self.score_scale = 1.0
         if calibrate_scores:
@@ -191,9 +201,10 @@ class NetNodes:
         self._trunk_fn = lambda a: self.mask_net.trunk(_nets.maskrcnn.image_to_feed(a, dev, self.mask_feed, ops=ops))
         # the whole detector with static shapes (nets/maskrcnn.py: heads_static / analyse_image_static): trunk + device-side RPN selection + box head + fixed-slot
         # post-processing + mask head + label image, no host synchronisation -> ONE hipGraph; returns (mask i32 HxW, labels [cap], n_labels, n_det)
-        def _det_fn(a):
+        def _det_fn(a, id_word=None):                                   # id_word: an eager call for an earlier frame (recompute) names that frame's constant word
             feats, logits, deltas = self._trunk_fn(a)
-            img, labels, n_lab, n_det = _nets.analyse_image_static(self.mask_net, feats, logits, deltas, (height, width), feed=self.mask_feed, confidence=self.confidence)
+            img, labels, n_lab, n_det = _nets.analyse_image_static(self.mask_net, feats, logits, deltas, (height, width), feed=self.mask_feed, confidence=self.confidence,
+                                                                   label_mode=self.label_mode, id_base=self._id_word if id_word is None else id_word)
             return img.to(torch.int32), labels, n_lab.to(torch.int32), n_det.to(torch.int32)
         self._det_fn = _det_fn
         with torch.no_grad():
@@ -229,6 +240,8 @@ class NetNodes:
     def infer(self, prev_bgr, cur_bgr, range_words=None):
         """prev_bgr / cur_bgr: u8 HxWx3 device tensors.  Returns (flow HxWx2 f32, depth HxW f32, mask HxW i32, labels, events): work enqueued on the caller's stream after
         this call sees the complete outputs (the caller's stream waits for the side stream's events); another stream or the host waits for the three events.
+        label_mode="instance": the mask holds per-frame instance ids above this frame's id base (self.id_base: ID_BASES alternate frame by frame), labels[id - id_base - 1]
+        is an id's class.
         range_words (pinned int32 [2], or on_range="recompute": NetNodes' own, valid until the next call; self.last_range names them): zeroed, then the frame's range flags
         of the flow context / the detector context are latched into words 0 / 1 on the caller's stream after the three events — they hold this frame's trips alone,
         readable on the host once the caller's stream has passed this point."""
@@ -244,6 +257,9 @@ class NetNodes:
             depth = (self.g_depth or self._depth_fn)(cur_bgr)
             e1 = torch.cuda.Event(); e1.record()
         with torch.cuda.stream(ss[2]):
+            if self.label_mode == "instance":                           # this frame's id base, into the word the graph reads: a device-to-device copy in stream order, nothing waits
+                self.id_base = self.ID_BASES[self._frames & 1]; self._frames += 1
+                self._id_word.copy_(self._base_word(self.id_base), non_blocking=True)
             if getattr(self, "skip_detector", False):                   # the literal "flow+depth+track+local-BA" chain of BASELINE's metric text (bench.py extra.e2e_without_detector)
                 if getattr(self, "_no_det", None) is None:
                     z = torch.zeros((), dtype=torch.int32, device=self.dev)
@@ -254,7 +270,7 @@ class NetNodes:
                 mask, labels, n_lab, n_det = self.g_det(cur_bgr)
                 self.last_counts = (n_lab, n_det)
             else:                                                       # dynamic head: its data-dependent tail synchronises the host while the other two networks run
-                mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk)
+                mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk, **self._label_args())
                 mask = mask_u8.to(torch.int32); self.last_counts = None
             e2 = torch.cuda.Event(); e2.record()
         for s, e in zip(ss, (e0, e1, e2)):                          # the outputs are valid in stream order on the CALLER's stream, whatever queue produced them
@@ -270,11 +286,24 @@ class NetNodes:
             self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
 
+    def _base_word(self, id_base):
+        """The constant device word that holds `id_base` (one of ID_BASES)."""
+        i = self.ID_BASES.index(int(id_base))
+        return self._id_bases[i:i + 1]
+
+    def _label_args(self, id_base=None):
+        """analyse_image's label arguments for a frame whose id base is `id_base` (None: the frame infer() saw last).  The dynamic head's list is not bounded by the slot
+        count (score ties at the cut: the overflow redo): only the ID_BASES[1] highest scores get an id, so that either range holds them and the sequence goes on."""
+        if self.label_mode != "instance":
+            return {}
+        return dict(label_mode="instance", id_base=self.id_base if id_base is None else int(id_base), max_instances=self.ID_BASES[1])
+
     @torch.no_grad()
-    def recompute(self, prev_bgr, cur_bgr, flow=True, detector=True):
+    def recompute(self, prev_bgr, cur_bgr, flow=True, detector=True, id_base=None):
         """The networks of a frame whose split-fp16 launches left the range, again in fp32's range: eager forwards inside nets.range_safe (no split-fp16 launch; nothing a
         captured graph reads is replaced) on the caller's stream.  Returns {"flow": HxWx2 f32 or None, "detector": (mask HxW i32, labels, n_lab, n_det) or None}; n_lab /
-        n_det are None after the dynamic head (no static detector).  The caller serialises it with infer() (the nodes' host-side state has one user at a time)."""
+        n_det are None after the dynamic head (no static detector).  The caller serialises it with infer() (the nodes' host-side state has one user at a time).
+        id_base (label_mode="instance"): the id base infer() gave THAT frame (its self.id_base then); None: the last frame's."""
         out = {"flow": None, "detector": None}
         if flow:
             with _nets.range_safe(self.flow_net):
@@ -283,10 +312,11 @@ class NetNodes:
         if detector and not getattr(self, "skip_detector", False):
             with _nets.range_safe(self.mask_net):
                 if self.g_det is not None:                              # the static head, eagerly (its trunk without the captured graph): the graph's output form
-                    mask, labels, n_lab, n_det = self._det_fn(cur_bgr)
+                    # (that frame's constant base word, not the graph's, which may already hold the next frame's)
+                    mask, labels, n_lab, n_det = self._det_fn(cur_bgr, self._base_word(self.id_base if id_base is None else id_base) if self.label_mode == "instance" else None)
                     out["detector"] = (mask, labels, n_lab, n_det)
                 else:
-                    mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence)
+                    mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, **self._label_args(id_base))
                     out["detector"] = (mask_u8.to(torch.int32), labels, None, None)
             self.range_recomputes["detector"] += 1
         return out
@@ -328,19 +358,20 @@ class NetNodes:
                                "kernels, the 1x1 ones on split-bf16)" % " and ".join(hit))
 
     @torch.no_grad()
-    def redo_detector_if_overflowed(self, cur_bgr, n_det_host, range_safe=False):
+    def redo_detector_if_overflowed(self, cur_bgr, n_det_host, range_safe=False, id_base=None):
         """The static head stores detections_per_img slots; score ties at the reference's kthvalue cut (box_head/inference.py:131-137) can leave more.  The caller reads
         n_det with the frame's hand-over and, in that (rare) case, recomputes the label image through the dynamic head (range_safe: a frame recomputed in fp32's range —
-        eagerly inside nets.range_safe, without the trunk's graph)."""
+        eagerly inside nets.range_safe, without the trunk's graph).  id_base: as in recompute(); in instance mode the 127 highest scores get an id (an id range holds no more),
+        the rest are left out of that frame's image."""
         cap = self.mask_net.config.detections_per_img
         if n_det_host <= cap:
             return None
         self.det_overflows += 1
         if range_safe:
             with _nets.range_safe(self.mask_net):
-                mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence)
+                mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, **self._label_args(id_base))
             return mask_u8.to(torch.int32), labels
-        mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk)
+        mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk, **self._label_args(id_base))
         return mask_u8.to(torch.int32), labels
 
 
@@ -376,7 +407,7 @@ class EndToEnd:
         h, w = nodes.h, nodes.w; dev = nodes.dev
         pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()
         self.host = [dict(bgr=pin((h, w, 3), torch.uint8), flow=pin((h, w, 2), torch.float32), depth=pin((h, w), torch.float32), mask=pin((h, w), torch.int32),
-                          counts=pin((2,), torch.int32), range=pin((2,), torch.int32)) for _ in range(self.RING)]
+                          counts=pin((2,), torch.int32), range=pin((2,), torch.int32), id_base=0) for _ in range(self.RING)]
         self.range_frames = []                # frames whose networks were recomputed in fp32's range (nodes.on_range == "recompute")
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         self.dev = [dict(bgr=mk((h, w, 3), torch.uint8), flow=mk((h, w, 2), torch.float32), depth=mk((h, w), torch.float32), mask=mk((h, w), torch.int32),
@@ -453,7 +484,7 @@ class EndToEnd:
         prev = self.dev[(slot - 1) % self.RING]["bgr"] if k > 0 else db["bgr"]          # (frame k - 1's slot is not reused before frame k has been tracked)
         # as in _redo_if_overflowed: on the network stream (stream order protects the contexts' scratch) and under the lock push() holds around infer()
         with self.net_lock, torch.cuda.stream(self.net_stream):
-            r = self.nodes.recompute(prev, db["bgr"], flow=hit_flow, detector=hit_det)
+            r = self.nodes.recompute(prev, db["bgr"], flow=hit_flow, detector=hit_det, id_base=hb["id_base"])
             if r["flow"] is not None:
                 db["flow"].copy_(r["flow"])
             if r["detector"] is not None:
@@ -474,7 +505,7 @@ class EndToEnd:
         # on the NETWORK stream (the detector's HIP ops share one device scratch, which stream order protects) and under the lock push() holds around infer():
         # the host-side state of the nodes (adopted stream, ctx scratch pointers, static trunk buffers) is not protected by stream order
         with self.net_lock, torch.cuda.stream(self.net_stream):
-            r = self.nodes.redo_detector_if_overflowed(self.dev[slot]["bgr"], n_det, range_safe=range_safe)
+            r = self.nodes.redo_detector_if_overflowed(self.dev[slot]["bgr"], n_det, range_safe=range_safe, id_base=self.host[slot]["id_base"])
             if r is not None:
                 self.dev[slot]["mask"].copy_(r[0])
             self.net_stream.synchronize()
@@ -502,6 +533,7 @@ class EndToEnd:
         prev = cur if self.prev is None else self.prev                   # first frame: RunNet has no previous image yet; the tracker ignores the flow of frame 0's predecessor
         with self.net_lock:
             flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None)
+            hb["id_base"] = self.nodes.id_base                           # (label_mode="instance": a later recomputation of this frame paints under the same ids)
         # graph outputs are static buffers that the next replay overwrites: park them in this slot's device buffers (three device-to-device copies of 4.8 MB in stream order)
         if self.nodes.streams is not None:
             for e in evs:
