@@ -308,29 +308,12 @@ def test_revisited_landmarks_leave_the_camera_window(vido, oracle, ctx, share, c
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"VIDO_BA_PERSIST": "1"}, {"VIDO_BA_NO_FUSED_LOCAL": "1"}, {"VIDO_BA_NO_SPEC": "1"}])
-def test_local_window_alternative_drivers_match_the_oracle(env):
-    """The local window has four drivers over the same kernels' bodies: the enqueued-ahead solve with the LM state on the device (default), the fused host-driven trial loop
-    (VIDO_BA_NO_SPEC=1), the persistent one-launch solver k_ba_local_lm (VIDO_BA_PERSIST=1: opt-in) and round 3's loop (VIDO_BA_NO_FUSED_LOCAL=1).
-    The switches are read once per process, so the alternatives run
-    the local-window oracle cases (same LM iteration AND trial counts, poses / points to 1e-4) and the facade's resident-window cross-check in a child process."""
-    import subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    e = dict(os.environ); e.update(env)
-    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_ba_gpu.py"), os.path.join(root, "tests", "test_facade_gpu.py"), "-q", "-x", "-m", "gpu",
-                        "-k", "(test_ba_matches_oracle and kw0 or test_ba_matches_oracle and kw1 or test_ba_matches_oracle and kw2 or zero_noise or device_resident_ba_window) and not alternative_drivers"],
-                       cwd=root, env=e, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
-    assert " passed" in p.stdout and "5 passed" in p.stdout, p.stdout[-1500:]
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"VIDO_BCR_SCALAR": "1"}, {"VIDO_BCR_BACK_LEVELS": "1"}, {"VIDO_BA_SCHUR_CHUNK": "64"}, {"VIDO_BA_SCHUR_CHUNK": "512"}, {"VIDO_BA_SCHUR_OLD": "1"}])
-def test_global_solver_forms_of_round_6_agree_with_the_older_ones(env, tmp_path):
-    """Round 6 changed three things inside a global LM trial: the Schur update of the block cyclic reduction (contraction over four lanes), its back substitution (ONE launch,
-    the levels chained by tagged granules: csrc/ba.hip::k_bcr_back_chain) and k_ba_schur_mfma (passes as one prefetching sequence, unit size chosen by the host).  The older
-    forms are still selectable by environment (read once per process): a child process solves the same 300-keyframe graph with each, and the results must agree with this
-    process' default forms — same LM iteration and trial counts, poses and landmarks to 1e-9 relative (they differ only in the order of a few sums)."""
+@pytest.mark.parametrize("env", [{"VIDO_BA_SCHUR_CHUNK": "64"}, {"VIDO_BA_SCHUR_CHUNK": "512"}])
+def test_global_solve_does_not_depend_on_the_schur_unit_size(env, tmp_path):
+    """k_ba_schur_mfma takes the landmarks per unit (window flush) as an argument and the host picks it from the map size (one workgroup per CU where the map allows).
+    VIDO_BA_SCHUR_CHUNK (read once per process) is the only way to reach the 64- and 512-landmark unit sizes on one map: a child process solves the same 300-keyframe graph
+    with each, and the results must agree with the size the host picks — same LM iteration and trial counts, poses and landmarks to 1e-9 relative (they differ only in the
+    order of a few sums)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys, numpy as np; sys.path.insert(0, %r); import vido_slam_amd as V\n"
@@ -341,7 +324,7 @@ def test_global_solver_forms_of_round_6_agree_with_the_older_ones(env, tmp_path)
     outs = []
     for tag, e in (("default", {}), ("alt", env)):
         f = str(tmp_path / (tag + ".npz"))
-        clean = {k: v for k, v in os.environ.items() if not k.startswith("VIDO_BCR_") and k not in ("VIDO_BA_SCHUR_CHUNK", "VIDO_BA_SCHUR_OLD")}
+        clean = {k: v for k, v in os.environ.items() if k != "VIDO_BA_SCHUR_CHUNK"}
         p = subprocess.run([sys.executable, "-c", code, f], env=dict(clean, **e), capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
         outs.append(np.load(f))

@@ -205,26 +205,26 @@ __device__ __forceinline__ void ba_flush_cam(const BaDev& P, int c, int cam0, do
 #pragma unroll
     for (int a = 0; a < 28; a++) acc[a] = 0;
 }
-// Body of the linearisation for virtual block `vb` (NT threads = NT / 64 groups of 64 consecutive observations x E).  k_ba_linearize runs it once per workgroup; the
-// persistent local-window solver (k_ba_local_lm) loops it over the blocks of its grid.  smem: LIN_SMEM_DOUBLES(NT) doubles, 16-byte aligned.  MEAS: the observation's
+// Body of the linearisation for block `vb` (LIN_THREADS threads = LIN_THREADS / 64 groups of 64 consecutive observations x E), shared by k_ba_linearize and k_bas_lin.
+// smem: LIN_SMEM_DOUBLES(LIN_THREADS) doubles, 16-byte aligned.  MEAS: the observation's
 // measurement rides along in the slot record's padding ([27, 30)) so that the trial chi2 can be formed landmark-major next to the back-substitution.
 #define LIN_SMEM_DOUBLES(NT) (LIN_SLOTS * 28 + ((NT) / 64) * 32 * LIN_RECP + (LIN_SLOTS + ((NT) / 64) * 32 + 1) / 2 + 2)
-template <int NT, bool MEAS>
+template <bool MEAS>
 __device__ __forceinline__ void ba_linearize_body(const BaDev& P, int E, int vb, double* smem)
 {
     double* lsum = smem;                                                                       // [LIN_SLOTS * 28]
-    double (*lin_stage)[32 * LIN_RECP] = (double (*)[32 * LIN_RECP])(smem + LIN_SLOTS * 28);     // [NT / 64][32 * LIN_RECP]   (LIN_SLOTS * 28 doubles = 896 bytes: 16-byte aligned)
-    int* lused = (int*)(smem + LIN_SLOTS * 28 + (NT / 64) * 32 * LIN_RECP);                      // [LIN_SLOTS]
-    int (*lin_sslot)[32] = (int (*)[32])(lused + LIN_SLOTS);                                     // [NT / 64][32]
+    double (*lin_stage)[32 * LIN_RECP] = (double (*)[32 * LIN_RECP])(smem + LIN_SLOTS * 28);     // [LIN_THREADS / 64][32 * LIN_RECP]   (LIN_SLOTS * 28 doubles = 896 bytes: 16-byte aligned)
+    int* lused = (int*)(smem + LIN_SLOTS * 28 + (LIN_THREADS / 64) * 32 * LIN_RECP);             // [LIN_SLOTS]
+    int (*lin_sslot)[32] = (int (*)[32])(lused + LIN_SLOTS);                                     // [LIN_THREADS / 64][32]
     constexpr int NREC = MEAS ? 30 : 28, NPIECE = MEAS ? 15 : 14;
     const int lane = threadIdx.x & 63;
     // (round 3: giving every XCD one CONTIGUOUS eighth of the camera-sorted list — so that the partial-line writes of a landmark's W / Cp slots meet in one L2 — was
     // measured and changed nothing: 109-112 us per 1 M edges either way, profiles/r3/README.md; the plain order stays)
-    const size_t wave_g = (size_t)vb * (NT / 64) + (threadIdx.x >> 6);
-    if ((size_t)vb * (NT / 64) * E * 64 >= (size_t)P.n_obs) return;      // (whole workgroup: the rounded-up tail)
+    const size_t wave_g = (size_t)vb * (LIN_THREADS / 64) + (threadIdx.x >> 6);
+    if ((size_t)vb * (LIN_THREADS / 64) * E * 64 >= (size_t)P.n_obs) return;      // (whole workgroup: the rounded-up tail)
     if (threadIdx.x < LIN_SLOTS * 28) lsum[threadIdx.x] = 0;
     if (threadIdx.x < LIN_SLOTS) lused[threadIdx.x] = 0;
-    const int cam0 = P.obs_cam[min((size_t)vb * (NT / 64) * E * 64, (size_t)P.n_obs - 1)];     // first camera of the workgroup
+    const int cam0 = P.obs_cam[min((size_t)vb * (LIN_THREADS / 64) * E * 64, (size_t)P.n_obs - 1)];     // first camera of the workgroup
     __syncthreads();
     double acc[28];
 #pragma unroll
@@ -330,7 +330,7 @@ __device__ __forceinline__ void ba_linearize_body(const BaDev& P, int E, int vb,
     }
     __syncthreads();
     // one thread per (slot, entry of the 6x6 block | bc | chi2): 43 atomics per camera the workgroup saw
-    for (int t = threadIdx.x; t < LIN_SLOTS * 43; t += NT) {
+    for (int t = threadIdx.x; t < LIN_SLOTS * 43; t += LIN_THREADS) {
         const int slot = t / 43, e = t - slot * 43, c = cam0 + slot;
         if (!lused[slot]) continue;
         if (e < 36) { const int a = e / 6, b = e - a * 6, lo = min(a, b), hi = max(a, b); atomicAdd(P.Hcd + 36 * c + e, lsum[slot * 28 + lo * 6 - lo * (lo - 1) / 2 + (hi - lo)]); }
@@ -341,7 +341,7 @@ __device__ __forceinline__ void ba_linearize_body(const BaDev& P, int E, int vb,
 __global__ __launch_bounds__(LIN_THREADS) void k_ba_linearize(BaDev P, int E)
 {
     __shared__ __attribute__((aligned(16))) double lin_smem[LIN_SMEM_DOUBLES(LIN_THREADS)];
-    ba_linearize_body<LIN_THREADS, false>(P, E, blockIdx.x, lin_smem);
+    ba_linearize_body<false>(P, E, blockIdx.x, lin_smem);
 }
 
 // odometry edges (k < n_odo) and the prior (k == n_odo): one wave per factor, lane a*6+b owns entry (a,b) of the
@@ -375,8 +375,9 @@ __device__ void ba_camfactor_body(const BaDev& P, int with_jac, const double* ca
 __global__ __launch_bounds__(64) void k_ba_camfactors(BaDev P, int with_jac, const double* cam, double* chi_out) { ba_camfactor_body(P, with_jac, cam, chi_out, blockIdx.x, threadIdx.x); }
 
 // max |diag| over camera blocks and landmark blocks (computeLambdaInit)
-__device__ __forceinline__ void ba_maxdiag_body(const BaDev& P, int n_ptl, int tid, int nt)
+__global__ __launch_bounds__(256) void k_ba_maxdiag(BaDev P, int n_ptl)
 {
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
     double m = 0;
     for (int a = tid; a < P.n6; a += nt) m = fmax(m, fabs(P.Hcd[36 * (a / 6) + 7 * (a % 6)]));
     for (int l = tid; l < n_ptl; l += nt) {          // runs before k_ba_schur has summed Hpp: diagonal of the landmark block from its slots
@@ -391,7 +392,6 @@ __device__ __forceinline__ void ba_maxdiag_body(const BaDev& P, int n_ptl, int t
         atomicMax((unsigned long long*)(P.scal + 1), (unsigned long long)__double_as_longlong(m));
     }
 }
-__global__ __launch_bounds__(256) void k_ba_maxdiag(BaDev P, int n_ptl) { ba_maxdiag_body(P, n_ptl, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x); }
 
 // S <- camera-camera part (+ lambda on the diagonal when add_lambda), r <- bc   (upper AND lower filled)
 // inline_odo (the dense LDS-path system of the local window, <= 64 camera-camera factors): the off-diagonal blocks of the factors are written here instead of by
@@ -442,7 +442,7 @@ __global__ void k_ba_add_odo(BaDev P)
 #ifndef BA_CHUNK
 #define BA_CHUNK 256      // landmarks per window flush: every flush is a set of HBM atomics, and atomics onto one cache line serialise (~45 ns each)
 #endif
-// (bid, nblk) = (blockIdx.x, gridDim.x) for the kernel below; the persistent local-window solver passes its own workgroup index and grid
+// (bid, nblk) = (blockIdx.x, gridDim.x) of the calling kernel (k_ba_schur, k_bas_schur)
 template <int MODE>
 __device__ __forceinline__ void ba_schur_body(const BaDev& P, int n_ptl, double lambda, int kcap, double* S_part /*[grid][n6*n6 + n6], MODE 0*/,
                                               const int* __restrict__ chunk_cmin /*MODE 2*/, const int* __restrict__ lorder /*MODE 2: landmarks by first camera*/,
@@ -1645,8 +1645,7 @@ __device__ double ba_update_cam(const BaDev& P, int c, const double* d, double l
     return sc;
 }
 
-// NT threads (>= 256): 768 in k_ba_chol_small6 (every tile of the first trailing update has its own thread), 512 inside the persistent solver (the first two steps take two rounds)
-template <int NT>
+// CH_NT = 768 threads: every tile of the first trailing update has its own thread.  Shared by k_ba_chol_small6 and k_bas_chol.
 __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_update, double lambda, double* cs6)
 {
     const int n = P.n6, nblk = n / 6, ldw = n + 1, tid = threadIdx.x;
@@ -1654,8 +1653,8 @@ __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_upd
     double* rW = W + (size_t)n * ldw;                        // [n] rhs -> z -> x
     double* Pn = rW + n;                                     // [n][7] panel rows of the current step
     __shared__ int ok;
-    for (int t = tid; t < n * n; t += NT) { const int i = t / n, j = t - i * n; if (j <= i) W[i * ldw + j] = P.S[t]; }
-    for (int t = tid; t < n; t += NT) rW[t] = P.r[t];
+    for (int t = tid; t < n * n; t += CH_NT) { const int i = t / n, j = t - i * n; if (j <= i) W[i * ldw + j] = P.S[t]; }
+    for (int t = tid; t < n; t += CH_NT) rW[t] = P.r[t];
     if (tid == 0) ok = 1;
     CH_PROF_DECL
     __syncthreads();
@@ -1741,7 +1740,7 @@ __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_upd
             lds_barrier();
             CH_TICK(3)
             // ---- B2: trailing update: tiles (row block ibr >= column block jc) except (0, 0), two 3-row halves each, packed densely
-            for (int it = tid - 192; it < nbelow * (nbelow + 1) - 2; it += NT - 192) {      // 2 half tiles per block of the lower triangle of the trailing matrix, block (0, 0) excepted
+            for (int it = tid - 192; it < nbelow * (nbelow + 1) - 2; it += CH_NT - 192) {      // 2 half tiles per block of the lower triangle of the trailing matrix, block (0, 0) excepted
             const int tl = (it >> 1) + 1, h3 = 3 * (it & 1);
             int ibr = (int)((sqrtf(8.f * (float)tl + 1.f) - 1.f) * 0.5f);
             ibr -= (ibr * (ibr + 1) / 2 > tl); ibr += ((ibr + 1) * (ibr + 2) / 2 <= tl);
@@ -1787,7 +1786,7 @@ __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_upd
                 for (int c = 0; c < 6; c++) if (tid == c) rW[pk + c] = t6[c];
             }
             lds_barrier();
-            for (int j = tid; j < pk; j += NT) {
+            for (int j = tid; j < pk; j += CH_NT) {
                 double sum = 0;
 #pragma unroll
                 for (int a = 0; a < 6; a++) sum += W[(pk + a) * ldw + j] * rW[pk + a];
@@ -1795,7 +1794,7 @@ __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_upd
             }
             lds_barrier();
         }
-        for (int t = tid; t < n; t += NT) P.x[t] = rW[t];
+        for (int t = tid; t < n; t += CH_NT) P.x[t] = rW[t];
     }
     CH_TICK(6)
     CH_PROF_PRINT("small6 [0 bar | 2 B1 | 3 bar | 4 A or B2 | 6 back]")
@@ -1811,7 +1810,7 @@ __device__ __forceinline__ void ba_chol_small6_body(const BaDev& P, int fuse_upd
 __global__ __launch_bounds__(CH_NT) void k_ba_chol_small6(BaDev P, int fuse_update, double lambda)
 {
     extern __shared__ double cs6_dyn[];
-    ba_chol_small6_body<CH_NT>(P, fuse_update, lambda, cs6_dyn);
+    ba_chol_small6_body(P, fuse_update, lambda, cs6_dyn);
 }
 
 // ---- reduced solve by block cyclic reduction (round 2) ---------------------------------------------------------------------------------------
@@ -1821,7 +1820,7 @@ __global__ __launch_bounds__(CH_NT) void k_ba_chol_small6(BaDev P, int fuse_upda
 // TRIDIAGONAL (nb = ceil(n6 / m) superblocks: 46 of 66), and cyclic reduction eliminates every other superblock of the current chain in parallel:
 //   level s (stride): blocks p = s mod 2s are eliminated — D_p = C C^T factored in LDS, GL_p = D_p^-1 L_p, GR_p = D_p^-1 L_{p+s}^T, y_p = D_p^-1 b_p
 //   (k_bcr_elim, one workgroup per eliminated block); the survivors a = 0 mod 2s take the Schur complements
-//   D_a -= L_a GR_{a-s} + L_{a+s}^T GL_{a+s},  b_a -= L_a y_{a-s} + L_{a+s}^T y_{a+s},  L_a' = -L_a GL_{a-s}   (k_bcr_update),
+//   D_a -= L_a GR_{a-s} + L_{a+s}^T GL_{a+s},  b_a -= L_a y_{a-s} + L_{a+s}^T y_{a+s},  L_a' = -L_a GL_{a-s}   (k_bcr_update4),
 // log2(nb) levels of two launches instead of 500 dependent steps; the back-substitution x_p = y_p - GL_p x_{p-s} - GR_p x_{p+s} walks the levels back.
 // Schur complements of an SPD matrix are SPD, so no pivoting is needed (block cyclic reduction is backward stable for SPD systems).  L_k is the block
 // (k, left neighbour of k in the current chain); symmetric storage is not exploited (the work is latency, not FLOPs).
@@ -1984,73 +1983,11 @@ template <int M> __global__ __launch_bounds__(BcrGeom<M>::NT) void k_bcr_elim(Bc
 //     (40 - 60 k cycles).  The thread-per-column form feeds 64 lanes x 2 FMAs from ONE broadcast read: that ratio is why it stays.
 //   * what did help: requesting the next chunk of a row before the FMAs of the current one (36.1 -> 34.5 us).
 // surviving block a = 2 s blockIdx.x takes D_a -= L_a GR_{a-s} + L_{a+s}^T GL_{a+s}, L_a' = -L_a GL_{a-s}, b_a -= L_a y_{a-s} + L_{a+s}^T y_{a+s}.
-// blockIdx.y = a slice of BCR_RB rows: the slice's rows of L_a and columns of L_{a+s} are staged in LDS (broadcast operands), thread j owns output column j of the
-// slice (BCR_RB + BCR_RB accumulators) and streams the rows of GR / GL with coalesced loads.
-#define BCR_RB 6
-__global__ __launch_bounds__(128) void k_bcr_update(BcrDev B, int s, const double* __restrict__ Lcur, double* __restrict__ Lnext)
-{
-    __shared__ double la[BCR_RB * 96], lq[BCR_RB * 96];
-    const int m = B.m, a = 2 * s * blockIdx.x, p = a - s, q = a + s, i0 = blockIdx.y * BCR_RB, j = threadIdx.x;
-    const bool has_p = p >= 0, has_q = q < B.nb;
-    const double* La = Lcur + (size_t)a * m * m; const double* Lq = Lcur + (size_t)q * m * m;
-    for (int t = j; t < BCR_RB * m; t += 128) {
-        const int r = t / m, k = t - r * m;
-        la[r * 96 + k] = has_p ? La[(size_t)(i0 + r) * m + k] : 0.0;          // L_a[i0 + r][k]
-        lq[r * 96 + k] = has_q ? Lq[(size_t)k * m + i0 + r] : 0.0;            // L_{a+s}^T[i0 + r][k]
-    }
-    __syncthreads();
-    if (j < m) {
-        const double* GRp = B.GR + (size_t)p * m * m + j; const double* GLp = B.GL + (size_t)p * m * m + j; const double* GLq = B.GL + (size_t)q * m * m + j;
-        double d[BCR_RB], ln[BCR_RB];
-#pragma unroll
-        for (int r = 0; r < BCR_RB; r++) { d[r] = 0.0; ln[r] = 0.0; }
-        if (has_p) {
-#pragma unroll 22
-            for (int k = 0; k < m; k++) {
-                const double gr = GRp[(size_t)k * m], gl = -GLp[(size_t)k * m];
-#pragma unroll
-                for (int r = 0; r < BCR_RB; r++) { const double l = la[r * 96 + k]; d[r] = __builtin_fma(l, gr, d[r]); ln[r] = __builtin_fma(l, gl, ln[r]); }
-            }
-        }
-        if (has_q) {
-#pragma unroll 22
-            for (int k = 0; k < m; k++) {
-                const double gl = GLq[(size_t)k * m];
-#pragma unroll
-                for (int r = 0; r < BCR_RB; r++) d[r] = __builtin_fma(lq[r * 96 + k], gl, d[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < BCR_RB; r++) {
-            B.D[(size_t)a * m * m + (size_t)(i0 + r) * m + j] -= d[r];
-            Lnext[(size_t)a * m * m + (size_t)(i0 + r) * m + j] = ln[r];        // block (a, a - 2s)
-        }
-    } else if (j >= 96 && j < 96 + BCR_RB) {
-        const int r = j - 96; double dv = 0.0;
-        if (has_p) for (int k = 0; k < m; k++) dv += la[r * 96 + k] * B.y[(size_t)p * m + k];
-        if (has_q) for (int k = 0; k < m; k++) dv += lq[r * 96 + k] * B.y[(size_t)q * m + k];
-        B.b[(size_t)a * m + i0 + r] -= dv;
-    }
-}
-// x_p = y_p - GL_p x_{p-s} - GR_p x_{p+s} for the blocks eliminated at level s; four lanes per row, each a quarter of the two dot products
-__global__ __launch_bounds__(384) void k_bcr_back(BcrDev B, int s)
-{
-    const int m = B.m, p = s + 2 * s * blockIdx.x, i = threadIdx.x >> 2, sub = threadIdx.x & 3;
-    double v = 0.0;
-    const int gi = p * m + i;
-    if (i < m) {
-        const double* gl = B.GL + (size_t)p * m * m + (size_t)i * m; const double* gr = B.GR + (size_t)p * m * m + (size_t)i * m;
-        const int l0 = (p - s) * m, r0 = (p + s) * m;
-        for (int k = sub; k < m; k += 4) { if (l0 + k < B.n6) v += gl[k] * B.x[l0 + k]; }
-        if (p + s < B.nb) for (int k = sub; k < m; k += 4) { if (r0 + k < B.n6) v += gr[k] * B.x[r0 + k]; }
-    }
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64);
-    if (i < m && sub == 0 && gi < B.n6) B.x[gi] = B.y[(size_t)p * m + i] - v;
-}
-
-// ---- round 6: the Schur update with the contraction split over four lanes, and the whole back substitution as ONE launch ---------------------------------------
-// k_bcr_update walks three 66-term contractions per thread with two dependent-latency-bound global loads per term (23 us per level for 1.7 MFLOP).  Here thread (j, kh)
+// blockIdx.y = a slice of BCR_RB rows: the slice's rows of L_a and columns of L_{a+s} are staged in LDS (broadcast operands), the rows of GR / GL are streamed with
+// coalesced loads.  A thread per output column (round 5) walked three 66-term contractions with two dependent-latency-bound global loads per term (23 us per level for
+// 1.7 MFLOP).  Here thread (j, kh)
 // takes the terms k = kh mod 4 of output column j: every load of a thread is in flight at once (17 + 17 + 17), the four partial sums meet in LDS.
+#define BCR_RB 6
 __global__ __launch_bounds__(320) void k_bcr_update4(BcrDev B, int s, const double* __restrict__ Lcur, double* __restrict__ Lnext)
 {
     __shared__ double la[BCR_RB * 96], lq[BCR_RB * 96], part[3][2 * BCR_RB][96];
@@ -2146,7 +2083,7 @@ __global__ __launch_bounds__(384) void k_bcr_back_chain(BcrDev B, const int2* __
     __syncthreads();
     double v = 0.0;
     if (i < m) {
-        // (the order of k_bcr_back: the left neighbour's terms, then the right one's, then the four lanes)
+        // (fixed order: the left neighbour's terms, then the right one's, then the four lanes)
 #pragma unroll
         for (int t = 0; t < 24; t++) { const int k = sub + 4 * t; if (k < m && l0 + k < B.n6) v += gl[t] * xs[0][k]; }
         if (has_r) {
@@ -2217,27 +2154,17 @@ __global__ __launch_bounds__(256) void k_ba_chi2(BaDev P, const double* cam, con
     block_atomic_add(out, acc);
 }
 
-// ---- the local window as ONE persistent launch (round 4) ------------------------------------------------------------------------------------------------------
+// ---- the local window: the phases of an LM trial, bodies shared by the k_bas_* kernels below --------------------------------------------------------------------
 // Round 3 drove the window's Levenberg-Marquardt loop from the host: ~10 launches and one read-back per trial, ~9 trials per frame — about 100 dependent stream operations
-// per solve, each of which queues behind the networks' convolution workgroups when the tracker shares the GPU (2.0 ms alone, 4.6 ms inside the pipeline).  Here the whole
-// solve (core/optimization_algorithm_levenberg.cpp:61-189 around block_solver.hpp:354-486) is one launch of a few dozen resident workgroups that walk the phases of an
-// iteration together, separated by grid-wide barriers (xwg.hpp), and take the accept / reject / stop decisions from the same reduced scalars — every thread of every
-// workgroup runs the same control flow, no broadcast, no host:
-//   L   linearise (ba_linearize_body over the grid's share of the observations, the measurement stored next to W) + camera-camera factors
+// per solve, each of which queues behind the networks' convolution workgroups when the tracker shares the GPU (2.0 ms alone, 4.6 ms inside the pipeline).  The phases:
+//   L   linearise (ba_linearize_body, the measurement stored next to W) + camera-camera factors
 //   M   first iteration only: max |diagonal| for the initial lambda
 //   S   Schur complement of this workgroup's landmarks into its LDS copy of the reduced system -> one partial per workgroup
 //   F   fold: S = camera part + lambda I + sum of the partials (plain stores: nothing to clear, no atomics), r likewise
-//   C   workgroup 0: pose-block Cholesky + back sweep in LDS, trial cameras, camera part of computeScale; the others wait
+//   C   one workgroup: pose-block Cholesky + back sweep in LDS, trial cameras, camera part of computeScale
 //   B   back-substitution with the trial's chi2 formed per landmark from the slot records (8 lanes per landmark), camera-camera factors at the trial state; the
 //       accumulators of the NEXT linearisation (the other of two copies) are cleared here
-// and then decide.  5 barriers per iteration; the accepted state flips between two buffers and is copied home at the end.
-struct BaLmCtl { unsigned bar_count, abort_word; int status, iterations, trials, n_lin, barriers, pad; double lambda_final, chi2_initial, chi2_final, lin_ticks; };
-struct BaLocalArgs {
-    BaLmCtl* ctl; double *red0, *red1, *S_part, *cam_out, *pt_home;
-    int n_ptl, kcap, max_iters; unsigned bar_base; double gain_threshold;
-};
-#define BAL_NT 512
-
+// and then decide; the accepted state flips between two buffers.
 __device__ __forceinline__ double bal_ld(const double* p) { return __longlong_as_double((long long)xwg_load64((const unsigned long long*)p)); }
 __device__ __forceinline__ void bal_st(double* p, double v) { xwg_store64((unsigned long long*)p, (unsigned long long)__double_as_longlong(v)); }
 
@@ -2321,46 +2248,17 @@ __device__ __forceinline__ void ba_backsub_chi2_body(const BaDev& P, int n_ptl, 
     if (threadIdx.x < 2) { double t = 0; for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += wsum[16 * threadIdx.x + w]; if (t != 0) atomicAdd(P.scal + (threadIdx.x == 0 ? 3 : 2), t); }
 }
 
-// ---- the same bodies as stand-alone launches of the HOST-driven local-window loop (the default: see DESIGN.md section 9 for why the persistent form is opt-in).  Round 3
-// spent 11 stream operations per LM iteration on the window (memset, linearise, camera factors | init S, Schur, fold, memset, Cholesky, back-substitution, chi2, camera
-// factors, read-back); with these it is 6: the camera factors ride in the linearisation / back-substitution launches as extra workgroups, the fold writes S outright (no
-// init, no atomics), the trial chi2 is formed landmark-major inside the back-substitution, the accumulators are double-buffered and cleared by the previous iteration.
-__global__ __launch_bounds__(LIN_THREADS) void k_ba_lin_local(BaDev P, int nvb)
-{
-    __shared__ __attribute__((aligned(16))) double lin_smem[LIN_SMEM_DOUBLES(LIN_THREADS)];
-    if ((int)blockIdx.x < nvb) { ba_linearize_body<LIN_THREADS, true>(P, 1, blockIdx.x, lin_smem); return; }
-    ba_camfactor_body(P, 1, P.cam, P.scal + 0, ((int)blockIdx.x - nvb) * (LIN_THREADS / 64) + (int)(threadIdx.x >> 6), threadIdx.x & 63);      // (a factor index past the list returns)
-}
-__global__ __launch_bounds__(256) void k_ba_fold_local(BaDev P, const double* S_part, int nparts, double lambda) { ba_fold_local_body(P, S_part, nparts, lambda, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256); }
-// (the LAST workgroup to finish — ticket counter, the classic threadfence reduction — copies the trial's five scalars straight into the host's pinned block: the host waits for
-//  the launch and reads them there, one copy per trial less on the stream)
-__global__ __launch_bounds__(256) void k_ba_backsub_chi2_local(BaDev P, int n_ptl, double lambda, int n_bs, double* zero_buf, int zero_len, int* ticket, double* host_scal)
-{
-    __shared__ double wsum[32];
-    __shared__ int is_last;
-    if ((int)blockIdx.x < n_bs) {
-        ba_backsub_chi2_body(P, n_ptl, lambda, blockIdx.x * 256 + threadIdx.x, n_bs * 256, wsum);
-        if (zero_buf) for (int t = blockIdx.x * 256 + threadIdx.x; t < zero_len; t += n_bs * 256) zero_buf[t] = 0.0;      // the NEXT linearisation's accumulators (the other copy)
-    } else ba_camfactor_body(P, 0, P.cam_new, P.scal + 2, ((int)blockIdx.x - n_bs) * 4 + (int)(threadIdx.x >> 6), threadIdx.x & 63);
-    __threadfence();                                            // this workgroup's atomics have been performed before its ticket is drawn
-    __syncthreads();
-    if (threadIdx.x == 0) is_last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (is_last) {
-        if (threadIdx.x < 5) host_scal[threadIdx.x] = bal_ld(P.scal + threadIdx.x);
-        if (threadIdx.x == 0) *ticket = 0;
-    }
-}
-
 // The solver's state flips between two buffers (accepted / trial) and the linearisation's accumulators between two copies: four variants of the problem descriptor, all
 // in the kernel arguments (constant memory, read with scalar loads where a field is used); `sel` picks one.  A descriptor mutated in place would live in registers.
 struct BaDev4 { BaDev v[4]; };      // [accumulator copy (iteration parity)][state flip]
-static_assert(sizeof(BaDev4) + sizeof(BaLocalArgs) <= 4000, "kernel arguments of k_ba_local_lm exceed the 4 KB kernarg segment");
-// ---- the local window ENQUEUED AHEAD (the default): the phases of the fused host-driven loop as launches that take the LM state from DEVICE memory (BaSpecCtl) and the
-// problem descriptor as the four variants of BaDev4, so the host can put a whole solve's trials on the stream without waiting for any of them.  A trial slot is
+// ---- the local window ENQUEUED AHEAD: the phases above as launches that take the LM state from DEVICE memory (BaSpecCtl) and the
+// problem descriptor as the four variants of BaDev4, so the host can put a whole solve's trials on the stream without waiting for any of them.  Round 3
+// spent 11 stream operations per LM iteration on the window (memset, linearise, camera factors | init S, Schur, fold, memset, Cholesky, back-substitution, chi2, camera
+// factors, read-back); here it is 5 launches: the camera factors ride in the linearisation / back-substitution launches as extra workgroups, the fold writes S outright (no
+// init, no atomics), the trial chi2 is formed landmark-major inside the back-substitution, the accumulators are double-buffered and cleared by the previous iteration.  A trial slot is
 // S, F, C, B (+ the LM policy, run by the last workgroup of B) and L, which only runs when the policy accepted the trial and asked for a new linearisation; every launch
 // returns at once when the policy has stopped the solve.  The policy is g2o's (optimization_algorithm_levenberg.cpp:61-189 + the facade's stop rules), the same
-// arithmetic as the host loop below and k_ba_local_lm: identical LM traces (tests/test_ba_gpu.py).
+// arithmetic as the host loop of ba_run: identical LM traces (tests/test_ba_gpu.py).
 struct BaSpecCtl {
     double lambda, ni, currentChi, iniChi, chi2_check, lastChi, chi_init, chi_final, gain_threshold;
     int it, qmax, nBad, flip, stop, need_lin, trials, max_iters;
@@ -2371,7 +2269,7 @@ __global__ __launch_bounds__(LIN_THREADS) void k_bas_lin(BaDev4 V, const BaSpecC
     __shared__ __attribute__((aligned(16))) double lin_smem[LIN_SMEM_DOUBLES(LIN_THREADS)];
     if (c->stop || !c->need_lin) return;
     const BaDev& P = bas_sel(V, c);
-    if ((int)blockIdx.x < nvb) { ba_linearize_body<LIN_THREADS, true>(P, 1, blockIdx.x, lin_smem); return; }
+    if ((int)blockIdx.x < nvb) { ba_linearize_body<true>(P, 1, blockIdx.x, lin_smem); return; }
     ba_camfactor_body(P, 1, P.cam, P.scal + 0, ((int)blockIdx.x - nvb) * (LIN_THREADS / 64) + (int)(threadIdx.x >> 6), threadIdx.x & 63);
 }
 __global__ void k_bas_init(BaDev4 V, BaSpecCtl* c)       // after the first linearisation + max diagonal: lambda_0 = tau * max diag (tau = 1e-5), chi2 at the initial state
@@ -2395,7 +2293,7 @@ __global__ __launch_bounds__(CH_NT) void k_bas_chol(BaDev4 V, const BaSpecCtl* c
 {
     extern __shared__ double cs6_dyn[];
     if (c->stop) return;
-    ba_chol_small6_body<CH_NT>(bas_sel(V, c), 1, c->lambda, cs6_dyn);
+    ba_chol_small6_body(bas_sel(V, c), 1, c->lambda, cs6_dyn);
 }
 __global__ __launch_bounds__(256) void k_bas_backsub(BaDev4 V, BaSpecCtl* c, int n_ptl, int n_bs, double* red0, double* red1, int red_len, int* ticket, BaSpecCtl* host_ctl)
 {
@@ -2443,81 +2341,6 @@ __global__ __launch_bounds__(256) void k_bas_backsub(BaDev4 V, BaSpecCtl* c, int
     *c = s;
     __threadfence_system();
     *host_ctl = s;                                                               // the host polls / reads the pinned mirror
-}
-
-__global__ __launch_bounds__(BAL_NT) void k_ba_local_lm(BaDev4 V, BaLocalArgs A)
-{
-    extern __shared__ __attribute__((aligned(16))) double bal_smem[];
-    __shared__ int bar_flag;
-    __shared__ double bal_wsum[32];
-    const int bid = blockIdx.x, nblk = gridDim.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = BAL_NT / 64, gt = bid * BAL_NT + tid, gnt = nblk * BAL_NT;
-    unsigned phase = 0; bool dead = false;
-    auto barrier = [&]() { if (!dead && !xwg_grid_barrier(&A.ctl->bar_count, &A.ctl->abort_word, (unsigned)nblk, A.bar_base, ++phase, &bar_flag)) dead = true; };
-    const int n6 = V.v[0].n6, n_cam = V.v[0].n_cam, n_obs = V.v[0].n_obs, ncf = V.v[0].n_odo + (V.v[0].prior_cam >= 0 ? 1 : 0);
-    const size_t red_len = (size_t)n_cam * 36 + n6 + 8;
-    for (size_t t = gt; t < red_len; t += gnt) { A.red0[t] = 0.0; A.red1[t] = 0.0; }
-    barrier();
-    double lambda = -1, ni = 2, lastChi = 0, chi2_check = 0, chi_init = 0, chi_final = 0, lin_ticks = 0; int nBad = 0, trials = 0, it = 0, n_lin = 0, flip = 0;
-    for (it = 0; it < A.max_iters && !dead; it++) {
-        double* red_next = (it & 1) ? A.red0 : A.red1;
-        // ---- L
-        const long long tk0 = wall_clock64();
-        { const BaDev& P = V.v[(it & 1) * 2 + flip];
-          const int nvb = (n_obs + BAL_NT - 1) / BAL_NT;
-          for (int vb = bid; vb < nvb; vb += nblk) { ba_linearize_body<BAL_NT, true>(P, 1, vb, bal_smem); __syncthreads(); }
-          for (int f = bid * nw + wave; f < ncf; f += nblk * nw) ba_camfactor_body(P, 1, P.cam, P.scal + 0, f, lane); }
-        barrier();
-        lin_ticks += (double)(wall_clock64() - tk0); n_lin++;
-        if (it == 0) { ba_maxdiag_body(V.v[flip], A.n_ptl, gt, gnt); barrier(); }
-        const double* scal = V.v[(it & 1) * 2].scal;
-        double currentChi = bal_ld(scal + 0); const double iniChi = currentChi;
-        if (it == 0) { lambda = 1e-5 * bal_ld(scal + 1); ni = 2; nBad = 0; chi_init = currentChi; chi_final = currentChi; }
-        double rho = 0; int qmax = 0;
-        do {
-            const BaDev& P = V.v[(it & 1) * 2 + flip];
-            // ---- S
-            ba_schur_body<0>(P, A.n_ptl, lambda, A.kcap, A.S_part, (const int*)nullptr, (const int*)nullptr, (const int2*)nullptr, bid, nblk, bal_smem);
-            barrier();
-            // ---- F
-            ba_fold_local_body(P, A.S_part, nblk, lambda, gt, gnt);
-            barrier();
-            // ---- C
-            if (bid == 0) ba_chol_small6_body<BAL_NT>(P, 1, lambda, bal_smem);
-            barrier();
-            // ---- B
-            ba_backsub_chi2_body(P, A.n_ptl, lambda, gt, gnt, bal_wsum);
-            for (int f = bid * nw + wave; f < ncf; f += nblk * nw) ba_camfactor_body(P, 0, P.cam_new, P.scal + 2, f, lane);
-            if (qmax == 0) for (size_t t = gt; t < red_len; t += gnt) red_next[t] = 0.0;      // (the other copy was last read in the previous iteration)
-            barrier();
-            const bool ok2 = bal_ld(scal + 4) > 0.5;
-            const double tempChi = ok2 ? bal_ld(scal + 2) : DBL_MAX, scale = ok2 ? bal_ld(scal + 3) : 0.0;
-            rho = (currentChi - tempChi) / (scale + 1e-3);
-            if (rho > 0 && isfinite(tempChi)) {
-                const double tr = 2 * rho - 1; double alpha = 1. - tr * tr * tr; alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi;
-                flip ^= 1;                                   // the trial state becomes the accepted one
-            } else { lambda *= ni; ni *= 2; }
-            qmax++; trials++;
-        } while (rho < 0 && qmax < 10 && !dead);
-        bool terminate = (qmax == 10 || rho == 0);
-        if (!terminate) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; if (nBad >= 3) terminate = true; }
-        const double chiNow = currentChi;
-        if (chi2_check < chiNow && it > 0) terminate = true;
-        chi2_check = chiNow;
-        if (it == 0) lastChi = chiNow;
-        else { const double gain = (lastChi - chiNow) / chiNow; lastChi = chiNow; if (gain >= 0 && gain < A.gain_threshold) terminate = true; }
-        chi_final = chiNow;
-        if (terminate) { it++; break; }
-    }
-    // the accepted state goes home: cameras into cam_out, landmarks into the caller's array when the last accepted trial left them in the other buffer
-    { const BaDev& P = V.v[flip];
-      for (int t = gt; t < n_cam * 12; t += gnt) A.cam_out[t] = P.cam[t];
-      if (P.pt != A.pt_home) for (size_t t = gt; t < (size_t)A.n_ptl * 3; t += gnt) A.pt_home[t] = P.pt[t]; }
-    if (gt == 0) {
-        BaLmCtl* c = A.ctl;
-        c->status = dead ? 1 : 0; c->iterations = it; c->trials = trials; c->n_lin = n_lin; c->barriers = (int)phase;
-        c->lambda_final = lambda; c->chi2_initial = chi_init; c->chi2_final = chi_final; c->lin_ticks = lin_ticks;
-    }
 }
 
 // ---- object part: dynamic-point chains -------------------------------------------------------------------------
@@ -2797,18 +2620,17 @@ struct BaState {
     int* d_long = nullptr; size_t long_cap = 0;      // landmarks with > 64 observations
     double* d_bcr = nullptr; size_t bcr_cap = 0;     // block-cyclic-reduction workspace (superblocks D, L x2, GL, GR, b, y)
     unsigned long long* d_bcr_xt = nullptr; size_t bcr_xt_cap = 0; int2* d_bcr_blocks = nullptr; int bcr_blocks_nb = 0, bcr_blocks_n = 0; unsigned bcr_epoch = 0; unsigned* d_bcr_abort = nullptr;      // k_bcr_back_chain: tagged granules of x, its (block, level) list, the solve counter
-    int* d_ticket = nullptr;                        // k_ba_backsub_chi2_local: workgroups finished so far (reset by the last one)
+    int* d_ticket = nullptr;                        // k_bas_backsub: workgroups finished so far (reset by the last one)
     std::vector<int> hv_i[8]; std::vector<double> hv_d;      // host scratch of the set-up (observation tables of the call): kept across calls — as fresh vectors they were ~40 MB of
                                                               // mmap + page faults + zero fill per global solve, the largest and most variable part of its host time
     struct BaSpecCtl* d_spec = nullptr; struct BaSpecCtl* h_spec = nullptr; int spec_last_trials = 12;      // the enqueued-ahead local solve: LM state on the device, its pinned mirror, the previous solve's trial count
-    struct BaLmCtl* d_ctl = nullptr; struct BaLmCtl* h_ctl = nullptr; unsigned bar_base = 0;   // persistent local-window solver: control block (device + pinned mirror), barrier count so far
 };
 void ba_state_destroy(vido_ctx* ctx)
 {
     BaState* S = ctx->ba; if (!S) return;
     for (void* p : S->allocs) hipFree(p);
     hipFree(S->d_parts); hipFree(S->d_scratch); hipHostFree(S->h_scal); hipFree(S->pool); hipHostFree(S->h_pool); hipFree(S->d_long); hipFree(S->d_bcr); hipFree(S->d_bcr_xt); hipFree(S->d_bcr_blocks); hipFree(S->d_bcr_abort);
-    hipFree(S->d_ctl); hipHostFree(S->h_ctl); hipFree(S->d_ticket); hipFree(S->d_spec); hipHostFree(S->h_spec);
+    hipFree(S->d_ticket); hipFree(S->d_spec); hipHostFree(S->h_spec);
     if (S->ev0) hipEventDestroy(S->ev0);
     if (S->ev1) hipEventDestroy(S->ev1);
     if (S->ev2) hipEventDestroy(S->ev2);
@@ -3358,8 +3180,7 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
     double* red = A.get<double>((size_t)n_pose * 36 + n6 + 8);      // [Hcd | bc | scal] contiguous for the linearisation all-reduce
     D.Hcd = red; D.bc = red + (size_t)n_pose * 36; D.scal = D.bc + n6;
     Bc.ok = D.scal + 4;
-    double* red1 = A.get<double>((size_t)n_pose * 36 + n6 + 8);     // second copy of the linearisation accumulators + the accepted cameras (persistent local-window solver)
-    double* cam_out = A.get<double>((size_t)n_pose * 12);
+    double* red1 = A.get<double>((size_t)n_pose * 36 + n6 + 8);     // second copy of the linearisation accumulators (the enqueued-ahead local solve)
     if (A.failed) return vido_set_error(ctx, VIDO_E_NOMEM, "ba: device allocation failed (n6=%d, n_obs=%d)", n6, no);
 #ifndef BA_SCHUR0_GRID
 #define BA_SCHUR0_GRID 256
@@ -3396,7 +3217,7 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
     // pipes and finish together, late), 121 carry one; units of 416 are 241 workgroups of 13 passes each, every one alone on its CU with its own loads in flight beside
     // its matrix phase
     int chunk = BA_CHUNK;
-    const bool mfma_schur_wanted = nd == 0 && !getenv("VIDO_BA_SCHUR_OLD");
+    const bool mfma_schur_wanted = nd == 0;
     if (mfma_schur_wanted && !lds_path && n_ptl) {
         static const int force_chunk = [] { const char* e = getenv("VIDO_BA_SCHUR_CHUNK"); return e ? atoi(e) : 0; }();
         int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device); if (ncu < 1) ncu = 256;
@@ -3499,59 +3320,14 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
     res->ms_setup = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     const auto t_loop = std::chrono::steady_clock::now();
     double lambda = -1, ni = 2, lastChi = 0, chi2_check = 0, ms_lin = 0, ms_schur = 0; int nBad = 0, trials = 0, it = 0, n_lin = 0, n_schur_timed = 0, n_schur_read = 0;
-    // ---- the local window as one persistent launch (k_ba_local_lm): static graph, LDS-resident reduced system, one GPU
-    // (opt-in, VIDO_BA_PERSIST=1: measured SLOWER than the host-driven loop below — 3.0 against 2.1 ms per solve alone on the GPU — and its 32 full-CU workgroups never
-    //  all become resident while the networks keep the chip busy; DESIGN.md section 9.  The default local-window path is the enqueued-ahead form of the fused loop below (`spec`); VIDO_BA_NO_SPEC=1 keeps the host-driven trial loop `fl`.)
-    static const bool want_persist = getenv("VIDO_BA_PERSIST") != nullptr, no_fused_local = getenv("VIDO_BA_NO_FUSED_LOCAL") != nullptr;
-    const bool local_static = lds_path && !allreduce && nd == 0 && n6 % 6 == 0 && n6 >= 12 && n_pose <= 64 && D.n_odo <= 64 && n_long == 0 && p.max_iters >= 1 && n_ptl > 0 && no > 0;
-    bool persist = local_static && want_persist;
-    const double* cam_final = nullptr;
-    if (persist) {
-        static const int persist_wgs = [] { const char* e = getenv("VIDO_BA_PERSIST_WGS"); const int v = e ? atoi(e) : 32; return std::max(1, std::min(v, 64)); }();
-        const size_t lds_bal = std::max(std::max(lds_chol6, (loc_sz + (size_t)(BAL_NT / 64) * (2 * kcap * 18 + kcap)) * sizeof(double)), (size_t)LIN_SMEM_DOUBLES(BAL_NT) * sizeof(double));
-        if (lds_bal > 159 * 1024) persist = false;
-        else {
-            if (!BS->d_ctl) { HIP_TRY(ctx, hipMalloc((void**)&BS->d_ctl, sizeof(BaLmCtl))); HIP_TRY(ctx, hipMemset(BS->d_ctl, 0, sizeof(BaLmCtl))); HIP_TRY(ctx, hipHostMalloc((void**)&BS->h_ctl, sizeof(BaLmCtl))); BS->bar_base = 0; }
-            if ((size_t)persist_wgs * loc_sz > BS->parts_cap) {
-                HIP_TRY(ctx, hipStreamSynchronize(st)); if (BS->d_parts) hipFree(BS->d_parts);
-                BS->parts_cap = (size_t)BA_SCHUR0_GRID * sz_sr; HIP_TRY(ctx, hipMalloc((void**)&BS->d_parts, BS->parts_cap * sizeof(double)));
-            }
-            HIP_TRY(ctx, ba_lds_attr(ctx->device, (const void*)k_ba_local_lm, (size_t)(lds_bal)));
-            BaDev4 V;
-            for (int par = 0; par < 2; par++) for (int flip = 0; flip < 2; flip++) {
-                BaDev& Q = V.v[par * 2 + flip]; Q = D;
-                double* rp = par ? red1 : red; Q.Hcd = rp; Q.bc = rp + (size_t)n_pose * 36; Q.scal = Q.bc + n6;
-                if (flip) { std::swap(Q.cam, Q.cam_new); std::swap(Q.pt, Q.pt_new); }
-            }
-            BaLocalArgs LA{BS->d_ctl, red, red1, BS->d_parts, cam_out, D.pt, n_ptl, kcap, p.max_iters, BS->bar_base, p.gain_threshold};
-            hipLaunchKernelGGL(k_ba_local_lm, dim3(persist_wgs), dim3(BAL_NT), lds_bal, st, V, LA);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(BS->h_ctl, BS->d_ctl, sizeof(BaLmCtl), hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(poses.data(), cam_out, (size_t)n_pose * 12 * sizeof(double), hipMemcpyDeviceToHost, st));      // (pageable destination: the copy is complete on return)
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            const BaLmCtl& C = *BS->h_ctl;
-            if (C.status != 0) {      // a workgroup never arrived at a barrier (never seen; the spins are bounded so that this is an error, not a hang)
-                HIP_TRY(ctx, hipMemset(BS->d_ctl, 0, sizeof(BaLmCtl))); BS->bar_base = 0;
-                return vido_set_error(ctx, VIDO_E_HIP, "ba: the persistent local-window solver lost a workgroup at a grid barrier (%d barriers in)", C.barriers);
-            }
-            BS->bar_base += (unsigned)C.barriers * (unsigned)persist_wgs;
-            it = C.iterations; trials = C.trials; lambda = C.lambda_final; n_lin = C.n_lin; ms_lin = C.lin_ticks * 1e-5;      // wall_clock64: 100 MHz
-            res->chi2_initial = C.chi2_initial; res->chi2_final = C.chi2_final;
-            cam_final = cam_out;
-        }
-    }
-    // the fused host-driven loop of the local window (k_ba_lin_local / k_ba_fold_local / k_ba_backsub_chi2_local): 6 stream operations per LM iteration instead of 11
-    const bool fl = local_static && !persist && !no_fused_local;
-    if (fl && !BS->d_ticket) { HIP_TRY(ctx, hipMalloc((void**)&BS->d_ticket, sizeof(int))); HIP_TRY(ctx, hipMemset(BS->d_ticket, 0, sizeof(int))); }
-    static const int fl_schur_grid_env = [] { const char* e = getenv("VIDO_BA_SCHUR0_GRID"); return e ? std::max(1, std::min(atoi(e), BA_SCHUR0_GRID)) : 128; }();
-    const int fl_grid = std::min(fl_schur_grid_env, std::max(1, (n_ptl + 3) / 4));       // partial reduced systems: every one is summed by the fold; tracker alone: 32 / 64 / 128 / 256 partials -> 2.49 / 2.13 / 1.95 / 1.95 ms per solve
-    const size_t red_len = (size_t)n_pose * 36 + n6 + 8;
-    // ---- the local window enqueued ahead (default; VIDO_BA_NO_SPEC=1 keeps the host-driven trial loop below): the LM state lives on the device, the host puts
+    // ---- a static local window (LDS-resident reduced system, one GPU) is enqueued ahead: the LM state lives on the device, the host puts
     // (previous solve's trials + 2) trial slots on the stream in one go and waits ONCE; a solve that needs more gets four more slots at a time.  No host round trip per trial:
     // inside the pipeline each one cost a stream drain behind the networks' workgroups.
-    static const bool no_spec = getenv("VIDO_BA_NO_SPEC") != nullptr;
-    const bool spec = fl && !no_spec;
-    if (spec) {
+    const bool local_static = lds_path && !allreduce && nd == 0 && n6 % 6 == 0 && n6 >= 12 && n_pose <= 64 && D.n_odo <= 64 && n_long == 0 && p.max_iters >= 1 && n_ptl > 0 && no > 0;
+    if (local_static) {
+        if (!BS->d_ticket) { HIP_TRY(ctx, hipMalloc((void**)&BS->d_ticket, sizeof(int))); HIP_TRY(ctx, hipMemset(BS->d_ticket, 0, sizeof(int))); }
+        const int parts_grid = std::min(128, std::max(1, (n_ptl + 3) / 4));       // partial reduced systems: every one is summed by the fold; tracker alone: 32 / 64 / 128 / 256 partials -> 2.49 / 2.13 / 1.95 / 1.95 ms per solve
+        const size_t red_len = (size_t)n_pose * 36 + n6 + 8;
         if (!BS->d_spec) { HIP_TRY(ctx, hipMalloc((void**)&BS->d_spec, sizeof(BaSpecCtl))); HIP_TRY(ctx, hipHostMalloc((void**)&BS->h_spec, sizeof(BaSpecCtl))); }
         BaDev4 V;
         for (int par = 0; par < 2; par++) for (int flip = 0; flip < 2; flip++) {
@@ -3573,8 +3349,8 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
         int budget = std::max(4, std::min(BS->spec_last_trials + 2, 48)), enq = 0;
         for (;;) {
             for (int sl = 0; sl < budget; sl++) {
-                hipLaunchKernelGGL(k_bas_schur, dim3(fl_grid), dim3(64 * schur0_waves), lds_schur, st, V, (const BaSpecCtl*)BS->d_spec, n_ptl, kcap, BS->d_parts);
-                hipLaunchKernelGGL(k_bas_fold, dim3(fold_grid), dim3(256), 0, st, V, (const BaSpecCtl*)BS->d_spec, (const double*)BS->d_parts, fl_grid);
+                hipLaunchKernelGGL(k_bas_schur, dim3(parts_grid), dim3(64 * schur0_waves), lds_schur, st, V, (const BaSpecCtl*)BS->d_spec, n_ptl, kcap, BS->d_parts);
+                hipLaunchKernelGGL(k_bas_fold, dim3(fold_grid), dim3(256), 0, st, V, (const BaSpecCtl*)BS->d_spec, (const double*)BS->d_parts, parts_grid);
                 hipLaunchKernelGGL(k_bas_chol, dim3(1), dim3(CH_NT), lds_chol6, st, V, (const BaSpecCtl*)BS->d_spec);
                 hipLaunchKernelGGL(k_bas_backsub, dim3(n_bs + (ncf + 3) / 4), dim3(256), 0, st, V, BS->d_spec, n_ptl, n_bs, red, red1, (int)red_len, BS->d_ticket, BS->h_spec);
                 hipLaunchKernelGGL(k_bas_lin, dim3(lin_grid), dim3(LIN_THREADS), 0, st, V, (const BaSpecCtl*)BS->d_spec, nvb);
@@ -3592,166 +3368,135 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
         n_lin = hs.it;
         { float ms = 0; if (hipEventElapsedTime(&ms, BS->ev0, BS->ev1) == hipSuccess) ms_lin = ms * n_lin; }
         if (hs.flip) { std::swap(D.cam, D.cam_new); std::swap(D.pt, D.pt_new); }
-    }
-    if (!persist && !spec) {
-    if (!fl) { if ((rc = chi2_at(D.cam, D.pt, 2, &res->chi2_initial))) return rc; res->chi2_final = res->chi2_initial; }
-    for (it = 0; it < p.max_iters; it++) {
-        // ---- linearise
-        const int ncf = D.n_odo + (D.prior_cam >= 0 ? 1 : 0);
-        if (fl) {
-            // accumulators double-buffered by iteration parity: this iteration's copy was cleared by the previous iteration's back-substitution launch (both copies — they are
-            // neighbours in the arena — by one memset before the first)
-            if (it == 0) HIP_TRY(ctx, hipMemsetAsync(red, 0, (size_t)((char*)(red1 + red_len) - (char*)red), st));
-            double* rp = (it & 1) ? red1 : red; D.Hcd = rp; D.bc = rp + (size_t)n_pose * 36; D.scal = D.bc + n6;
-            const int nvb = (no + LIN_THREADS - 1) / LIN_THREADS;
-            if (it == 0) HIP_TRY(ctx, hipEventRecord(BS->ev0, st));
-            hipLaunchKernelGGL(k_ba_lin_local, dim3(nvb + (ncf + LIN_THREADS / 64 - 1) / (LIN_THREADS / 64)), dim3(LIN_THREADS), 0, st, D, nvb);
-            if (it == 0) { HIP_TRY(ctx, hipEventRecord(BS->ev1, st)); n_lin++; }
-        } else {
-        HIP_TRY(ctx, hipMemsetAsync(red, 0, ((size_t)n_pose * 36 + n6 + 8) * sizeof(double), st));
-        HIP_TRY(ctx, hipEventRecord(BS->ev0, st));
-        if (no) hipLaunchKernelGGL(k_ba_linearize, dim3((no + LIN_THREADS * lin_E - 1) / (LIN_THREADS * lin_E)), dim3(LIN_THREADS), 0, st, D, lin_E);
-        HIP_TRY(ctx, hipEventRecord(BS->ev1, st));
-        if (nd) hipLaunchKernelGGL(k_badyn_linearize, dim3((nd + 255) / 256), dim3(256), 0, st, D);
-        n_lin++;
-        if (ncf) hipLaunchKernelGGL(k_ba_camfactors, dim3(ncf), dim3(64), 0, st, D, 1, D.cam, D.scal + 0);
-        }
-        if (it == 0) hipLaunchKernelGGL(k_ba_maxdiag, dim3(64), dim3(256), 0, st, D, n_ptl);
-        HIP_TRY(ctx, hipGetLastError());
-        if (allreduce) {     // camera diagonal blocks, bc, chi2 (sum) — then the max-diagonal (max) on its own
-            if (it == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); double md; HIP_TRY(ctx, hipMemcpy(&md, D.scal + 1, 8, hipMemcpyDeviceToHost)); HIP_TRY(ctx, hipMemsetAsync(D.scal + 1, 0, 8, st));
-                           if ((rc = AR(red, (size_t)n_pose * 36 + n6 + 1, 0))) return rc;
-                           // the stream-ordered RCCL path does not synchronise inside AR(): order the blocking copy below behind the memset and the sum all-reduce on `st`
-                           // (it == 0 only; ADVICE r2: without this the landmark part of the max-diagonal could be zeroed after it had been written)
-                           HIP_TRY(ctx, hipStreamSynchronize(st));
-                           HIP_TRY(ctx, hipMemcpy(D.scal + 1, &md, 8, hipMemcpyHostToDevice)); if ((rc = AR(D.scal + 1, 1, 1))) return rc;
-                           // the camera part of the max must see the SUMMED camera diagonals
-                           hipLaunchKernelGGL(k_ba_maxdiag, dim3(64), dim3(256), 0, st, D, 0); if ((rc = AR(D.scal + 1, 1, 1))) return rc; }
-            else if ((rc = AR(red, (size_t)n_pose * 36 + n6 + 1, 0))) return rc;
-        }
-        // chi2 at the linearisation point (scal[0]) is only needed once the first trial of this iteration has been evaluated, so after the
-        // first iteration (whose lambda needs the max diagonal) it is read together with the trial's scalars: one host sync per trial
-        bool have_chi = false; double currentChi = 0, iniChi = 0;
-        if (it == 0 || allreduce) {
-            if ((rc = read_scal())) return rc;
-            currentChi = iniChi = BS->h_scal[0]; have_chi = true;
-            if (it == 0) { lambda = 1e-5 * BS->h_scal[1]; ni = 2; nBad = 0; }
-            if (it == 0 && fl) { res->chi2_initial = res->chi2_final = currentChi; float ms = 0; if (hipEventElapsedTime(&ms, BS->ev0, BS->ev1) == hipSuccess) ms_lin += ms; }      // (the linearisation point of the first iteration IS the initial state; the timed launch carries the camera factors too)
-        }
-        double rho = 0; int qmax = 0;
-        do {
-            if (fl) {
-                // ---- S, F, C, B as four launches (bodies shared with k_ba_local_lm)
-                hipLaunchKernelGGL(k_ba_schur<0>, dim3(fl_grid), dim3(64 * schur0_waves), lds_schur, st, D, n_ptl, lambda, kcap, BS->d_parts, (const int*)nullptr, (const int*)nullptr, (const int2*)nullptr);
-                hipLaunchKernelGGL(k_ba_fold_local, dim3(std::min(64, (int)((loc_sz + 255) / 256))), dim3(256), 0, st, D, (const double*)BS->d_parts, fl_grid, lambda);
-                hipLaunchKernelGGL(k_ba_chol_small6, dim3(1), dim3(CH_NT), lds_chol6, st, D, 1, lambda);
-                const int n_bs = std::min((n_ptl + 31) / 32, 1024);
-                hipLaunchKernelGGL(k_ba_backsub_chi2_local, dim3(n_bs + (ncf + 3) / 4), dim3(256), 0, st, D, n_ptl, lambda, n_bs, qmax == 0 ? ((it & 1) ? red : red1) : (double*)nullptr, (int)red_len,
-                                   BS->d_ticket, BS->h_scal);
-                HIP_TRY(ctx, hipGetLastError());
-                HIP_TRY(ctx, hipStreamSynchronize(st));      // the launch's last workgroup has written the trial's scalars into h_scal
-            } else {
-            // ---- reduced system of this shard.  With an all-reduce every rank contributes Hcd/bc ALREADY summed,
-            // so only rank 0 adds the camera-camera part (+lambda) to S; the others start from zero.
-            const int add_cam = (!allreduce || p.rank == 0) ? 1 : 0;
-            const int inline_odo = (lds_path && !allreduce && D.bw < 0 && D.n_odo <= 64) ? 1 : 0;
-            hipLaunchKernelGGL(k_ba_init_S, dim3(std::min(2048, (int)((sz_sr + 255) / 256))), dim3(256), 0, st, D, lambda, add_cam, inline_odo);
-            if (!add_cam) HIP_TRY(ctx, hipMemsetAsync(D.r, 0, n6 * sizeof(double), st));
-            if (add_cam && D.n_odo && !inline_odo) hipLaunchKernelGGL(k_ba_add_odo, dim3((D.n_odo * 36 + 255) / 256), dim3(256), 0, st, D);
-            if (n_ptl) {
-                if (lds_path) {
-                    hipLaunchKernelGGL(k_ba_schur<0>, dim3(schur_grid), dim3(64 * schur0_waves), lds_schur, st, D, n_ptl, lambda, kcap, BS->d_parts, (const int*)nullptr, (const int*)nullptr, (const int2*)nullptr);
-                    hipLaunchKernelGGL(k_ba_fold_parts, dim3(std::min(256, (int)((loc_sz + 255) / 256)), std::min(8, schur_grid)), dim3(256), 0, st, D, BS->d_parts, schur_grid);
-                } else if (use_mfma_schur) {
-                    HIP_TRY(ctx, hipEventRecord(BS->ev2, st));
-                    hipLaunchKernelGGL(k_ba_schur_mfma, dim3(std::min(n_chunks, 1024)), dim3(SM_NT), SM_LDS_BYTES, st, D, n_ptl, lambda, (const int*)d_chunk_cmin, (const int*)d_lorder, (const int2*)d_lbc, chunk);
-                    HIP_TRY(ctx, hipEventRecord(BS->ev3, st)); n_schur_timed++;
-                }
-                else hipLaunchKernelGGL(k_ba_schur<2>, dim3(std::min(n_chunks, 1024)), dim3(64 * schur2_waves), lds_schur, st, D, n_ptl, lambda, kcap, (double*)nullptr, (const int*)d_chunk_cmin, (const int*)d_lorder, (const int2*)d_lbc);
-            }
-            if (n_long) hipLaunchKernelGGL(k_ba_schur_long, dim3(n_long), dim3(256), 0, st, D, lambda, (const int*)d_long);
-            if (nd) {
-                hipLaunchKernelGGL(k_badyn_factor, dim3((n_chain + 63) / 64), dim3(64), 0, st, D, lambda);
-                hipLaunchKernelGGL(k_badyn_schur, dim3(dyn_grid), dim3(64), dyn_lds, st, D, BS->d_scratch, lmax, dyn_lds ? 1 : 0);
-            }
+    } else {
+        if ((rc = chi2_at(D.cam, D.pt, 2, &res->chi2_initial))) return rc;
+        res->chi2_final = res->chi2_initial;
+        for (it = 0; it < p.max_iters; it++) {
+            // ---- linearise
+            const int ncf = D.n_odo + (D.prior_cam >= 0 ? 1 : 0);
+            HIP_TRY(ctx, hipMemsetAsync(red, 0, ((size_t)n_pose * 36 + n6 + 8) * sizeof(double), st));
+            HIP_TRY(ctx, hipEventRecord(BS->ev0, st));
+            if (no) hipLaunchKernelGGL(k_ba_linearize, dim3((no + LIN_THREADS * lin_E - 1) / (LIN_THREADS * lin_E)), dim3(LIN_THREADS), 0, st, D, lin_E);
+            HIP_TRY(ctx, hipEventRecord(BS->ev1, st));
+            if (nd) hipLaunchKernelGGL(k_badyn_linearize, dim3((nd + 255) / 256), dim3(256), 0, st, D);
+            n_lin++;
+            if (ncf) hipLaunchKernelGGL(k_ba_camfactors, dim3(ncf), dim3(64), 0, st, D, 1, D.cam, D.scal + 0);
+            if (it == 0) hipLaunchKernelGGL(k_ba_maxdiag, dim3(64), dim3(256), 0, st, D, n_ptl);
             HIP_TRY(ctx, hipGetLastError());
-            if ((rc = AR(Sr, sz_sr, 0))) return rc;
-            // ---- replicated reduced solve
-            if (!inline_odo) HIP_TRY(ctx, hipMemsetAsync(D.scal + 2, 0, 2 * sizeof(double), st));
-            const int fuse_update = (lds_path && n6 % 6 == 0 && n6 >= 12 && !allreduce && n_pose <= 64) ? 1 : 0;
-            if (lds_path && n6 % 6 == 0 && n6 >= 12) hipLaunchKernelGGL(k_ba_chol_small6, dim3(1), dim3(CH_NT), lds_chol6, st, D, fuse_update, lambda);
-            else if (lds_path) hipLaunchKernelGGL(k_ba_chol_small, dim3(1), dim3(1024), lds_chol, st, D);
-            else if (Bc.m) {                                   // block cyclic reduction: 2 launches per level, log2(nb) levels, then the levels back
-                const int m = Bc.m, nb = Bc.nb;
-                // scalar_piv: round 5's reduced solve around the same elimination kernel (k_bcr_update, one back-substitution launch per level), for comparison
-                static const bool scalar_piv = getenv("VIDO_BCR_SCALAR") != nullptr;
-                auto elim = [&](int n_blocks, int sft, const double* Lc, int mode) {
-                    if (m == 66) hipLaunchKernelGGL(k_bcr_elim<66>, dim3(n_blocks, mode ? 1 : 2), dim3(BcrGeom<66>::NT), BcrGeom<66>::LDS, st, Bc, sft, Lc, mode);
-                    else         hipLaunchKernelGGL(k_bcr_elim<96>, dim3(n_blocks, mode ? 1 : 2), dim3(BcrGeom<96>::NT), BcrGeom<96>::LDS, st, Bc, sft, Lc, mode);
-                };
-                hipLaunchKernelGGL(k_bcr_pack, dim3(nb), dim3(256), 0, st, Bc);
-                double *Lc = Bc.L0, *Ln = Bc.L1; int smax = 0;
-                for (int sft = 1; sft < nb; sft *= 2) {
-                    const int n_el = (nb - sft + 2 * sft - 1) / (2 * sft), n_sv = (nb + 2 * sft - 1) / (2 * sft);
-                    elim(n_el, sft, Lc, 0);
-                    if (scalar_piv) hipLaunchKernelGGL(k_bcr_update, dim3(n_sv, m / BCR_RB), dim3(128), 0, st, Bc, sft, (const double*)Lc, Ln);
-                    else            hipLaunchKernelGGL(k_bcr_update4, dim3(n_sv, m / BCR_RB), dim3(320), 0, st, Bc, sft, (const double*)Lc, Ln);
-                    std::swap(Lc, Ln); smax = sft;
+            if (allreduce) {     // camera diagonal blocks, bc, chi2 (sum) — then the max-diagonal (max) on its own
+                if (it == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); double md; HIP_TRY(ctx, hipMemcpy(&md, D.scal + 1, 8, hipMemcpyDeviceToHost)); HIP_TRY(ctx, hipMemsetAsync(D.scal + 1, 0, 8, st));
+                               if ((rc = AR(red, (size_t)n_pose * 36 + n6 + 1, 0))) return rc;
+                               // the stream-ordered RCCL path does not synchronise inside AR(): order the blocking copy below behind the memset and the sum all-reduce on `st`
+                               // (it == 0 only; ADVICE r2: without this the landmark part of the max-diagonal could be zeroed after it had been written)
+                               HIP_TRY(ctx, hipStreamSynchronize(st));
+                               HIP_TRY(ctx, hipMemcpy(D.scal + 1, &md, 8, hipMemcpyHostToDevice)); if ((rc = AR(D.scal + 1, 1, 1))) return rc;
+                               // the camera part of the max must see the SUMMED camera diagonals
+                               hipLaunchKernelGGL(k_ba_maxdiag, dim3(64), dim3(256), 0, st, D, 0); if ((rc = AR(D.scal + 1, 1, 1))) return rc; }
+                else if ((rc = AR(red, (size_t)n_pose * 36 + n6 + 1, 0))) return rc;
+            }
+            // chi2 at the linearisation point (scal[0]) is only needed once the first trial of this iteration has been evaluated, so after the
+            // first iteration (whose lambda needs the max diagonal) it is read together with the trial's scalars: one host sync per trial
+            bool have_chi = false; double currentChi = 0, iniChi = 0;
+            if (it == 0 || allreduce) {
+                if ((rc = read_scal())) return rc;
+                currentChi = iniChi = BS->h_scal[0]; have_chi = true;
+                if (it == 0) { lambda = 1e-5 * BS->h_scal[1]; ni = 2; nBad = 0; }
+            }
+            double rho = 0; int qmax = 0;
+            do {
+                // ---- reduced system of this shard.  With an all-reduce every rank contributes Hcd/bc ALREADY summed,
+                // so only rank 0 adds the camera-camera part (+lambda) to S; the others start from zero.
+                const int add_cam = (!allreduce || p.rank == 0) ? 1 : 0;
+                const int inline_odo = (lds_path && !allreduce && D.bw < 0 && D.n_odo <= 64) ? 1 : 0;
+                hipLaunchKernelGGL(k_ba_init_S, dim3(std::min(2048, (int)((sz_sr + 255) / 256))), dim3(256), 0, st, D, lambda, add_cam, inline_odo);
+                if (!add_cam) HIP_TRY(ctx, hipMemsetAsync(D.r, 0, n6 * sizeof(double), st));
+                if (add_cam && D.n_odo && !inline_odo) hipLaunchKernelGGL(k_ba_add_odo, dim3((D.n_odo * 36 + 255) / 256), dim3(256), 0, st, D);
+                if (n_ptl) {
+                    if (lds_path) {
+                        hipLaunchKernelGGL(k_ba_schur<0>, dim3(schur_grid), dim3(64 * schur0_waves), lds_schur, st, D, n_ptl, lambda, kcap, BS->d_parts, (const int*)nullptr, (const int*)nullptr, (const int2*)nullptr);
+                        hipLaunchKernelGGL(k_ba_fold_parts, dim3(std::min(256, (int)((loc_sz + 255) / 256)), std::min(8, schur_grid)), dim3(256), 0, st, D, BS->d_parts, schur_grid);
+                    } else if (use_mfma_schur) {
+                        HIP_TRY(ctx, hipEventRecord(BS->ev2, st));
+                        hipLaunchKernelGGL(k_ba_schur_mfma, dim3(std::min(n_chunks, 1024)), dim3(SM_NT), SM_LDS_BYTES, st, D, n_ptl, lambda, (const int*)d_chunk_cmin, (const int*)d_lorder, (const int2*)d_lbc, chunk);
+                        HIP_TRY(ctx, hipEventRecord(BS->ev3, st)); n_schur_timed++;
+                    }
+                    else hipLaunchKernelGGL(k_ba_schur<2>, dim3(std::min(n_chunks, 1024)), dim3(64 * schur2_waves), lds_schur, st, D, n_ptl, lambda, kcap, (double*)nullptr, (const int*)d_chunk_cmin, (const int*)d_lorder, (const int2*)d_lbc);
                 }
-                elim(1, 0, Lc, 1);
-                static const bool back_levels = getenv("VIDO_BCR_BACK_LEVELS") != nullptr;      // (round 5's launch per level, for comparison)
-                if (scalar_piv || back_levels) { for (int sft = smax; sft >= 1; sft /= 2) hipLaunchKernelGGL(k_bcr_back, dim3((nb - sft + 2 * sft - 1) / (2 * sft)), dim3(384), 0, st, Bc, sft); }
-                else {
+                if (n_long) hipLaunchKernelGGL(k_ba_schur_long, dim3(n_long), dim3(256), 0, st, D, lambda, (const int*)d_long);
+                if (nd) {
+                    hipLaunchKernelGGL(k_badyn_factor, dim3((n_chain + 63) / 64), dim3(64), 0, st, D, lambda);
+                    hipLaunchKernelGGL(k_badyn_schur, dim3(dyn_grid), dim3(64), dyn_lds, st, D, BS->d_scratch, lmax, dyn_lds ? 1 : 0);
+                }
+                HIP_TRY(ctx, hipGetLastError());
+                if ((rc = AR(Sr, sz_sr, 0))) return rc;
+                // ---- replicated reduced solve
+                if (!inline_odo) HIP_TRY(ctx, hipMemsetAsync(D.scal + 2, 0, 2 * sizeof(double), st));
+                const int fuse_update = (lds_path && n6 % 6 == 0 && n6 >= 12 && !allreduce && n_pose <= 64) ? 1 : 0;
+                if (lds_path && n6 % 6 == 0 && n6 >= 12) hipLaunchKernelGGL(k_ba_chol_small6, dim3(1), dim3(CH_NT), lds_chol6, st, D, fuse_update, lambda);
+                else if (lds_path) hipLaunchKernelGGL(k_ba_chol_small, dim3(1), dim3(1024), lds_chol, st, D);
+                else if (Bc.m) {                                   // block cyclic reduction: 2 launches per level, log2(nb) levels, then the levels back in one launch
+                    const int m = Bc.m, nb = Bc.nb;
+                    auto elim = [&](int n_blocks, int sft, const double* Lc, int mode) {
+                        if (m == 66) hipLaunchKernelGGL(k_bcr_elim<66>, dim3(n_blocks, mode ? 1 : 2), dim3(BcrGeom<66>::NT), BcrGeom<66>::LDS, st, Bc, sft, Lc, mode);
+                        else         hipLaunchKernelGGL(k_bcr_elim<96>, dim3(n_blocks, mode ? 1 : 2), dim3(BcrGeom<96>::NT), BcrGeom<96>::LDS, st, Bc, sft, Lc, mode);
+                    };
+                    hipLaunchKernelGGL(k_bcr_pack, dim3(nb), dim3(256), 0, st, Bc);
+                    double *Lc = Bc.L0, *Ln = Bc.L1;
+                    for (int sft = 1; sft < nb; sft *= 2) {
+                        const int n_el = (nb - sft + 2 * sft - 1) / (2 * sft), n_sv = (nb + 2 * sft - 1) / (2 * sft);
+                        elim(n_el, sft, Lc, 0);
+                        hipLaunchKernelGGL(k_bcr_update4, dim3(n_sv, m / BCR_RB), dim3(320), 0, st, Bc, sft, (const double*)Lc, Ln);
+                        std::swap(Lc, Ln);
+                    }
+                    elim(1, 0, Lc, 1);
                     if (++BS->bcr_epoch == 0) BS->bcr_epoch = 1;                  // (a tag of 0 is what the zeroed buffer holds)
                     hipLaunchKernelGGL(k_bcr_back_chain, dim3(BS->bcr_blocks_n), dim3(384), 0, st, Bc, (const int2*)BS->d_bcr_blocks, BS->d_bcr_xt, BS->bcr_epoch, BS->d_bcr_abort);
                 }
-            }
-            else if (D.bw >= 0 && band6_lds) hipLaunchKernelGGL(k_chol_band6, dim3(1), dim3(CH_NT), band6_lds, st, D, (D.bw - 5) / 6);
-            else if (D.bw >= 0 && band6s_lds && band6s_nb == 8) hipLaunchKernelGGL(k_chol_band6s<8>, dim3(1), dim3(CG_NT), band6s_lds, st, D, (D.bw - 5) / 6);
-            else if (D.bw >= 0 && band6s_lds) hipLaunchKernelGGL(k_chol_band6s<4>, dim3(1), dim3(CG_NT), band6s_lds, st, D, (D.bw - 5) / 6);
-            else if (D.bw >= 0) hipLaunchKernelGGL(k_chol_band, dim3(1), dim3(1024), (size_t)D.bw * (CB_NB + 1) * sizeof(double), st, D);
-            else { const double one = 1.0; HIP_TRY(ctx, hipMemcpyAsync(D.scal + 4, &one, 8, hipMemcpyHostToDevice, st)); if ((rc = chol_large(ctx, D.S, n6, D.x, D.scal + 4, chol_tmp, st))) return rc; }
-            // ---- trial state + its chi2
-            if (!fuse_update) hipLaunchKernelGGL(k_ba_update_cams, dim3((n_pose + 63) / 64), dim3(64), 0, st, D, (allreduce && p.rank != 0) ? 0.0 : lambda);
-            if (allreduce && p.rank != 0) HIP_TRY(ctx, hipMemsetAsync(D.scal + 3, 0, sizeof(double), st));      // camera part of computeScale counted once (rank 0)
-            if (n_ptl) hipLaunchKernelGGL(k_ba_backsub, dim3(std::min((n_ptl + 31) / 32, 1024)), dim3(256), 0, st, D, n_ptl, lambda);
-            if (no) hipLaunchKernelGGL(k_ba_chi2, dim3((no + 255) / 256), dim3(256), 0, st, D, D.cam_new, D.pt_new, D.scal + 2);
-            if (nd) { hipLaunchKernelGGL(k_badyn_backsub, dim3((n_chain + 63) / 64), dim3(64), 0, st, D, lambda);
-                      hipLaunchKernelGGL(k_badyn_chi2, dim3((nd + 255) / 256), dim3(256), 0, st, D, (const double*)D.cam_new, (const double*)D.dyn_new, D.scal + 2); }
-            if (ncf) hipLaunchKernelGGL(k_ba_camfactors, dim3(ncf), dim3(64), 0, st, D, 0, D.cam_new, D.scal + 2);
-            HIP_TRY(ctx, hipGetLastError());
-            if ((rc = AR(D.scal + 2, 2, 0))) return rc;
-            if ((rc = read_scal())) return rc;
-            }
-            if (!have_chi) { currentChi = iniChi = BS->h_scal[0]; have_chi = true; }
-            if (qmax == 0 && !fl) { float ms = 0; if (hipEventElapsedTime(&ms, BS->ev0, BS->ev1) == hipSuccess) ms_lin += ms; }
-            if (!fl && n_schur_timed > n_schur_read) { float ms = 0; if (hipEventElapsedTime(&ms, BS->ev2, BS->ev3) == hipSuccess) ms_schur += ms; n_schur_read = n_schur_timed; }
-            const bool ok2 = BS->h_scal[4] > 0.5;
-            const double tempChi = ok2 ? BS->h_scal[2] : DBL_MAX, scale = ok2 ? BS->h_scal[3] : 0.0;
-            rho = (currentChi - tempChi) / (scale + 1e-3);
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - pow((2 * rho - 1), 3); alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi;
-                std::swap(D.cam, D.cam_new); std::swap(D.pt, D.pt_new); std::swap(D.dyn, D.dyn_new);
-            } else { lambda *= ni; ni *= 2; }
-            qmax++; trials++;
-        } while (rho < 0 && qmax < 10);
-        bool terminate = (qmax == 10 || rho == 0);
-        if (!terminate) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; if (nBad >= 3) terminate = true; }
-        const double chiNow = currentChi;     // chi2 at the accepted state (the trial that produced it evaluated it)
-        if (chi2_check < chiNow && it > 0) terminate = true;
-        chi2_check = chiNow;
-        if (it == 0) lastChi = chiNow;
-        else { const double gain = (lastChi - chiNow) / chiNow; lastChi = chiNow; if (gain >= 0 && gain < p.gain_threshold) terminate = true; }
-        res->chi2_final = chiNow;
-        if (terminate) { it++; break; }
-    }
+                else if (D.bw >= 0 && band6_lds) hipLaunchKernelGGL(k_chol_band6, dim3(1), dim3(CH_NT), band6_lds, st, D, (D.bw - 5) / 6);
+                else if (D.bw >= 0 && band6s_lds && band6s_nb == 8) hipLaunchKernelGGL(k_chol_band6s<8>, dim3(1), dim3(CG_NT), band6s_lds, st, D, (D.bw - 5) / 6);
+                else if (D.bw >= 0 && band6s_lds) hipLaunchKernelGGL(k_chol_band6s<4>, dim3(1), dim3(CG_NT), band6s_lds, st, D, (D.bw - 5) / 6);
+                else if (D.bw >= 0) hipLaunchKernelGGL(k_chol_band, dim3(1), dim3(1024), (size_t)D.bw * (CB_NB + 1) * sizeof(double), st, D);
+                else { const double one = 1.0; HIP_TRY(ctx, hipMemcpyAsync(D.scal + 4, &one, 8, hipMemcpyHostToDevice, st)); if ((rc = chol_large(ctx, D.S, n6, D.x, D.scal + 4, chol_tmp, st))) return rc; }
+                // ---- trial state + its chi2
+                if (!fuse_update) hipLaunchKernelGGL(k_ba_update_cams, dim3((n_pose + 63) / 64), dim3(64), 0, st, D, (allreduce && p.rank != 0) ? 0.0 : lambda);
+                if (allreduce && p.rank != 0) HIP_TRY(ctx, hipMemsetAsync(D.scal + 3, 0, sizeof(double), st));      // camera part of computeScale counted once (rank 0)
+                if (n_ptl) hipLaunchKernelGGL(k_ba_backsub, dim3(std::min((n_ptl + 31) / 32, 1024)), dim3(256), 0, st, D, n_ptl, lambda);
+                if (no) hipLaunchKernelGGL(k_ba_chi2, dim3((no + 255) / 256), dim3(256), 0, st, D, D.cam_new, D.pt_new, D.scal + 2);
+                if (nd) { hipLaunchKernelGGL(k_badyn_backsub, dim3((n_chain + 63) / 64), dim3(64), 0, st, D, lambda);
+                          hipLaunchKernelGGL(k_badyn_chi2, dim3((nd + 255) / 256), dim3(256), 0, st, D, (const double*)D.cam_new, (const double*)D.dyn_new, D.scal + 2); }
+                if (ncf) hipLaunchKernelGGL(k_ba_camfactors, dim3(ncf), dim3(64), 0, st, D, 0, D.cam_new, D.scal + 2);
+                HIP_TRY(ctx, hipGetLastError());
+                if ((rc = AR(D.scal + 2, 2, 0))) return rc;
+                if ((rc = read_scal())) return rc;
+                if (!have_chi) { currentChi = iniChi = BS->h_scal[0]; have_chi = true; }
+                if (qmax == 0) { float ms = 0; if (hipEventElapsedTime(&ms, BS->ev0, BS->ev1) == hipSuccess) ms_lin += ms; }
+                if (n_schur_timed > n_schur_read) { float ms = 0; if (hipEventElapsedTime(&ms, BS->ev2, BS->ev3) == hipSuccess) ms_schur += ms; n_schur_read = n_schur_timed; }
+                const bool ok2 = BS->h_scal[4] > 0.5;
+                const double tempChi = ok2 ? BS->h_scal[2] : DBL_MAX, scale = ok2 ? BS->h_scal[3] : 0.0;
+                rho = (currentChi - tempChi) / (scale + 1e-3);
+                if (rho > 0 && std::isfinite(tempChi)) {
+                    double alpha = 1. - pow((2 * rho - 1), 3); alpha = std::min(alpha, 2. / 3.);
+                    lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi;
+                    std::swap(D.cam, D.cam_new); std::swap(D.pt, D.pt_new); std::swap(D.dyn, D.dyn_new);
+                } else { lambda *= ni; ni *= 2; }
+                qmax++; trials++;
+            } while (rho < 0 && qmax < 10);
+            bool terminate = (qmax == 10 || rho == 0);
+            if (!terminate) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; if (nBad >= 3) terminate = true; }
+            const double chiNow = currentChi;     // chi2 at the accepted state (the trial that produced it evaluated it)
+            if (chi2_check < chiNow && it > 0) terminate = true;
+            chi2_check = chiNow;
+            if (it == 0) lastChi = chiNow;
+            else { const double gain = (lastChi - chiNow) / chiNow; lastChi = chiNow; if (gain >= 0 && gain < p.gain_threshold) terminate = true; }
+            res->chi2_final = chiNow;
+            if (terminate) { it++; break; }
+        }
     }
     res->iterations = it; res->lm_trials = trials; res->lambda_final = lambda;
     res->ms_schur_kernel = n_schur_read ? ms_schur / n_schur_read : 0.0;
-    res->ms_linearize_kernel = n_lin ? ms_lin / n_lin : 0.0;      // (persistent solver: the linearisation phase up to its grid barrier, device clock)
+    res->ms_linearize_kernel = n_lin ? ms_lin / n_lin : 0.0;
     res->ms_solve_loop = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
-    if (!cam_final) HIP_TRY(ctx, hipMemcpyAsync(poses.data(), D.cam, (size_t)n_pose * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(poses.data(), D.cam, (size_t)n_pose * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (n_ptl && !DI) HIP_TRY(ctx, hipMemcpyAsync(prob->pt_xyz + 3 * (size_t)pt_lo, D.pt, (size_t)n_ptl * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (n_ptl && DI && D.pt != DI->pt) HIP_TRY(ctx, hipMemcpyAsync(DI->pt, D.pt, (size_t)n_ptl * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));      // the accepted state may sit in the other buffer
     if (nd) HIP_TRY(ctx, hipMemcpyAsync(d_xyz.data(), D.dyn, (size_t)nd * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
