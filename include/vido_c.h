@@ -173,7 +173,8 @@ int vido_update_mask(vido_ctx* ctx, int slot_last, int slot_cur, const int32_t* 
                      int32_t* recovered_out, int cap, int32_t* n_recovered);
 int vido_read_maps(vido_ctx* ctx, int slot, float* depth_out, float* flow_out, int32_t* mask_out);   /* any pointer may be NULL */
 /* mask / depth / flow of slot `slot` at ((int)x, (int)y) of n points (host xy in, host values out; points outside the image give 0): the only map data the host-side
- * renew stages need (vido_renew_*_sampled) — a few thousand points instead of three whole maps. */
+ * renew stages need (vido_renew_*_sampled) — a few thousand points instead of three whole maps.  Inside means 0 <= (int)x < width and 0 <= (int)y < height: x in (-1, 0)
+ * truncates to column 0.  Capacity: n <= 2 * max(2 * n_features + 256, ceil(width / 4) * ceil(height / 4)); a larger n is VIDO_E_INVALID.  n == 0 is a successful no-op. */
 int vido_gather_point_samples(vido_ctx* ctx, int slot, const float* xy, int n, int32_t* mask_out, float* depth_out, float* flow_out);
 /* Frame::UnprojectStereoStat/Object, addnoise=0 (Frame.cc:706-771): Tcw row-major 4x4 f32. */
 int vido_unproject_world(vido_ctx* ctx, const float* keys_xy, const float* z, int n, const vido_track_params* p,

@@ -29,22 +29,37 @@ struct TrackState {
 };
 
 // ---- kernels -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_depth_prescale(float* __restrict__ d, size_t n4, int mode, float factor, float bf, float scale)
+__device__ __forceinline__ float prescale_one(float x, int mode, float factor, float bf, float scale)
 {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        float4 v = ((float4*)d)[i];
+    if (x < 0) return 0.f;
+    if (mode == 0) return x / factor;
+    if (mode == 1) return bf / (x / factor);
+    return scale * bf / (x / factor);
+}
+// d[0, n): `head` scalars up to the first 16-byte boundary, n4 float4 from there, `tail` scalars after them (head = tail = 0 for an aligned map of 4 k pixels:
+// the float4 body alone).  A frame of 1242 x 375 pixels is not a multiple of 4 long, and slot 1 of such a size starts 8 bytes off a boundary.
+__global__ __launch_bounds__(256) void k_depth_prescale(float* __restrict__ d, int head, size_t n4, int tail, int mode, float factor, float bf, float scale)
+{
+    const size_t t0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    float4* body = (float4*)(d + head);
+    for (size_t i = t0; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        float4 v = body[i];
         float* e = (float*)&v;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float x = e[k];
-            if (x < 0) x = 0;
-            else if (mode == 0) x = x / factor;
-            else if (mode == 1) x = bf / (x / factor);
-            else x = scale * bf / (x / factor);
-            e[k] = x;
-        }
-        ((float4*)d)[i] = v;
+        for (int k = 0; k < 4; k++) e[k] = prescale_one(e[k], mode, factor, bf, scale);
+        body[i] = v;
     }
+    if (t0 < (size_t)(head + tail)) {
+        const size_t e = t0 < (size_t)head ? t0 : head + 4 * n4 + (t0 - head);
+        d[e] = prescale_one(d[e], mode, factor, bf, scale);
+    }
+}
+static void launch_depth_prescale(hipStream_t st, float* d, size_t n, const vido_track_params* p)
+{
+    const int head = (int)std::min<size_t>(n, ((16 - ((uintptr_t)d & 15)) & 15) / 4);
+    const size_t n4 = (n - head) / 4; const int tail = (int)(n - head - 4 * n4);
+    const int grid = (int)std::min<size_t>(std::max<size_t>((n4 + 255) / 256, 1), 2048);
+    hipLaunchKernelGGL(k_depth_prescale, dim3(grid), dim3(256), 0, st, d, head, n4, tail, p->dataset, p->depth_map_factor, p->bf, p->kaist_scale);
 }
 
 // exclusive position of a flagged element among all flagged elements of the workgroup so far, in thread
@@ -296,7 +311,6 @@ int vido_frame_upload(vido_ctx* ctx, int slot0, int n_frames, float* depth, cons
     if (slot0 < 0 || n_frames < 1 || slot0 + n_frames > T->B || !depth || !flow || !mask)
         return vido_set_error(ctx, VIDO_E_INVALID, "frame_upload: slots [%d,%d) outside [0,%d) or null map", slot0, slot0 + n_frames, T->B);
     const size_t px = (size_t)T->W * T->H, n = px * n_frames;
-    if ((n & 3) != 0) return vido_set_error(ctx, VIDO_E_INVALID, "frame_upload: width*height must be a multiple of 4");      // every argument is validated before any state changes
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if (on_device == 2) {
@@ -305,7 +319,7 @@ int vido_frame_upload(vido_ctx* ctx, int slot0, int n_frames, float* depth, cons
         // tracker's first synchronisation ~1.1 ms (profiles/r6/tracker_zero_copy_maps.txt).  The caller keeps a frame's maps alive and untouched while the slot is in use (the
         // tracker reads the current and the previous frame).
         for (int f = 0; f < n_frames; f++) { T->sdepth[slot0 + f] = depth + (size_t)f * px; T->sflow[slot0 + f] = (float*)flow + (size_t)f * px * 2; T->smask[slot0 + f] = (int32_t*)mask + (size_t)f * px; }
-        hipLaunchKernelGGL(k_depth_prescale, dim3((int)std::min<size_t>((n / 4 + 255) / 256, 2048)), dim3(256), 0, st, depth, n / 4, p->dataset, p->depth_map_factor, p->bf, p->kaist_scale);
+        launch_depth_prescale(st, depth, n, p);
         HIP_TRY(ctx, hipGetLastError());
         return VIDO_OK;
     }
@@ -315,8 +329,7 @@ int vido_frame_upload(vido_ctx* ctx, int slot0, int n_frames, float* depth, cons
     HIP_TRY(ctx, hipMemcpyAsync(T->d_mask + slot0 * px, mask, n * 4, in_kind(on_device), st));
     // the slot tables are repointed only once the copies have been accepted (a failed enqueue leaves the previous frame's slots referenced)
     for (int f = 0; f < n_frames; f++) { T->sdepth[slot0 + f] = T->d_depth + (slot0 + f) * px; T->sflow[slot0 + f] = T->d_flow + (slot0 + f) * px * 2; T->smask[slot0 + f] = T->d_mask + (slot0 + f) * px; }
-    const int grid = (int)std::min<size_t>((n / 4 + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_depth_prescale, dim3(grid), dim3(256), 0, st, dd, n / 4, p->dataset, p->depth_map_factor, p->bf, p->kaist_scale);
+    launch_depth_prescale(st, dd, n, p);
     // the reference mutates the caller's depth buffer in place (Tracking.cc:299-322): hand the scaled map back
     HIP_TRY(ctx, hipMemcpyAsync(depth, dd, n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     if (!on_device) HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -427,7 +440,6 @@ int vido_frontend_batch(vido_ctx* ctx, const uint8_t* imgs, int imgs_on_device, 
         return vido_set_error(ctx, VIDO_E_INVALID, "frontend_batch: slots [%d,%d) outside [0,%d) or null map", slot0, slot0 + n_frames, T->B);
     hipStream_t st = ctx->stream, st2 = ctx->stream2;
     const size_t px = (size_t)T->W * T->H, n = px * n_frames;
-    if ((n & 3) != 0) return vido_set_error(ctx, VIDO_E_INVALID, "frontend_batch: width*height must be a multiple of 4");
     const int step = p->dense_step > 0 ? p->dense_step : 4;
     const int lattice = ((T->W + step - 1) / step) * ((T->H + step - 1) / step);
     if (lattice > T->max_obj) return vido_set_error(ctx, VIDO_E_INVALID, "frontend_batch: dense_step %d gives %d probes > %d", step, lattice, T->max_obj);
@@ -458,7 +470,7 @@ int vido_frontend_batch(vido_ctx* ctx, const uint8_t* imgs, int imgs_on_device, 
         HIP_TRY(ctx, hipMemcpyAsync(T->d_flow + slot0 * px * 2, flow, n * 8, hipMemcpyDeviceToDevice, st2));
         HIP_TRY(ctx, hipMemcpyAsync(T->d_mask + slot0 * px, mask, n * 4, hipMemcpyDeviceToDevice, st2));
     }
-    hipLaunchKernelGGL(k_depth_prescale, dim3((int)std::min<size_t>((n / 4 + 255) / 256, 2048)), dim3(256), 0, st2, dd, n / 4, p->dataset, p->depth_map_factor, p->bf, p->kaist_scale);
+    launch_depth_prescale(st2, dd, n, p);
     if (host_maps) HIP_TRY(ctx, hipMemcpyAsync(hm_depth, dd, n * 4, hipMemcpyDeviceToHost, st2));                       // in-place semantics of Tracking.cc:299-322 ...
     else if (!alias) HIP_TRY(ctx, hipMemcpyAsync(depth, dd, n * 4, hipMemcpyDeviceToDevice, st2));
     hipLaunchKernelGGL(k_dense_sample, dim3(n_frames), dim3(1024), 0, st2, (const float*)dd, fl, mk,

@@ -322,6 +322,13 @@ class FrameFeatures:
         self.ctx._check(self.ctx.lib.vido_gather_object_depth_label(self.ctx.h, slot, _ptr(keys), len(keys), C.c_float(self.p.th_depth_obj), _ptr(d), _ptr(l)))
         return d, l
 
+    def gather_point_samples(self, slot, xy):
+        """mask / depth / flow of `slot` at ((int)x, (int)y) of every point (vido_gather_point_samples) -> (mask (n,) i32, depth (n,) f32, flow (n,2) f32)."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2); n = len(xy)
+        m = np.empty(n, np.int32); d = np.empty(n, np.float32); f = np.empty((n, 2), np.float32)
+        self.ctx._check(self.ctx.lib.vido_gather_point_samples(self.ctx.h, slot, _ptr(xy), n, _ptr(m), _ptr(d), _ptr(f)))
+        return m, d, f
+
     def update_mask(self, slot_last, slot_cur, last_label, last_corr):
         last_label = np.ascontiguousarray(last_label, np.int32); last_corr = np.ascontiguousarray(last_corr, np.float32).reshape(-1, 2)
         rec = np.zeros(64, np.int32); nrec = C.c_int32()
