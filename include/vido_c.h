@@ -172,6 +172,25 @@ int vido_gather_object_depth_label(vido_ctx* ctx, int slot, const float* keys_xy
 int vido_update_mask(vido_ctx* ctx, int slot_last, int slot_cur, const int32_t* last_label, const float* last_corr_xy, int n,
                      int32_t* recovered_out, int cap, int32_t* n_recovered);
 int vido_read_maps(vido_ctx* ctx, int slot, float* depth_out, float* flow_out, int32_t* mask_out);   /* any pointer may be NULL */
+/* Forward warp of a whole label image through dense flow (no reference counterpart; vido_update_mask above repaints ONE lost label with the reference's quirks and is
+ * independent of this).  DEVICE pointers: mask_prev i32 [H,W], flow f32 [H,W,2] (dx, dy) from mask_prev's frame into the target frame, depth_prev f32 [H,W] or NULL,
+ * out i32 [H,W] (another buffer than mask_prev; EVERY pixel is written), stats_out 3 x i32 or NULL.
+ *   sources   a pixel (x, y) with L = mask_prev > 0, both flow components finite with |f| < 32768 and, with a depth map, depth finite and > 0; its target is
+ *             (x + rint(dx), y + rint(dy)), round to nearest with ties to even, kept iff inside the image.  Labels <= 0 never scatter.
+ *   collisions a target takes the minimum of (depth bits as u32) << 32 | (u32)L over the sources that land on it (upper half 0 without depth): the nearer source, on equal
+ *             depth the smaller label.
+ *   holes     an unhit target takes L iff at least 5 of its 8 neighbours (outside the image = not hit) were hit and resolved to L; one pass, no cascade; else 0.
+ *   stats_out sources kept, target pixels hit, pixels filled.
+ * The result is independent of execution order (bit-exact against tests/refimpl/mask_propagate_np.py).  Two memsets and two launches on the context's adopted stream
+ * (vido_set_stream), no host synchronisation; the context's key plane (8 bytes per pixel of its width x height) is allocated by the FIRST call, so one call comes before a
+ * stream capture.  One plane per context: calls on different streams must not overlap.  out == mask_prev, a null map, H or W outside [1, 4095] or
+ * H * W > width * height of the context: VIDO_E_INVALID. */
+int vido_mask_propagate(vido_ctx* ctx, const int32_t* mask_prev, const float* flow, const float* depth_prev /* NULL ok */, int H, int W, int32_t* out,
+                        int32_t* stats_out /* NULL ok */);
+/* The same on the tracker's slot maps, on the context's own stream: mask, flow and (pre-scaled, metric) depth of slot_last -> the mask of slot_cur, whose previous content
+ * is overwritten (after vido_frame_upload of slot_cur; with on_device = 2 that is the CALLER's adopted mask buffer).  stats_out: HOST, 3 x i32; NULL: nothing is waited
+ * for.  slot_last == slot_cur, a slot outside [0, vido_track_slots()) or two slots adopting one mask buffer: VIDO_E_INVALID. */
+int vido_frame_propagate_mask(vido_ctx* ctx, int slot_last, int slot_cur, int32_t* stats_out /* HOST, NULL ok */);
 /* mask / depth / flow of slot `slot` at ((int)x, (int)y) of n points (host xy in, host values out; points outside the image give 0): the only map data the host-side
  * renew stages need (vido_renew_*_sampled) — a few thousand points instead of three whole maps.  Inside means 0 <= (int)x < width and 0 <= (int)y < height: x in (-1, 0)
  * truncates to column 0.  Capacity: n <= 2 * max(2 * n_features + 256, ceil(width / 4) * ceil(height / 4)); a larger n is VIDO_E_INVALID.  n == 0 is a successful no-op. */
@@ -575,7 +594,8 @@ int vido_tracklets_incremental(int n_rows, const int32_t* row_off, const int32_t
  * One live system per process, like the reference (Frame's statics, Frame.cc:26-30). */
 typedef struct vido_system vido_system;
 typedef struct vido_system_stats {          /* of the last vido_system_track_rgbd call */
-    int32_t frame_id, n_keypoints, n_static, n_static_inliers, n_objects, n_object_points, ba_window, pad;
+    int32_t frame_id, n_keypoints, n_static, n_static_inliers, n_objects, n_object_points, ba_window;
+    int32_t mask_propagated;                 /* Mask.PropagateMissing: 1 — 1 when this frame came without a mask and took the previous frame's, propagated (vido_frame_propagate_mask); else 0 */
     float ms_total;                          /* TrackRGBD wall time */
     float ms_update_mask, ms_frame;          /* Tracking::UpdateMask; Frame::Frame (cvtColor + ORB + lists) + hand-over gathers */
     float ms_cam_pose, ms_obj_tracking, ms_obj_motion, ms_renew;   /* the reference's all_timing[1..4] (Tracking.cc:1120-1324); obj_motion = sum over objects */
@@ -590,7 +610,10 @@ const char* vido_system_last_error(const vido_system* sys);      /* NULL sys: er
 /* im: u8 interleaved, `channels` 1 (gray), 3 or 4 (BGR[A], or RGB[A] when the settings say Camera.RGB: 1), tight rows; depth f32 (raw sensor
  * units; REWRITTEN IN PLACE with the pre-scaled depth like the reference does to the caller's Mat, Tracking.cc:299-322); flow f32 x2; mask i32;
  * all width*height, host memory, alive until the NEXT call returns (the reference keeps shallow references, Tracking.cc:343-345, 777-780).
- * n_image: StopFrame = n_image - 1.  Tcw_out: row-major 4x4 world->camera pose of this frame (identity for the first). */
+ * n_image: StopFrame = n_image - 1.  Tcw_out: row-major 4x4 world->camera pose of this frame (identity for the first).
+ * Settings key Mask.PropagateMissing: 1 (default 0): `mask` (here, and mask_dev of the device form) may be NULL on every frame but the first of a sequence; the frame's mask is
+ * then the previous frame's, warped through the previous frame's flow with the nearer pre-scaled depth winning a collision (vido_frame_propagate_mask), before any list is
+ * built from it; vido_system_stats.mask_propagated reports it.  With the key at 0 a NULL mask is VIDO_E_INVALID as before. */
 int         vido_system_track_rgbd(vido_system* sys, const uint8_t* im, int channels, int width, int height, float* depth, const float* flow,
                                    const int32_t* mask, double timestamp, int n_image, float Tcw_out[16]);
 /* The same with the image (u8, 1 / 3 / 4 interleaved channels) and the three maps already RESIDENT ON THE DEVICE (plain device pointers; depth is rescaled in place on the

@@ -188,6 +188,12 @@ public:
     void VerifyStaticDescriptors();
     void GetVerifyStats(int* n_checked, int* n_rejected) const { if (n_checked) *n_checked = nVerifyChecked; if (n_rejected) *n_rejected = nVerifyRejected; }
     bool bVerifyDescriptor = false; int nVerifyMaxHamming = 64, nVerifyChecked = 0, nVerifyRejected = 0;
+    /* extension (Mask.PropagateMissing: 1): a GrabImageRGBD call with an EMPTY mask, or a GrabImageRGBDDevice call with a null mask pointer, takes the frame's mask from
+       the previous frame: its mask warped through its flow, the nearer (pre-scaled) depth winning a collision (vido_frame_propagate_mask), before any list is built.
+       The first frame of a sequence needs a mask.  nMaskPropagated: 1 when the last frame's mask was propagated.  With the key at 0 (default) nothing changes. */
+    void PropagateMissingMask();
+    bool bPropagateMissingMask = false; int nMaskPropagated = 0;
+    cv::Mat mPropMaskHost; int32_t* mPropMaskDev[2] = {nullptr, nullptr}; size_t mPropMaskPx = 0;      /* the placeholder mask that goes into the slot (host form) / the slots' own mask buffers (device form) */
 
     enum eTrackingState { NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2 };
     enum eDataState { OMD = 1, KITTI = 2, KAIST = 3 };

@@ -17,6 +17,7 @@
 #include <iostream>
 #include <sstream>
 #include <stdexcept>
+#include <hip/hip_runtime_api.h>      // the device mask buffers of Mask.PropagateMissing (Tracking::GrabImageRGBDDevice)
 
 namespace VIDO_SLAM {
 
@@ -883,17 +884,34 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
     if (kv.count("RansacSeed")) ransac_seed = (unsigned)num(kv, "RansacSeed");
     bVerifyDescriptor = num(kv, "Verify.Descriptor", 0) != 0; nVerifyMaxHamming = (int)num(kv, "Verify.MaxHamming", 70);      // (70: profiles/r8/descriptor_verify.txt)
     g_verify_desc = bVerifyDescriptor;
+    bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
     all_timing.assign(5, 0.f);
 }
-Tracking::~Tracking() { delete mpORBextractorLeft; }
+Tracking::~Tracking() { delete mpORBextractorLeft; for (int i = 0; i < 2; i++) if (mPropMaskDev[i]) (void)hipFree(mPropMaskDev[i]); }
+
+// Mask.PropagateMissing: 1 and a frame handed over without a mask (no reference counterpart: the reference segments every frame).  The frame's maps are in slot_cur_ with
+// a placeholder mask; the previous slot's mask is warped through the previous slot's flow into it (vido_frame_propagate_mask: the nearer pre-scaled depth wins a collision)
+// before UpdateMask and before any list is built from the mask.
+void Tracking::PropagateMissingMask()
+{
+    check(vido_frame_propagate_mask(g_ctx, 1 - slot_cur_, slot_cur_, nullptr), "frame_propagate_mask");
+    nMaskPropagated = 1;
+}
 
 
-cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat&,
+cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Mat& imFlow, const cv::Mat& maskSEM_in, const cv::Mat&,
                                 const std::vector<std::vector<float> >&, const double& timestamp, cv::Mat&, const int& nImage)
 {
     const auto t_grab = std::chrono::steady_clock::now();
     StopFrame = nImage - 1; ms_wait_inputs = 0;
     if (mState == NO_IMAGES_YET) f_id = 0;
+    nMaskPropagated = 0;
+    const bool propagate = bPropagateMissingMask && maskSEM_in.empty();
+    if (propagate) {
+        if (mState == NO_IMAGES_YET) throw std::runtime_error("GrabImageRGBD: Mask.PropagateMissing: the first frame of a sequence needs a mask");
+        if (mPropMaskHost.rows != imD.rows || mPropMaskHost.cols != imD.cols) mPropMaskHost = cv::Mat::zeros(imD.rows, imD.cols, CV_32SC1);      // the placeholder that goes up with the maps
+    }
+    const cv::Mat& maskSEM = propagate ? mPropMaskHost : maskSEM_in;
     if (imD.type() != CV_32FC1 || imFlow.type() != CV_32FC2 || maskSEM.type() != CV_32SC1 || !imD.isContinuous() || !imFlow.isContinuous() || !maskSEM.isContinuous())
         throw std::runtime_error("GrabImageRGBD: depth CV_32F, flow CV_32FC2, mask CV_32SC1 (continuous) expected");
     vido_ctx* c = mpORBextractorLeft->context(imRGB.cols, imRGB.rows);
@@ -904,6 +922,7 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
     slot_cur_ = (mState == NO_IMAGES_YET) ? 0 : 1 - slot_cur_; g_slot = slot_cur_;
     // depth pre-scale in place on the caller's buffer (:299-322) + maps resident in the slot
     check(vido_frame_upload(c, slot_cur_, 1, imD.ptr<float>(), imFlow.ptr<float>(), maskSEM.ptr<int32_t>(), 0, &g_tp), "frame_upload");
+    if (propagate) PropagateMissingMask();
     if (imRGB.channels() == 1) mImGray = imRGB;
     else {                                                     // :327-340 cvtColor: done on the device by the extractor's ingest, which fills mImGray
         if (imRGB.type() != CV_8UC3 && imRGB.type() != CV_8UC4) throw std::runtime_error("GrabImageRGBD: image must be CV_8UC1 / CV_8UC3 / CV_8UC4");
@@ -926,8 +945,11 @@ cv::Mat Tracking::GrabImageRGBDDevice(const void* im_dev, int channels, int widt
     const auto t_grab = std::chrono::steady_clock::now();
     StopFrame = nImage - 1;
     if (mState == NO_IMAGES_YET) f_id = 0;
-    if (!im_dev || !depth_dev || !flow_dev || !mask_dev || width < 1 || height < 1 || (channels != 1 && channels != 3 && channels != 4))
+    nMaskPropagated = 0;
+    const bool propagate = bPropagateMissingMask && !mask_dev;
+    if (!im_dev || !depth_dev || !flow_dev || (!mask_dev && !propagate) || width < 1 || height < 1 || (channels != 1 && channels != 3 && channels != 4))
         throw std::runtime_error("GrabImageRGBDDevice: device image (1 / 3 / 4 channels), depth, flow and mask pointers expected");
+    if (propagate && mState == NO_IMAGES_YET) throw std::runtime_error("GrabImageRGBDDevice: Mask.PropagateMissing: the first frame of a sequence needs a mask");
     vido_ctx* c = mpORBextractorLeft->context(width, height);
     g_ctx = c;
     ms_wait_inputs = 0;
@@ -941,7 +963,21 @@ cv::Mat Tracking::GrabImageRGBDDevice(const void* im_dev, int channels, int widt
     g_tp.dataset = mTestData == OMD ? 0 : (mTestData == KITTI ? 1 : 2); g_tp.depth_map_factor = mDepthMapFactor; g_tp.bf = mbf; g_tp.kaist_scale = mScale;
     g_tp.th_depth_bg = mThDepth; g_tp.th_depth_obj = mThDepthObj; g_tp.dense_step = 4; g_tp.fx = mK.at<float>(0, 0); g_tp.fy = mK.at<float>(1, 1); g_tp.cx = mK.at<float>(0, 2); g_tp.cy = mK.at<float>(1, 2);
     slot_cur_ = (mState == NO_IMAGES_YET) ? 0 : 1 - slot_cur_; g_slot = slot_cur_;
+    if (bPropagateMissingMask && mState == NO_IMAGES_YET) {      // the first frame of a sequence (no slot is in use): the tracker's two mask buffers for frames that come without one — allocated here, never in a later frame
+        const size_t px = (size_t)width * height;
+        if (px != mPropMaskPx) {
+            for (int i = 0; i < 2; i++) { if (mPropMaskDev[i]) (void)hipFree(mPropMaskDev[i]); mPropMaskDev[i] = nullptr; }
+            mPropMaskPx = 0;
+            for (int i = 0; i < 2; i++) if (hipMalloc((void**)&mPropMaskDev[i], px * 4) != hipSuccess) throw std::runtime_error("GrabImageRGBDDevice: no device memory for the propagated masks");
+            mPropMaskPx = px;
+        }
+    }
+    if (propagate) {      // the slot's mask for this frame: the buffer of this slot's parity (a zero-copy slot adopts it; the previous slot may still refer to the other)
+        if ((size_t)width * height != mPropMaskPx) throw std::runtime_error("GrabImageRGBDDevice: Mask.PropagateMissing: the frame size changed inside a sequence");
+        mask_dev = mPropMaskDev[slot_cur_ & 1];
+    }
     check(vido_frame_upload(c, slot_cur_, 1, depth_dev, flow_dev, (const int32_t*)mask_dev, detail::g_zero_copy_maps ? 2 : 1, &g_tp), "frame_upload");      // device -> slot (no PCIe), or the slot adopts the buffers; depth pre-scale in place
+    if (propagate) PropagateMissingMask();
     mImGray = cv::Mat(height, width, CV_8UC1);                  // size carrier: the pixels stay on the device (ORBextractor::SetDeviceSource)
     mpORBextractorLeft->SetDeviceSource(im_dev, channels, mbRGB);
     mDepthMap = cv::Mat(); mFlowMap = cv::Mat(); mSegMap = cv::Mat();
@@ -1389,7 +1425,7 @@ cv::Mat System::TrackRGBD(const cv::Mat& im, cv::Mat& depthmap, const cv::Mat& f
     // the realtime demo hands over the services' wire types (run_vido.cc:57-110: depth MONO16, mask MONO8); the offline one converts first
     // (run_vido_slam.cc:96-118).  Both are accepted: 16U depth -> 32F (converted copy becomes the caller's Mat, like convertTo in place), 8U mask -> 32S.
     if (depthmap.type() == CV_16UC1) { cv::Mat d32; depthmap.convertTo(d32, CV_32F); depthmap = d32; }
-    if (masksem.type() == CV_8UC1) { cv::Mat m32; masksem.convertTo(m32, CV_32SC1); return mpTracker->GrabImageRGBD(im, depthmap, flowmap, m32, Tgt, vObjPose_gt, ts, imTraj, nImage); }
+    if (!masksem.empty() && masksem.type() == CV_8UC1) { cv::Mat m32; masksem.convertTo(m32, CV_32SC1); return mpTracker->GrabImageRGBD(im, depthmap, flowmap, m32, Tgt, vObjPose_gt, ts, imTraj, nImage); }
     return mpTracker->GrabImageRGBD(im, depthmap, flowmap, masksem, Tgt, vObjPose_gt, ts, imTraj, nImage);
 }
 cv::Mat System::TrackRGBDDevice(const void* im_dev, int channels, int width, int height, float* depth_dev, const float* flow_dev, const int* mask_dev, void* ready_event,
@@ -1461,12 +1497,13 @@ int vido_system_track_rgbd(vido_system* s, const uint8_t* im, int channels, int 
                            double timestamp, int n_image, float Tcw_out[16])
 {
     if (!s || !s->inited) return VIDO_E_INVALID;
-    if (!im || !depth || !flow || !mask || !Tcw_out || width <= 0 || height <= 0 || (channels != 1 && channels != 3 && channels != 4)) { s->err = "vido_system_track_rgbd: bad argument"; return VIDO_E_INVALID; }
+    const bool no_mask_ok = s->sys.GetTracker() && s->sys.GetTracker()->bPropagateMissingMask;      // Mask.PropagateMissing: 1 — a NULL mask means "propagate the last frame's"
+    if (!im || !depth || !flow || (!mask && !no_mask_ok) || !Tcw_out || width <= 0 || height <= 0 || (channels != 1 && channels != 3 && channels != 4)) { s->err = "vido_system_track_rgbd: bad argument"; return VIDO_E_INVALID; }
     try {
         s->im = cv::Mat(height, width, CV_MAKETYPE(CV_8U, channels), (void*)im);
         s->depth = cv::Mat(height, width, CV_32FC1, (void*)depth);
         s->flow = cv::Mat(height, width, CV_32FC2, (void*)flow);
-        s->mask = cv::Mat(height, width, CV_32SC1, (void*)mask);
+        s->mask = mask ? cv::Mat(height, width, CV_32SC1, (void*)mask) : cv::Mat();
         if (s->traj.empty()) s->traj = cv::Mat::zeros(600, 800, CV_8UC3);
         const cv::Mat id = cv::Mat::eye(4, 4, CV_32F); const std::vector<std::vector<float> > gt;
         cv::Mat T = s->sys.TrackRGBD(s->im, s->depth, s->flow, s->mask, id, gt, timestamp, s->traj, n_image);
@@ -1482,7 +1519,8 @@ int vido_system_track_rgbd_device(vido_system* s, const void* im_dev, int channe
                                   void* ready_event, double timestamp, int n_image, float Tcw_out[16])
 {
     if (!s || !s->inited) return VIDO_E_INVALID;
-    if (!im_dev || !depth_dev || !flow_dev || !mask_dev || !Tcw_out || width <= 0 || height <= 0 || (channels != 1 && channels != 3 && channels != 4)) { s->err = "vido_system_track_rgbd_device: bad argument"; return VIDO_E_INVALID; }
+    const bool no_mask_ok = s->sys.GetTracker() && s->sys.GetTracker()->bPropagateMissingMask;
+    if (!im_dev || !depth_dev || !flow_dev || (!mask_dev && !no_mask_ok) || !Tcw_out || width <= 0 || height <= 0 || (channels != 1 && channels != 3 && channels != 4)) { s->err = "vido_system_track_rgbd_device: bad argument"; return VIDO_E_INVALID; }
     try {
         cv::Mat T = s->sys.TrackRGBDDevice(im_dev, channels, width, height, depth_dev, flow_dev, (const int*)mask_dev, ready_event, timestamp, n_image);
         for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw_out[r * 4 + c] = T.at<float>(r, c);
@@ -1504,6 +1542,7 @@ int vido_system_get_stats(const vido_system* s, vido_system_stats* o)
     o->frame_id = T->f_id - 1; o->n_keypoints = F->N; o->n_static = (int)F->mvStatKeysTmp.size(); o->n_static_inliers = 0;
     for (int id : F->nStaInlierID) if (id >= 0) o->n_static_inliers++;
     int no = 0; for (size_t i = 0; i < F->bObjStat.size(); i++) if (F->bObjStat[i]) no++;
+    o->mask_propagated = T->nMaskPropagated;
     o->n_objects = no; o->n_object_points = (int)F->mvObjKeys.size(); o->ba_window = std::min(std::max(T->f_id - 1, 0), T->nWINDOW_SIZE);
     o->ms_total = T->ms_total; o->ms_update_mask = T->ms_update_mask; o->ms_frame = T->ms_frame; o->ms_wait_inputs = T->ms_wait_inputs; o->ms_orb = VIDO_SLAM::detail::LastFrameStageMs(0); o->ms_lists = VIDO_SLAM::detail::LastFrameStageMs(1);
     if (T->all_timing.size() >= 5) { o->ms_cam_pose = T->all_timing[1]; o->ms_obj_tracking = T->all_timing[2]; o->ms_renew = T->all_timing[4]; }

@@ -268,6 +268,15 @@ void track_state_destroy(vido_ctx* ctx)
     delete T; ctx->trk = nullptr;
 }
 
+// maskprop.hip: where the maps of one slot live and the frame size (the slot tables are private to this file)
+int track_slot_maps(vido_ctx* ctx, int slot, float** depth, float** flow, int32_t** mask, int* W, int* H)
+{
+    TrackState* T; int rc = track_state(ctx, &T); if (rc) return rc;
+    if (slot < 0 || slot >= T->B) return VIDO_E_INVALID;
+    *depth = T->sdepth[slot]; *flow = T->sflow[slot]; *mask = T->smask[slot]; *W = T->W; *H = T->H;
+    return VIDO_OK;
+}
+
 static inline hipMemcpyKind in_kind(int on_device) { return on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
 
 __global__ __launch_bounds__(256) void k_diag_lds(int* out) { __shared__ int pad[8192]; pad[threadIdx.x] = threadIdx.x; __syncthreads(); if (threadIdx.x == 0 && blockIdx.x == 0) out[1] = pad[255]; }

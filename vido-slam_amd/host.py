@@ -63,6 +63,8 @@ def load_library():
     lib.vido_hamming_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -208,6 +210,14 @@ class Context:
         idx = np.empty(len(a), np.int32); dist = np.empty(len(a), np.int32)
         self._check(self.lib.vido_hamming_match(self.h, _ptr(a), len(a), _ptr(b), len(b), _ptr(idx), _ptr(dist), 0))
         return idx, dist
+
+    # ---- label-image propagation ---------------------------------------------------------------------
+    def frame_propagate_mask(self, slot_last, slot_cur):
+        """vido_frame_propagate_mask: warp slot_last's mask through slot_last's flow (nearer pre-scaled depth wins a collision) into slot_cur's mask, on the context's own
+        stream.  Returns (sources kept, pixels hit, pixels filled); the rule is include/vido_c.h's, the numpy statement tests/refimpl/mask_propagate_np.py."""
+        st = (C.c_int32 * 3)()
+        self._check(self.lib.vido_frame_propagate_mask(self.h, int(slot_last), int(slot_cur), st))
+        return int(st[0]), int(st[1]), int(st[2])
 
     def hamming_match_device(self, a_ptr, na, b_ptr, nb, idx_ptr, dist_ptr):
         self._check(self.lib.vido_hamming_match(self.h, C.c_void_p(a_ptr), na, C.c_void_p(b_ptr), nb, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), 1))

@@ -638,6 +638,46 @@ class HipOps:
                                                            C.c_void_p(out.data_ptr())))
         return out
 
+    def mask_propagate(self, mask, flow, depth=None, out=None, stats=None):
+        """vido_mask_propagate on device tensors: mask int32 [H,W] of frame k-1, flow float32 [H,W,2] (dx, dy) from k-1 into k, depth float32 [H,W] of k-1 or None ->
+        the label image of frame k, int32 [H,W] (`out`, or a new tensor).  A pixel with label > 0 and a usable flow vector (and depth, when given) lands on
+        (x + rint(dx), y + rint(dy)); several on one pixel: the nearer, then the smaller label; an unhit pixel with 5 of 8 neighbours of one label takes it.  stats: an
+        int32 tensor of >= 3 elements that receives (sources kept, pixels hit, pixels filled), or None.  Enqueued on torch's current stream, nothing is waited for; the
+        first call of a context allocates, so it comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out aliasing mask raise."""
+        from ..host import VidoError
+        def bad(why):
+            raise VidoError(-1, "mask_propagate: " + why)
+        for name, t, dt in (("mask", mask, torch.int32), ("flow", flow, torch.float32), ("depth", depth, torch.float32), ("out", out, torch.int32), ("stats", stats, torch.int32)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != mask.device:
+                bad("%s is on another device than mask" % name)
+        if mask.dim() != 2:
+            bad("mask must be [H, W]")
+        H, W = int(mask.shape[0]), int(mask.shape[1])
+        if tuple(flow.shape) != (H, W, 2):
+            bad("flow must be [%d, %d, 2], got %s" % (H, W, tuple(flow.shape)))
+        if depth is not None and tuple(depth.shape) != (H, W):
+            bad("depth must be [%d, %d], got %s" % (H, W, tuple(depth.shape)))
+        if out is None:
+            out = torch.empty((H, W), device=mask.device, dtype=torch.int32)
+        elif tuple(out.shape) != (H, W):
+            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
+        if out.data_ptr() < mask.data_ptr() + 4 * H * W and mask.data_ptr() < out.data_ptr() + 4 * H * W:
+            bad("out aliases mask")
+        if stats is not None and stats.numel() < 3:
+            bad("stats needs 3 elements")
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_mask_propagate(self.ctx.h, C.c_void_p(mask.data_ptr()), C.c_void_p(flow.data_ptr()), C.c_void_p(depth.data_ptr()) if depth is not None else None,
+                                                         H, W, C.c_void_p(out.data_ptr()), C.c_void_p(stats.data_ptr()) if stats is not None else None))
+        return out
+
     def mask_instance_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, id_base=None, areas=False):
         """Masker + instance image (vido_mask_instance_image): mask_label_image's inputs in priority order (highest first) -> [H,W] u8 = id_base + 1 + index of the first
         detection with a nonzero label whose pasted mask covers the pixel, 0 elsewhere.  id_base: None (0), an int, or a DEVICE int32 tensor of one element that the kernel

@@ -131,13 +131,26 @@ class NetNodes:
     on_range: what a frame whose split-fp16 launches left fp16's range (|x| >= 65504, an infinity or a NaN: its outputs are not valid) gets.  "raise" (default): the caller's
     check_conv1x1_range raises, the sequence stops.  "recompute": infer() ends each frame with a latch of both contexts' range flags into that frame's own words
     (vido_range_latch, in stream order), and the caller recomputes a tripped frame's networks in fp32's range (recompute(); infer_checked() does it all; EndToEnd does it
-    before the frame is tracked).  Only LiteFlowNet (its context) and the detector launch split-fp16 kernels; MonoDepth2 shares the detector's context and launches none."""
+    before the frame is tracked).  Only LiteFlowNet (its context) and the detector launch split-fp16 kernels; MonoDepth2 shares the detector's context and launches none.
+
+    detect_every = N (an integer >= 1; default 1: the detector runs on every frame and nothing below applies): the detector runs on calls 0, N, 2N, ...; on the calls in
+    between it is not launched, and the frame's mask is the previous frame's mask warped through this call's flow (HipOps.mask_propagate, csrc/maskprop.hip) on the
+    detector's stream behind the flow's event, into one of two buffers the nodes own (a graph's static output is overwritten by the next replay).  No depth is passed: the
+    networks' depth is a normalised disparity, not metric, so where two objects land on one pixel the SMALLER LABEL wins, not the nearer object.  A propagated frame returns
+    the last detector frame's labels and reports no detections (so no overflow); label_mode="instance": the id base advances per detector RUN, a propagated frame keeps its
+    source's ids and base (self.id_base).  carried_mask is the image the next propagated frame starts from — a device tensor an external detector or a test may write;
+    detector_runs / propagated_frames count, last_propagated tells which the last call was.  Not with on_range="recompute": a flow recomputed after the fact would
+    invalidate the masks already propagated through it (open)."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
-                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class"):
+                 mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
+                 detect_every=1):
+        self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
+        self.detect_every = int(detect_every)
+        self.detector_runs = self.propagated_frames = 0; self.last_propagated = False; self._calls = 0
         if on_range not in self.RANGE_MODES:
             raise ValueError("on_range: one of %s, not %r" % (self.RANGE_MODES, on_range))
         if label_mode not in _nets.maskrcnn.LABEL_MODES:
@@ -170,6 +183,10 @@ class NetNodes:
         self._id_bases = torch.tensor(self.ID_BASES, dtype=torch.int32, device=dev) if label_mode == "instance" else None
         self._id_word = torch.zeros((1,), dtype=torch.int32, device=dev) if label_mode == "instance" else None
         self.id_base = 0; self._frames = 0
+        # detect_every > 1: the two mask buffers propagated frames alternate between (carried_mask: the one the next propagated frame reads), the labels and label count of
+        # the last detector frame, and a zero for the detection count of propagated frames.  The first mask_propagate call allocates the context's key plane: here, not in a frame
+        self._carry = None; self._carry_i = 0; self._last_labels = None; self._last_nlab = None
+        self._set_detect_every(self.detect_every)
         # random-init detector: un-saturate the class scores so that the reference's detections_per_img cap binds (see nets/weights.py); a synthetic textured frame
         self.score_scale = 1.0
         if calibrate_scores:
@@ -256,11 +273,20 @@ class NetNodes:
         with torch.cuda.stream(ss[1]):
             depth = (self.g_depth or self._depth_fn)(cur_bgr)
             e1 = torch.cuda.Event(); e1.record()
+        det_frame = self.detect_every == 1 or self._calls % self.detect_every == 0
+        self._calls += 1
         with torch.cuda.stream(ss[2]):
-            if self.label_mode == "instance":                           # this frame's id base, into the word the graph reads: a device-to-device copy in stream order, nothing waits
-                self.id_base = self.ID_BASES[self._frames & 1]; self._frames += 1
+            if self.label_mode == "instance" and det_frame:             # this frame's id base, into the word the graph reads: a device-to-device copy in stream order, nothing waits
+                self.id_base = self.ID_BASES[self._frames & 1]; self._frames += 1      # (per detector run: a propagated frame keeps its source's ids)
                 self._id_word.copy_(self._base_word(self.id_base), non_blocking=True)
-            if getattr(self, "skip_detector", False):                   # the literal "flow+depth+track+local-BA" chain of BASELINE's metric text (bench.py extra.e2e_without_detector)
+            if not det_frame:                                           # the previous frame's mask through this call's flow; the detector is not launched
+                ss[2].wait_event(e0)
+                dst = self._carry[self._carry_i ^ 1]
+                self.ops.mask_propagate(self._carry[self._carry_i], flow, out=dst)
+                self._carry_i ^= 1
+                mask, labels = dst, self._last_labels
+                self.last_counts = None if self._last_nlab is None else (self._last_nlab, self._zero_count)
+            elif getattr(self, "skip_detector", False):                   # the literal "flow+depth+track+local-BA" chain of BASELINE's metric text (bench.py extra.e2e_without_detector)
                 if getattr(self, "_no_det", None) is None:
                     z = torch.zeros((), dtype=torch.int32, device=self.dev)
                     self._no_det = (torch.zeros((self.h, self.w), dtype=torch.int32, device=self.dev), torch.zeros((1,), dtype=torch.int64, device=self.dev), z, z.clone())
@@ -272,6 +298,14 @@ class NetNodes:
             else:                                                       # dynamic head: its data-dependent tail synchronises the host while the other two networks run
                 mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk, **self._label_args())
                 mask = mask_u8.to(torch.int32); self.last_counts = None
+            self.last_propagated = not det_frame
+            if det_frame:
+                self.detector_runs += 1
+                if self._carry is not None:                             # the image the next propagated frame starts from (the graph's static output does not outlive the next replay)
+                    self._carry[self._carry_i].copy_(mask, non_blocking=True)
+                    self._last_labels = labels; self._last_nlab = None if self.last_counts is None else self.last_counts[0]
+            else:
+                self.propagated_frames += 1
             e2 = torch.cuda.Event(); e2.record()
         for s, e in zip(ss, (e0, e1, e2)):                          # the outputs are valid in stream order on the CALLER's stream, whatever queue produced them
             if s is not cur:
@@ -285,6 +319,31 @@ class NetNodes:
             range_words.zero_()
             self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
+
+    @staticmethod
+    def _check_detect_every(detect_every, on_range):
+        import numbers as _numbers
+        if isinstance(detect_every, bool) or not isinstance(detect_every, _numbers.Integral) or detect_every < 1:
+            raise ValueError("detect_every: an integer >= 1, not %r" % (detect_every,))
+        if detect_every > 1 and on_range == "recompute":
+            raise ValueError("detect_every = %d with on_range='recompute': a flow recomputed after the fact would invalidate the masks already propagated through it" % detect_every)
+
+    def _set_detect_every(self, detect_every):
+        """The constructor's set-up of the cadence (also tools/prof_detect_every.py, between sequences, so that one set of networks serves every cadence): a new sequence starts —
+        the next infer() is a detector frame under id base 0.  Not part of the interface; never while frames are in flight."""
+        self._check_detect_every(detect_every, self.on_range)
+        self.detect_every = int(detect_every); self._calls = 0; self._frames = 0; self.id_base = 0; self.last_propagated = False
+        if self.detect_every > 1 and self._carry is None:
+            self._carry = [torch.zeros((self.h, self.w), dtype=torch.int32, device=self.dev) for _ in range(2)]
+            self._zero_count = torch.zeros((), dtype=torch.int32, device=self.dev)
+            self.ops.mask_propagate(self._carry[0], torch.zeros((self.h, self.w, 2), dtype=torch.float32, device=self.dev), out=self._carry[1])
+        elif self.detect_every == 1:
+            self._carry = None; self._carry_i = 0; self._last_labels = None; self._last_nlab = None
+
+    @property
+    def carried_mask(self):
+        """detect_every > 1: the int32 HxW device tensor the next propagated frame is warped from (the last frame's mask); writable in place.  None with detect_every = 1."""
+        return None if self._carry is None else self._carry[self._carry_i]
 
     def _base_word(self, id_base):
         """The constant device word that holds `id_base` (one of ID_BASES)."""
@@ -407,7 +466,7 @@ class EndToEnd:
         h, w = nodes.h, nodes.w; dev = nodes.dev
         pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()
         self.host = [dict(bgr=pin((h, w, 3), torch.uint8), flow=pin((h, w, 2), torch.float32), depth=pin((h, w), torch.float32), mask=pin((h, w), torch.int32),
-                          counts=pin((2,), torch.int32), range=pin((2,), torch.int32), id_base=0) for _ in range(self.RING)]
+                          counts=pin((2,), torch.int32), range=pin((2,), torch.int32), id_base=0, propagated=False) for _ in range(self.RING)]
         self.range_frames = []                # frames whose networks were recomputed in fp32's range (nodes.on_range == "recompute")
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         self.dev = [dict(bgr=mk((h, w, 3), torch.uint8), flow=mk((h, w, 2), torch.float32), depth=mk((h, w), torch.float32), mask=mk((h, w), torch.int32),
@@ -443,7 +502,8 @@ class EndToEnd:
                         safe = self._recompute_if_tripped(k, slot)
                     if self.nodes.g_det is not None:                     # the static head's overflow flag (rare): needs the frame's counts, i.e. a host wait for this one event
                         ev.synchronize()
-                        self._redo_if_overflowed(slot, range_safe=safe)
+                        if not hb["propagated"]:                         # (a propagated frame ran no detector: nothing to redo)
+                            self._redo_if_overflowed(slot, range_safe=safe)
                         if self.nodes.on_range == "raise":
                             self.nodes.check_conv1x1_range()             # (the frame's networks are complete: ev)
                     t1 = _time.perf_counter()
@@ -534,6 +594,7 @@ class EndToEnd:
         with self.net_lock:
             flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None)
             hb["id_base"] = self.nodes.id_base                           # (label_mode="instance": a later recomputation of this frame paints under the same ids)
+            hb["propagated"] = bool(getattr(self.nodes, "last_propagated", False))      # (detect_every > 1: the mask was warped from the frame before, no detector ran)
         # graph outputs are static buffers that the next replay overwrites: park them in this slot's device buffers (three device-to-device copies of 4.8 MB in stream order)
         if self.nodes.streams is not None:
             for e in evs:

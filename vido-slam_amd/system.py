@@ -19,7 +19,7 @@ from .host import load_library, VidoError, VIDO_OK
 class SystemStats(C.Structure):
     """vido_system_stats."""
     _fields_ = [("frame_id", C.c_int32), ("n_keypoints", C.c_int32), ("n_static", C.c_int32), ("n_static_inliers", C.c_int32),
-                ("n_objects", C.c_int32), ("n_object_points", C.c_int32), ("ba_window", C.c_int32), ("pad", C.c_int32),
+                ("n_objects", C.c_int32), ("n_object_points", C.c_int32), ("ba_window", C.c_int32), ("mask_propagated", C.c_int32),
                 ("ms_total", C.c_float), ("ms_update_mask", C.c_float), ("ms_frame", C.c_float), ("ms_cam_pose", C.c_float),
                 ("ms_obj_tracking", C.c_float), ("ms_obj_motion", C.c_float), ("ms_renew", C.c_float), ("ms_local_ba", C.c_float), ("ms_wait_inputs", C.c_float), ("ms_orb", C.c_float), ("ms_lists", C.c_float)]
 
@@ -69,7 +69,9 @@ class System:
     def TrackRGBD(self, im, depthmap, flowmap, masksem, mTcw_gt=None, vObjPose_gt=None, timestamp=0.0, imTraj=None, nImage=10000):
         """im u8 (H,W) / (H,W,3|4); depthmap f32 (H,W) — REWRITTEN IN PLACE with the pre-scaled depth (Tracking.cc:299-322);
         flowmap f32 (H,W,2); masksem i32 (H,W).  Returns Tcw (4,4) f32.  mTcw_gt / vObjPose_gt / imTraj: accepted and ignored
-        (ground-truth metrics and the trajectory canvas are viewer / evaluation features)."""
+        (ground-truth metrics and the trajectory canvas are viewer / evaluation features).
+        masksem=None (settings key Mask.PropagateMissing: 1, not on the first frame): the frame takes the previous frame's mask, propagated through the previous frame's
+        flow (stats()["mask_propagated"] == 1); with the key at 0 the library refuses the call."""
         if self.h is None:
             raise VidoError(-1, "System.TrackRGBD before Init")
         if im.dtype != np.uint8 or not im.flags.c_contiguous:
@@ -78,13 +80,13 @@ class System:
             raise VidoError(-1, "TrackRGBD: depthmap must be a writable C-contiguous float32 array (it is rescaled in place)")
         if flowmap.dtype != np.float32 or not flowmap.flags.c_contiguous:
             flowmap = np.ascontiguousarray(flowmap, np.float32)
-        if masksem.dtype != np.int32 or not masksem.flags.c_contiguous:
+        if masksem is not None and (masksem.dtype != np.int32 or not masksem.flags.c_contiguous):
             masksem = np.ascontiguousarray(masksem, np.int32)
         h, w = im.shape[:2]
         cn = 1 if im.ndim == 2 else im.shape[2]
         T = np.empty((4, 4), np.float32)
         keep = (im, depthmap, flowmap, masksem)
-        rc = self.lib.vido_system_track_rgbd(self.h, im.ctypes.data, cn, w, h, depthmap.ctypes.data, flowmap.ctypes.data, masksem.ctypes.data,
+        rc = self.lib.vido_system_track_rgbd(self.h, im.ctypes.data, cn, w, h, depthmap.ctypes.data, flowmap.ctypes.data, masksem.ctypes.data if masksem is not None else None,
                                              float(timestamp), int(nImage), T.ctypes.data)
         self._keep = keep
         if rc != VIDO_OK:
@@ -108,12 +110,13 @@ class System:
     def TrackRGBDDevice(self, im_dev, channels, width, height, depth_dev, flow_dev, mask_dev, ready_event=None, timestamp=0.0, nImage=10000):
         """System::TrackRGBDDevice (extension, SURVEY.md 8f row 4): the same call on DEVICE-resident buffers given as raw pointers (e.g. tensor.data_ptr()): u8 image with
         `channels` interleaved channels, depth f32 (rescaled in place on the device), flow f32 x2, mask i32 of a width x height frame; ready_event: raw hipEvent_t
-        (torch.cuda.Event.cuda_event) recorded by the producer of the buffers, or None.  The caller keeps the buffers alive for two frames.  Returns Tcw (4,4) f32."""
+        (torch.cuda.Event.cuda_event) recorded by the producer of the buffers, or None.  The caller keeps the buffers alive for two frames.  Returns Tcw (4,4) f32.
+        mask_dev = 0 / None with Mask.PropagateMissing: 1: as masksem=None of TrackRGBD."""
         if self.h is None:
             raise VidoError(-1, "System.TrackRGBDDevice before Init")
         T = np.empty((4, 4), np.float32)
         rc = self.lib.vido_system_track_rgbd_device(self.h, C.c_void_p(int(im_dev)), int(channels), int(width), int(height), C.c_void_p(int(depth_dev)), C.c_void_p(int(flow_dev)),
-                                                    C.c_void_p(int(mask_dev)), C.c_void_p(int(ready_event)) if ready_event else None, float(timestamp), int(nImage), T.ctypes.data)
+                                                    C.c_void_p(int(mask_dev)) if mask_dev else None, C.c_void_p(int(ready_event)) if ready_event else None, float(timestamp), int(nImage), T.ctypes.data)
         if rc != VIDO_OK:
             raise VidoError(rc, self.lib.vido_system_last_error(self.h).decode())
         return T
