@@ -191,6 +191,27 @@ int vido_mask_propagate(vido_ctx* ctx, const int32_t* mask_prev, const float* fl
  * is overwritten (after vido_frame_upload of slot_cur; with on_device = 2 that is the CALLER's adopted mask buffer).  stats_out: HOST, 3 x i32; NULL: nothing is waited
  * for.  slot_last == slot_cur, a slot outside [0, vido_track_slots()) or two slots adopting one mask buffer: VIDO_E_INVALID. */
 int vido_frame_propagate_mask(vido_ctx* ctx, int slot_last, int slot_cur, int32_t* stats_out /* HOST, NULL ok */);
+/* Instance ids that persist across frames: association of the previous handed-over label image, already warped into this frame (vido_mask_propagate's output), with the
+ * detector's new instance image by pixel overlap (no reference counterpart).  ALL pointers are DEVICE pointers: prev i32 [H,W] or NULL (all zero: first frame), cur i32
+ * [H,W] with value 1 + slot (id base 0), classes i64 [n] or NULL (every slot live; values are kept as their low 32 bits), state i32 [768] read and written, out i32 [H,W]
+ * (may be cur; EVERY pixel is written), lut_out i32 [256] or NULL, stats_out i32 [4] or NULL.
+ *   state      [0] the cursor; [256 + id] the class of id, nonzero exactly when the id is live or held; [512 + id] the calls the id has been lost.  All zeros: new sequence.
+ *   0 clean    p = prev where 1 <= prev <= 254, else 0;  c = cur where 1 <= cur <= n and classes[cur - 1] != 0, else 0.
+ *   1 count    C[p][c] over all pixels; Ap[p] = sum_c C[p][c] (p >= 1), Ac[c] = sum_p C[p][c] (c >= 1), zero column and row included.
+ *   2 match    c with Ac[c] > 0 takes the p >= 1 with 2 C[p][c] > Ap[p] + Ac[c] - C[p][c] (IoU strictly above 1/2).  Such a p is unique and no two c share one (more than
+ *              half of a pixel set can go to one partner only): no order, no tie rule.  The threshold is fixed.
+ *   3 fresh    each unmatched c with Ac[c] > 0, ascending: the next id after the cursor, cyclic over 1..254, with Ap[id] == 0 and not handed out in this call; cursor = id.
+ *              The cursor only moves forward: a retired id comes back only after 254 others were handed out.  No id free: the instance gets 0 and counts as left out.
+ *   4 lut      LUT[c] = the matched p, the fresh id, or 0; an assigned id: class[id] = classes[c - 1] (1 without classes), lost[id] = 0.
+ *   5 lost     each p with Ap[p] > 0 that nothing matched: lost[p] += 1; lost[p] <= hold: KEEP[p] = p (held in place), else KEEP[p] = 0 and class[p] = lost[p] = 0.  Ids
+ *              with Ap == 0 not assigned in this call are cleared the same way (no re-identification once an id is retired).
+ *   6 image    out = LUT[c] where that is nonzero, else KEEP[p].  stats_out: matched, fresh, lost (held or retired), left out.
+ * Bit-exact against tests/refimpl/mask_associate_np.py whatever the execution order (integer counts).  One memset and three launches on the context's adopted stream
+ * (vido_set_stream), no host synchronisation; the context's 256 KB count table is allocated by the FIRST call, so one call comes before a stream capture.  One table per
+ * context: calls on different streams must not overlap.  cur, state or out NULL, out == prev, H or W outside [1, 4095], H * W > width * height of the context, hold < 0 or
+ * n < 0: VIDO_E_INVALID; n > 127: VIDO_E_CAPACITY. */
+int vido_mask_associate(vido_ctx* ctx, const int32_t* prev /* NULL ok */, const int32_t* cur, int H, int W, const int64_t* classes /* NULL ok */, int n, int hold,
+                        int32_t* state /* DEVICE i32[768], in/out */, int32_t* out, int32_t* lut_out /* i32[256], NULL ok */, int32_t* stats_out /* i32[4], NULL ok */);
 /* mask / depth / flow of slot `slot` at ((int)x, (int)y) of n points (host xy in, host values out; points outside the image give 0): the only map data the host-side
  * renew stages need (vido_renew_*_sampled) — a few thousand points instead of three whole maps.  Inside means 0 <= (int)x < width and 0 <= (int)y < height: x in (-1, 0)
  * truncates to column 0.  Capacity: n <= 2 * max(2 * n_features + 256, ceil(width / 4) * ceil(height / 4)); a larger n is VIDO_E_INVALID.  n == 0 is a successful no-op. */

@@ -50,6 +50,7 @@ struct vido_ctx {
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
     struct MaskPropState* mprop = nullptr;   // maskprop.hip: key plane + counters of vido_mask_propagate / vido_frame_propagate_mask
+    struct MaskAssocState* massoc = nullptr; // maskassoc.hip: count table + lookups of vido_mask_associate
     struct BaWin* bawin = nullptr;     // bawin.hip: the device-resident local-BA window
     void* detpost_buf = nullptr; size_t detpost_cap = 0; unsigned long long detpost_sig = 0;   // detpost.hip: scratch of the RPN selection (keys, histograms, state)
     void* rccl_comm = nullptr;         // ncclComm_t of vido_rccl_init (rccl.cpp): the sharded BA's all-reduce on this context's stream
@@ -86,6 +87,7 @@ OrbView orb_view(vido_ctx* ctx);
 void track_state_destroy(vido_ctx* ctx);
 int track_slot_maps(vido_ctx* ctx, int slot, float** depth, float** flow, int32_t** mask, int* W, int* H);      // (track.hip) for maskprop.hip
 void maskprop_state_destroy(vido_ctx* ctx);
+void maskassoc_state_destroy(vido_ctx* ctx);
 void ham_state_destroy(vido_ctx* ctx);
 void pose_state_destroy(vido_ctx* ctx);
 void ba_state_destroy(vido_ctx* ctx);

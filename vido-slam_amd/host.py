@@ -65,6 +65,7 @@ def load_library():
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.vido_mask_associate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

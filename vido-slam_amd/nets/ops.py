@@ -678,6 +678,59 @@ class HipOps:
                                                          H, W, C.c_void_p(out.data_ptr()), C.c_void_p(stats.data_ptr()) if stats is not None else None))
         return out
 
+    def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
+        """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
+        (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),
+        classes int64 [>= n] or None (every slot live), n (default: classes' length, 127 without classes), hold >= 0 -> the label image under ids that persist, int32 [H,W]
+        (`out`, which may be `cur`, or a new tensor).  An instance takes over the previous id it overlaps with IoU > 1/2, any other gets the next free id of 1..254 behind the
+        state's cursor; a previous id nothing matched is held in place for `hold` calls, then retired.  lut: int32 [>= 256] that receives slot + 1 -> id; stats: int32
+        [>= 4] that receives (matched, fresh, lost, left out).  Enqueued on torch's current stream, nothing is waited for; the first call of a context allocates, so it
+        comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out overlapping prev (or cur, other than being cur) raise."""
+        from ..host import VidoError
+        def bad(why):
+            raise VidoError(-1, "mask_associate: " + why)
+        for name, t, dt in (("cur", cur, torch.int32), ("prev", prev, torch.int32), ("state", state, torch.int32), ("classes", classes, torch.int64), ("out", out, torch.int32),
+                            ("lut", lut, torch.int32), ("stats", stats, torch.int32)):
+            if t is None:
+                if name in ("cur", "state"):
+                    bad("%s is required" % name)
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != cur.device:
+                bad("%s is on another device than cur" % name)
+        if cur.dim() != 2:
+            bad("cur must be [H, W]")
+        H, W = int(cur.shape[0]), int(cur.shape[1])
+        if prev is not None and tuple(prev.shape) != (H, W):
+            bad("prev must be [%d, %d], got %s" % (H, W, tuple(prev.shape)))
+        if state.numel() != 768:
+            bad("state needs 768 elements")
+        if n is None:
+            n = int(classes.numel()) if classes is not None else 127
+        n = int(n)
+        if classes is not None and classes.numel() < n:
+            bad("classes holds %d elements, n = %d" % (classes.numel(), n))
+        if out is None:
+            out = torch.empty((H, W), device=cur.device, dtype=torch.int32)
+        elif tuple(out.shape) != (H, W):
+            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
+        for name, t in (("prev", prev), ("cur", cur)):
+            if t is not None and out.data_ptr() < t.data_ptr() + 4 * H * W and t.data_ptr() < out.data_ptr() + 4 * H * W and not (name == "cur" and out.data_ptr() == t.data_ptr()):
+                bad("out aliases %s" % name)
+        if lut is not None and lut.numel() < 256:
+            bad("lut needs 256 elements")
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_mask_associate(self.ctx.h, ptr(prev), ptr(cur), H, W, ptr(classes), n, int(hold), ptr(state), ptr(out), ptr(lut), ptr(stats)))
+        return out
+
     def mask_instance_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, id_base=None, areas=False):
         """Masker + instance image (vido_mask_instance_image): mask_label_image's inputs in priority order (highest first) -> [H,W] u8 = id_base + 1 + index of the first
         detection with a nonzero label whose pasted mask covers the pixel, 0 elsewhere.  id_base: None (0), an int, or a DEVICE int32 tensor of one element that the kernel

@@ -118,6 +118,60 @@ def _offer_miopen_db():
 _offer_miopen_db()
 
 
+class InstanceIds:
+    """Instance ids that persist across frames (csrc/maskassoc.hip): what an external detector, NetNodes(stable_ids=True) or a test drives.  Owns two
+    int32 HxW label images (the one handed over last and the one being written), the association state (int32 [768]: cursor, class and lost count per id) and the
+    counters of the last detected() call (stats, int32 [4]: matched, fresh, lost, left out).  Everything is enqueued on torch's current stream; nothing waits for the device.
+
+    detected(inst_mask, classes, flow=None): inst_mask int32 HxW at id base 0 (value 1 + slot), classes int64 [n <= 127] (0 = unused slot), flow float32 HxWx2 from the
+    previous frame into this one, or None on the first frame of a sequence.  The image handed over last is warped through the flow (HipOps.mask_propagate) and associated
+    with inst_mask (HipOps.mask_associate): an instance takes over the id it overlaps with IoU > 1/2, any other gets a fresh id; an id the detector misses stays in the
+    image at its flow-predicted place for `hold` detector frames.  propagated(flow): a frame without a detector run, the last image warped through the flow.  Both return
+    the frame's mask, one of the two images: valid until the next call.  mask is the image handed over last (writable: the next call starts from it),
+    classes_by_id an int64 [255] device tensor refreshed in stream order by detected(): [id - 1] is the class of id, 0 when the id is neither live nor held."""
+
+    def __init__(self, ops, h, w, hold=0):
+        import numbers as _numbers
+        if isinstance(hold, bool) or not isinstance(hold, _numbers.Integral) or hold < 0:
+            raise ValueError("hold: an integer >= 0, not %r" % (hold,))
+        self.ops, self.h, self.w, self.hold = ops, int(h), int(w), int(hold)
+        dev = torch.device("cuda", ops.ctx.cfg.device)
+        self._img = [torch.zeros((self.h, self.w), dtype=torch.int32, device=dev) for _ in range(2)]
+        self._i = 0
+        self.state = torch.zeros((768,), dtype=torch.int32, device=dev)
+        self.stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+        self.classes_by_id = torch.zeros((255,), dtype=torch.int64, device=dev)
+        # the first call of either op allocates in its context (key plane, count table): here, so that a frame — or a capture — never does
+        ops.mask_propagate(self._img[0], torch.zeros((self.h, self.w, 2), dtype=torch.float32, device=dev), out=self._img[1])
+        ops.mask_associate(None, self._img[1], self.state, n=0, hold=self.hold, out=self._img[0], stats=self.stats)
+
+    @property
+    def mask(self):
+        return self._img[self._i]
+
+    def reset(self):
+        """A new sequence: no ids live, the cursor back at the start, both images empty."""
+        self.state.zero_(); self.stats.zero_(); self.classes_by_id.zero_(); self._i = 0      # (mask is the tensor it was after construction)
+        for m in self._img:
+            m.zero_()
+
+    def detected(self, inst_mask, classes, flow=None):
+        last, other = self._img[self._i], self._img[self._i ^ 1]
+        if flow is None:
+            out = self.ops.mask_associate(None, inst_mask, self.state, classes=classes, hold=self.hold, out=other, stats=self.stats)
+            self._i ^= 1
+        else:
+            self.ops.mask_propagate(last, flow, out=other)
+            out = self.ops.mask_associate(other, inst_mask, self.state, classes=classes, hold=self.hold, out=last, stats=self.stats)
+        self.classes_by_id.copy_(self.state[257:512], non_blocking=True)
+        return out
+
+    def propagated(self, flow):
+        out = self.ops.mask_propagate(self._img[self._i], flow, out=self._img[self._i ^ 1])
+        self._i ^= 1
+        return out
+
+
 class NetNodes:
     """The three network nodes (flow_net / mono_depth2 / mask_rcnn ROS services, run_vido.cc:142-157) resident on one device, fp32 like
     the reference.  infer(prev_bgr, cur_bgr) enqueues the three forwards — the detector on the caller's stream, LiteFlowNet and MonoDepth2 back to back on ONE side stream
@@ -140,15 +194,28 @@ class NetNodes:
     the last detector frame's labels and reports no detections (so no overflow); label_mode="instance": the id base advances per detector RUN, a propagated frame keeps its
     source's ids and base (self.id_base).  carried_mask is the image the next propagated frame starts from — a device tensor an external detector or a test may write;
     detector_runs / propagated_frames count, last_propagated tells which the last call was.  Not with on_range="recompute": a flow recomputed after the fact would
-    invalidate the masks already propagated through it (open)."""
+    invalidate the masks already propagated through it (open).
+
+    stable_ids = True (needs label_mode="instance"; stable_hold = h >= 0): instance ids that persist across frames (InstanceIds, csrc/maskassoc.hip).
+    The detector paints at id base 0 on EVERY frame (id_base stays 0, the graph's id word is never switched); on a detector frame its stream waits for the flow's event,
+    as it already does on propagated frames, and the mask handed over is InstanceIds.detected(detector image, slot classes, flow) — an instance keeps the id of the
+    object it overlaps (IoU > 1/2) in the previous mask warped through the flow, a new one takes the next of 1..254, one the detector misses stays for stable_hold detector
+    frames; on a propagated frame it is InstanceIds.propagated(flow).  labels is InstanceIds.classes_by_id (int64 [255]): labels[id - id_base - 1] still reads an id's
+    class.  carried_mask is the image handed over last, also with detect_every = 1.  An overflow of the static head keeps the static head's slots: the redo through
+    the dynamic head would rank the detections anew after the ids were given, so it is skipped and only counted in det_overflows.  Not with skip_detector (infer() raises
+    ValueError: a frame without a detector image would leave the carried image and the id state behind the sequence).  Not with on_range="recompute", for
+    the reason that applies to detect_every > 1: every later mask descends from the flows already used.  With stable_ids = False nothing of this exists: the launches,
+    the id bases and the outputs are those of before."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
-                 detect_every=1):
+                 detect_every=1, stable_ids=False, stable_hold=0):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
+        self._check_stable_ids(stable_ids, stable_hold, label_mode, on_range)
+        self.stable_ids = bool(stable_ids); self.stable_hold = int(stable_hold); self._ids = None
         self.detect_every = int(detect_every)
         self.detector_runs = self.propagated_frames = 0; self.last_propagated = False; self._calls = 0
         if on_range not in self.RANGE_MODES:
@@ -186,6 +253,9 @@ class NetNodes:
         # detect_every > 1: the two mask buffers propagated frames alternate between (carried_mask: the one the next propagated frame reads), the labels and label count of
         # the last detector frame, and a zero for the detection count of propagated frames.  The first mask_propagate call allocates the context's key plane: here, not in a frame
         self._carry = None; self._carry_i = 0; self._last_labels = None; self._last_nlab = None
+        if self.stable_ids:                                           # (its first calls allocate the key plane and the count table in the detector's context: here, not in a frame)
+            self._ids = InstanceIds(ops, height, width, hold=self.stable_hold)
+            self._zero_count = torch.zeros((), dtype=torch.int32, device=dev)
         self._set_detect_every(self.detect_every)
         # random-init detector: un-saturate the class scores so that the reference's detections_per_img cap binds (see nets/weights.py); a synthetic textured frame
         self.score_scale = 1.0
@@ -262,6 +332,8 @@ class NetNodes:
         range_words (pinned int32 [2], or on_range="recompute": NetNodes' own, valid until the next call; self.last_range names them): zeroed, then the frame's range flags
         of the flow context / the detector context are latched into words 0 / 1 on the caller's stream after the three events — they hold this frame's trips alone,
         readable on the host once the caller's stream has passed this point."""
+        if self._ids is not None and getattr(self, "skip_detector", False):
+            raise ValueError("stable_ids with skip_detector: a frame without a detector image would leave the carried image and the id state behind the sequence")
         cur = torch.cuda.current_stream()
         ss = [s or cur for s in self.streams] if self.streams else [cur, cur, cur]
         for s in ss:
@@ -276,10 +348,16 @@ class NetNodes:
         det_frame = self.detect_every == 1 or self._calls % self.detect_every == 0
         self._calls += 1
         with torch.cuda.stream(ss[2]):
-            if self.label_mode == "instance" and det_frame:             # this frame's id base, into the word the graph reads: a device-to-device copy in stream order, nothing waits
+            if self._ids is not None:                                   # stable ids: base 0 on every frame, the word the graph reads is never switched
+                first = self._calls == 1
+            elif self.label_mode == "instance" and det_frame:           # this frame's id base, into the word the graph reads: a device-to-device copy in stream order, nothing waits
                 self.id_base = self.ID_BASES[self._frames & 1]; self._frames += 1      # (per detector run: a propagated frame keeps its source's ids)
                 self._id_word.copy_(self._base_word(self.id_base), non_blocking=True)
-            if not det_frame:                                           # the previous frame's mask through this call's flow; the detector is not launched
+            if not det_frame and self._ids is not None:                 # stable ids: the image handed over last through this call's flow
+                ss[2].wait_event(e0)
+                mask, labels = self._ids.propagated(flow), self._ids.classes_by_id
+                self.last_counts = None if self._last_nlab is None else (self._last_nlab, self._zero_count)
+            elif not det_frame:                                         # the previous frame's mask through this call's flow; the detector is not launched
                 ss[2].wait_event(e0)
                 dst = self._carry[self._carry_i ^ 1]
                 self.ops.mask_propagate(self._carry[self._carry_i], flow, out=dst)
@@ -299,6 +377,15 @@ class NetNodes:
                 mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, trunk=self.g_trunk, **self._label_args())
                 mask = mask_u8.to(torch.int32); self.last_counts = None
             self.last_propagated = not det_frame
+            if det_frame and self._ids is not None:
+                # the detector's per-frame ids -> ids that persist: behind the flow's event, the last mask is warped into this frame and associated with the detector's image
+                if not first:
+                    ss[2].wait_event(e0)
+                if not torch.is_tensor(labels):
+                    labels = torch.as_tensor(labels, dtype=torch.int64)
+                mask = self._ids.detected(mask.contiguous(), labels.to(device=self.dev, dtype=torch.int64).contiguous(), None if first else flow)
+                labels = self._ids.classes_by_id
+                self._last_nlab = None if self.last_counts is None else self.last_counts[0]
             if det_frame:
                 self.detector_runs += 1
                 if self._carry is not None:                             # the image the next propagated frame starts from (the graph's static output does not outlive the next replay)
@@ -328,11 +415,26 @@ class NetNodes:
         if detect_every > 1 and on_range == "recompute":
             raise ValueError("detect_every = %d with on_range='recompute': a flow recomputed after the fact would invalidate the masks already propagated through it" % detect_every)
 
+    @staticmethod
+    def _check_stable_ids(stable_ids, stable_hold, label_mode, on_range):
+        import numbers as _numbers
+        if not stable_ids:
+            return
+        if label_mode != "instance":
+            raise ValueError("stable_ids needs label_mode='instance', not %r: ids that persist are instance ids" % (label_mode,))
+        if on_range == "recompute":
+            raise ValueError("stable_ids with on_range='recompute': a flow recomputed after the fact would invalidate the ids already carried through it")
+        if isinstance(stable_hold, bool) or not isinstance(stable_hold, _numbers.Integral) or stable_hold < 0:
+            raise ValueError("stable_hold: an integer >= 0, not %r" % (stable_hold,))
+
     def _set_detect_every(self, detect_every):
         """The constructor's set-up of the cadence (also tools/prof_detect_every.py, between sequences, so that one set of networks serves every cadence): a new sequence starts —
         the next infer() is a detector frame under id base 0.  Not part of the interface; never while frames are in flight."""
         self._check_detect_every(detect_every, self.on_range)
         self.detect_every = int(detect_every); self._calls = 0; self._frames = 0; self.id_base = 0; self.last_propagated = False
+        if self._ids is not None:                                     # stable ids: InstanceIds owns the images; a new sequence starts with no id live
+            self._ids.reset(); self._last_nlab = None
+            return
         if self.detect_every > 1 and self._carry is None:
             self._carry = [torch.zeros((self.h, self.w), dtype=torch.int32, device=self.dev) for _ in range(2)]
             self._zero_count = torch.zeros((), dtype=torch.int32, device=self.dev)
@@ -342,7 +444,10 @@ class NetNodes:
 
     @property
     def carried_mask(self):
-        """detect_every > 1: the int32 HxW device tensor the next propagated frame is warped from (the last frame's mask); writable in place.  None with detect_every = 1."""
+        """detect_every > 1: the int32 HxW device tensor the next propagated frame is warped from (the last frame's mask); writable in place.  None with detect_every = 1.
+        stable_ids: the image handed over last (InstanceIds.mask), at any detect_every: the next frame, detector frame or not, is warped from it."""
+        if self._ids is not None:
+            return self._ids.mask
         return None if self._carry is None else self._carry[self._carry_i]
 
     def _base_word(self, id_base):
@@ -426,6 +531,8 @@ class NetNodes:
         if n_det_host <= cap:
             return None
         self.det_overflows += 1
+        if self._ids is not None:                                     # stable ids: the ids were given to the static head's slots; the frame keeps them (class docstring)
+            return None
         if range_safe:
             with _nets.range_safe(self.mask_net):
                 mask_u8, labels = _nets.analyse_image(self.mask_net, cur_bgr, feed=self.mask_feed, confidence=self.confidence, **self._label_args(id_base))
