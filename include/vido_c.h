@@ -324,11 +324,19 @@ int vido_correlation(vido_ctx* ctx, const float* first, const float* second, int
                      float* out, int on_device);
 /* the static detector head's tail (confidence test, stable descending order by score, labels of the live slots, their count) in one launch: csrc/nets.hip::k_det_order */
 int vido_det_order(vido_ctx* ctx, const float* scores, const long long* labels, const int* n_det, float confidence, int cap, long long* order, long long* labels_out, long long* n_live);
+/* vido_det_order that also writes the count as an int32 DEVICE word (n_live32, may be NULL): the word the `_n` entry points of the mask head read. */
+int vido_det_order_n(vido_ctx* ctx, const float* scores, const long long* labels, const int* n_det, float confidence, int cap, long long* order, long long* labels_out, long long* n_live,
+                     int32_t* n_live32);
 /* FPN level of every box (LevelMapper, modeling/poolers.py:11-45: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min) in one launch */
 int vido_roi_levels(vido_ctx* ctx, const float* boxes, int n, float k_min, float k_max, int* out);
 /* The mask head's tail for the one class channel a detection needs (mask_head/roi_mask_predictors.py:27-31 + inference.py:29-47): out[n][p] = sigmoid(sum_c w[label[n]][c]
  * feat[n][c][p] + b[label[n]]); feat [n][c][hw] f32, w [classes][c], labels int64 [n], out [n][hw] (csrc/nets.hip). */
 int vido_mask_logit_select(vido_ctx* ctx, const float* feat, const float* w, const float* b, const long long* labels, float* out, int n, int c, int hw, int classes);
+/* The `_n` forms of the mask head (vido_roi_align_fpn_nhwc_n, vido_conv3x3_h_bias_act_n, vido_deconv2x2_bias_act_n, vido_mask_logit_select_n): the call over a batch of n
+ * slots of which only the first *n_live are LIVE.  n_live is a DEVICE int32 word read when the kernel runs, hence at every replay of a captured graph, and clamped to [0, n];
+ * NULL means all n (the plain entry points forward that).  The launch shape is that of n slots; the work is that of n_live: the slots behind the count are never READ (their
+ * rows may hold stale bytes) and, except here, never written.  vido_mask_logit_select_n writes ZEROS to them, so the masks tensor is fully defined. */
+int vido_mask_logit_select_n(vido_ctx* ctx, const float* feat, const float* w, const float* b, const long long* labels, float* out, int n, int c, int hw, int classes, const int32_t* n_live);
 /* Conv epilogue on a DEVICE tensor x[N,C,H,W] (f32, contiguous), in place: x = leaky_relu(x + bias[c], slope) — the bias add and the
  * LeakyReLU(0.1) that follow every convolution of flow_net/src/layers.py fused into one pass (slope = 1: plain bias add). */
 int vido_bias_act(vido_ctx* ctx, float* x, const float* bias, int N, int C, int H, int W, float slope);
@@ -401,6 +409,8 @@ int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, 
  * (vido_slam_amd/nets/ops.py::pack_deconv2x2).  vido_deconv2x2_supported: cout % 128 == 0, cin % 32 == 0, (h w) % 4 == 0, n h w >= 128, split-fp16 arithmetic selected. */
 int vido_deconv2x2_supported(int n, int cin, int cout, int h, int w);
 int vido_deconv2x2_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope);
+/* ... of the first *n_live images only (see vido_mask_logit_select_n): a tile of columns that straddles the count reads zeros for the images behind it and stores nothing there. */
+int vido_deconv2x2_bias_act_n(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live);
 /* ... with the residual at half the resolution [cout][h/2][w/2], added nearest-upsampled: the FPN's lateral convolution + top-down sum (backbone/fpn.py:55-66); h, w even */
 int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual_half, float* y, int cin, int cout, int h, int w, float slope);
 
@@ -454,6 +464,8 @@ int vido_fc_h(vido_ctx* ctx, const float* x, const void* w_packed, const float* 
 int vido_conv3x3_h_supported(int n, int cin, int cout, int h, int w);
 int vido_conv3x3_h_workgroups(int n, int cout, int h, int w);
 int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope);
+/* ... of the first *n_live images only (see vido_mask_logit_select_n); the live workgroups are dealt over the chip as a launch of n_live images would deal them. */
+int vido_conv3x3_h_bias_act_n(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live);
 long long vido_wino3x3_packed_floats_form(int cin, int cout, int form);
 int vido_wino3x3_pack_form(const float* w, int cin, int cout, int form, float* u_packed);
 int vido_wino3x3_bias_act_form(vido_ctx* ctx, const float* x, const float* u_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, int form);
@@ -495,6 +507,9 @@ int vido_nchw_to_nhwc(vido_ctx* ctx, const float* src, int B, int C, int H, int 
 /* vido_roi_align_fpn with CHANNELS-LAST maps feat[l] = [H[l]][W[l]][C] (vido_nchw_to_nhwc once per frame; the box and the mask pooler share the copies). */
 int vido_roi_align_fpn_nhwc(vido_ctx* ctx, const float* const feat[4], const int H[4], const int W[4], const float scale[4], int C, const float* boxes, const int32_t* level,
                             int n, int pooled_h, int pooled_w, int sampling_ratio, float* out);
+/* ... of the first *n_live boxes only (see vido_mask_logit_select_n). */
+int vido_roi_align_fpn_nhwc_n(vido_ctx* ctx, const float* const feat[4], const int H[4], const int W[4], const float scale[4], int C, const float* boxes, const int32_t* level,
+                              int n, int pooled_h, int pooled_w, int sampling_ratio, float* out, const int32_t* n_live);
 /* ---- The local-BA window resident on the device between frames (vido-slam_amd/csrc/bawin.hip).  The reference re-assembles the graph of
  * Optimizer::PartialBatchOptimization from the Map on every call (Optimizer.cc:56-94, 276-350).  Here a ring of the last frames' static features stays on the device:
  * vido_bawin_push_frame sends one frame's rows (Get3DinCamera measurement, world point, index of the previous frame's feature it continues: Map::vpFeatSta / vfDepSta /

@@ -29,7 +29,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define C1_TM 128
 #define C1_TN 128
 
-struct C1Args { const float* x; const float* wp; const float* bias; const float* res; float* y; int M, N, K, mt, total, nchunk; float slope; unsigned xbytes, wbytes; int W; unsigned* range_flag; int hwimg, c4; };      // hwimg > 0 (k_conv1x1_b3 only): x is a BATCH [img][K][hwimg] and position p = img hwimg + hw; c4: RES 3
+struct C1Args { const float* x; const float* wp; const float* bias; const float* res; float* y; int M, N, K, mt, total, nchunk; float slope; unsigned xbytes, wbytes; int W; unsigned* range_flag; int hwimg, c4; const int* n_live; };      // hwimg > 0 (k_conv1x1_b3 only): x is a BATCH [img][K][hwimg] and position p = img hwimg + hw; c4: RES 3; n_live (RES 3, may be null): device word, the first n_live images are computed
 
 // RES: 1 a residual [cout][H*W] is added, 2 a residual at HALF the resolution [cout][H/2][W/2] is added nearest-upsampled (the FPN's top-down path: fpn.py
 // `F.interpolate(last_inner, scale_factor=2, mode="nearest") + inner_lateral`); KC: input channels per chunk and barrier (64: 128 KB of LDS, 128 matrix instructions per
@@ -335,8 +335,19 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
     extern __shared__ __attribute__((aligned(16))) float c1_lds[];
     char* L = (char*)c1_lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), w = wv & 3, g = wv >> 2;
-    const int per = gridDim.x >> 3, item = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (item >= A.total) return;
+    // RES 3 with a live count (a device word read here, i.e. at every replay of a captured graph): the columns are those of the first n_live images, NL of them.  The tiles are
+    // dealt as a launch over NL columns deals them, the workgroups behind them leave before their first copy and barrier; the tile that straddles NL gets zeros for the columns
+    // behind it (the descriptors below end with the live images, so the stale bytes there — an infinity would raise the range flag — are never READ) and stores nothing for them.
+    int total = A.total, per = gridDim.x >> 3, NL = A.N;
+    unsigned xbytes = A.xbytes;
+    if constexpr (RES == 3) {
+        if (A.n_live) {
+            const int nl = min(max(*A.n_live, 0), A.N / A.hwimg);
+            NL = nl * A.hwimg; total = A.mt * ((NL + C1_TN - 1) / C1_TN); per = (total + 7) >> 3; xbytes = 4u * (unsigned)A.K * (unsigned)NL;
+        }
+    }
+    const int q8 = blockIdx.x >> 3, item = (blockIdx.x & 7) * per + q8;
+    if (q8 >= per || item >= total) return;
     const int nt = item / A.mt, mtile = item - nt * A.mt, n0 = nt * C1_TN, m0 = mtile * C1_TM;
     const int ns = A.nchunk, nb = ns / G;                                 // k-steps of 16 input channels (even: K % 32 == 0), slots
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)A.wp, 0, A.wbytes, 0x00020000);
@@ -362,7 +373,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
         const unsigned aoff = (unsigned)(NP * 1024) * (unsigned)t, boff = bstep * (unsigned)t;
 #pragma unroll
         for (int q = 0; q < NP; q++) __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (__attribute__((address_space(3))) void*)(S + q * 4096), 16, avo, abase[q] + aoff, 0, 0);
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A.x + boff), 0, A.xbytes - boff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A.x + boff), 0, xbytes - boff, 0x00020000);
 #pragma unroll
         for (int q = 0; q < 2; q++) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void*)(S + NP * 4096 + q * 4096), 16, bvo[q], 0, 0, 0);
     };
@@ -509,7 +520,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
     }
     auto ep_load = [&](int rb, Ep& E) {
         const int co0 = m0 + 32 * rb + 4 * (lane >> 5);
-        if (q_out < A.N) {
+        if (q_out < NL) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int co = co0 + 8 * (r >> 2) + (r & 3);
@@ -524,7 +535,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
         float ov[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) ov[r] = other ? other[r * 64] : 0.f;
-        if (q_out < A.N) {
+        if (q_out < NL) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int co = co0 + 8 * (r >> 2) + (r & 3);
@@ -611,10 +622,10 @@ int vido_conv1x1_layout(int cin, int cout, int hw)
  *   0: element (co, k) at [co / 32][k / 8][32 * (k & 1) + co % 32][(k % 8) / 2];   1: at [co / 16][k / 16][16 * (k & 3) + co % 16][(k % 16) / 4]
  * (vido_slam_amd/nets/ops.py::pack_conv1x1).  slope 0 = ReLU, 1 = none (0 <= slope <= 1).  Enqueues on the adopted stream; capturable. */
 static int c1_launch(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, int res_mode, float* y, int cin, int cout, int hw, int w, float slope,
-                     int hwimg = 0, int c4 = 0)
+                     int hwimg = 0, int c4 = 0, const int32_t* n_live = nullptr)
 {
     if (!ctx) return VIDO_E_INVALID;
-    if (!x || !w_packed || !y || x == y || !vido_conv1x1_supported(cin, cout, hw) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 3) || ((uintptr_t)w_packed & 15))
+    if (!x || !w_packed || !y || x == y || !vido_conv1x1_supported(cin, cout, hw) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)n_live) & 3) || ((uintptr_t)w_packed & 15))
         return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1: no kernel for %d -> %d channels at %d positions (or a pointer is misaligned, or slope outside [0, 1])", cin, cout, hw);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
@@ -624,7 +635,7 @@ static int c1_launch(vido_ctx* ctx, const float* x, const float* w_packed, const
     if (layout >= 2) {
         const int np = layout == 3 ? 2 : 3;
         const int mt = cout / C1_TM, ntl = (hw + C1_TN - 1) / C1_TN, total = mt * ntl;
-        C1Args A{x, w_packed, bias, residual, y, cout, hw, cin, mt, total, cin / 16, slope, (unsigned)(4ll * cin * hw), (unsigned)(2ll * np * cin * cout), w, ctx->c1_range_flag, hwimg, c4};
+        C1Args A{x, w_packed, bias, residual, y, cout, hw, cin, mt, total, cin / 16, slope, (unsigned)(4ll * cin * hw), (unsigned)(2ll * np * cin * cout), w, ctx->c1_range_flag, hwimg, c4, n_live};
         // form: VIDO_CONV1X1_B3_FORM = 0 (default: by shape), 1 = <1, 6>, 2 = <2, 4>, 3 = <1, 4> two workgroups per CU
         static const int force_form = [] { const char* e = getenv("VIDO_CONV1X1_B3_FORM"); return e ? atoi(e) : 0; }();
         int form = force_form ? force_form : (cin >= 512 && total <= 320 ? 2 : 3);
@@ -699,8 +710,13 @@ int vido_deconv2x2_supported(int n, int cin, int cout, int h, int w)
 }
 int vido_deconv2x2_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope)
 {
+    return vido_deconv2x2_bias_act_n(ctx, x, w_packed, bias, y, n, cin, cout, h, w, slope, nullptr);
+}
+/* ... of the first *n_live images (a DEVICE int32 word read when the kernel runs, clamped to [0, n]; NULL: all n): the images behind are neither read nor written. */
+int vido_deconv2x2_bias_act_n(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live)
+{
     if (ctx && !vido_deconv2x2_supported(n, cin, cout, h, w)) return vido_set_error(ctx, VIDO_E_INVALID, "deconv2x2: no kernel for %d x %d -> %d channels at %d x %d", n, cin, cout, h, w);
-    return c1_launch(ctx, x, w_packed, bias, nullptr, 3, y, cin, 4 * cout, n * h * w, w, slope, h * w, cout);
+    return c1_launch(ctx, x, w_packed, bias, nullptr, 3, y, cin, 4 * cout, n * h * w, w, slope, h * w, cout, n_live);
 }
 
 int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope)

@@ -45,7 +45,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define C3_PBUF(BR) (2 * C3_PLANE(BR))
 #define C3_LDS(BR) (C3_RBW * C3_WSLOT + C3_RAW(BR) + 2 * C3_PBUF(BR))
 
-struct C3Args { const float* x; const void* wp; const float* bias; float* y; int N, Cin, Cout, H, W, nby, nbx, mt, total, nchunk; float slope; unsigned wbytes; unsigned* range_flag; };
+struct C3Args { const float* x; const void* wp; const float* bias; float* y; int N, Cin, Cout, H, W, nby, nbx, mt, total, nchunk; float slope; unsigned wbytes; unsigned* range_flag; const int* n_live; };      // n_live (may be null): device word, the first n_live images of the batch are computed
 
 template <int RPW, int CG>
 __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
@@ -54,8 +54,13 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
     extern __shared__ __attribute__((aligned(16))) char c3_lds[];
     char* L = c3_lds;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int per = gridDim.x >> 3, item = (blockIdx.x & 7) * per + (blockIdx.x >> 3);      // an XCD walks a contiguous range of items, the channel block fastest
-    if (item >= A.total) return;
+    // an XCD walks a contiguous range of items, the channel block fastest.  With a live count (read here, i.e. at every replay of a captured graph) the items are those of a
+    // launch over the first n_live images — the same round-robin over the XCDs, the workgroups behind them leave before their first copy and barrier — so an image past the
+    // count is neither computed nor READ (its rows may hold stale bytes: an infinity there would raise the range flag)
+    int total = A.total, per = gridDim.x >> 3;
+    if (A.n_live) { const int nl = min(max(*A.n_live, 0), A.N); total = nl * A.nby * A.nbx * A.mt; per = (total + 7) >> 3; }
+    const int q8 = blockIdx.x >> 3, item = (blockIdx.x & 7) * per + q8;
+    if (q8 >= per || item >= total) return;
     const int nt = item / A.mt, mtile = item - nt * A.mt, m0 = mtile * MT;
     const int bpi = A.nby * A.nbx, n = nt / bpi, brem = nt - n * bpi, by = brem / A.nbx, bx = brem - by * A.nbx, Y0 = by * BR, X0 = bx * 16;
     const int rp = CG == 1 ? w : (w & 3), rb0 = CG == 1 ? 0 : RPW * (w >> 2);      // the wave's row pair of the block, its first row block of 32 channels
@@ -248,15 +253,22 @@ int vido_conv3x3_h_workgroups(int n, int cout, int h, int w) { const int br = c3
  * slope: 0 = ReLU, 1 = none (0 <= slope <= 1).  Activations must be finite and below 65504 in magnitude (else: vido_conv1x1_range_flag).  Enqueues on the adopted stream; capturable. */
 int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope)
 {
+    return vido_conv3x3_h_bias_act_n(ctx, x, w_packed, bias, y, n, cin, cout, h, w, slope, nullptr);
+}
+
+/* The same over the first *n_live images only (n_live: a DEVICE int32 word read when the kernel runs — at every replay of a captured graph —, clamped to [0, n]; NULL: all n).
+ * The launch shape is that of n images; the images behind the count are neither read nor written (x may hold anything there, y keeps what it held). */
+int vido_conv3x3_h_bias_act_n(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live)
+{
     if (!ctx) return VIDO_E_INVALID;
-    if (!x || !w_packed || !y || x == y || !vido_conv3x3_h_supported(n, cin, cout, h, w) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y) & 3) || ((uintptr_t)w_packed & 15))
+    if (!x || !w_packed || !y || x == y || !vido_conv3x3_h_supported(n, cin, cout, h, w) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)n_live) & 3) || ((uintptr_t)w_packed & 15))
         return vido_set_error(ctx, VIDO_E_INVALID, "conv3x3_h: no kernel for %d x %d -> %d channels at %d x %d (or a pointer is misaligned, or slope outside [0, 1])", n, cin, cout, h, w);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
     const int br = c3_block_rows(n, cout, h, w);
     const int nby = (h + br - 1) / br, nbx = (w + 15) / 16, mt = cout >= 128 ? cout / 128 : 1, total = n * nby * nbx * mt;
     const int nchunk = (cin + 15) / 16;
-    C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag};
+    C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag, n_live};
     static bool attr[64] = {};
     if (!attr[ctx->device & 63]) {
 #define C3_ATTR(RPW_, CG_) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h<RPW_, CG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3_LDS(16 / CG_)))

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_correlation_reduce(const float* __restr
 // live[i] = score[i] > confidence and i < n_det; order = stable descending sort of (live ? score : -1); labels_out[r] = live[order[r]] ? label[order[r]] : 0; n_live.
 // cap <= 1024 slots, one workgroup, rank by counting (a stable sort: ties keep their slot order, like torch.sort(stable=True)).
 __global__ __launch_bounds__(1024) void k_det_order(const float* __restrict__ scores, const long long* __restrict__ labels, const int* __restrict__ n_det, float confidence, int cap,
-                                                   long long* __restrict__ order, long long* __restrict__ labels_out, long long* __restrict__ n_live)
+                                                   long long* __restrict__ order, long long* __restrict__ labels_out, long long* __restrict__ n_live, int* __restrict__ n_live32)
 {
     __shared__ float key[1024];
     __shared__ int cnt;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(1024) void k_det_order(const float* __restrict__ sc
         if (live) atomicAdd(&cnt, 1);
     }
     __syncthreads();
-    if (i == 0) *n_live = cnt;
+    if (i == 0) { *n_live = cnt; if (n_live32) *n_live32 = cnt; }      // (n_live32: the word the mask head's `_n` launches read)
 }
 
 // LevelMapper of the FPN pooler (maskrcnn_benchmark/modeling/poolers.py:11-45) for every box in ONE launch — the same fp32 operations in the same order as the torch
@@ -108,10 +108,14 @@ __global__ void k_roi_levels(const float* __restrict__ boxes, int n, float k_min
 
 // one thread per pixel of one detection: 256 (c) multiply-adds down the channels, the detection's weight row in LDS; reads are coalesced over the pixels
 __global__ __launch_bounds__(256) void k_mask_logit_select(const float* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ b, const long long* __restrict__ labels,
-                                                           float* __restrict__ out, int c, int hw, int classes)
+                                                           float* __restrict__ out, int c, int hw, int classes, const int* __restrict__ n_live)
 {
     __shared__ float wl[1024];
     const int n = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    if (n_live && n >= *n_live) {                                    // a slot behind the live count: zeros, its features (never computed) are not read
+        if (p < hw) out[(size_t)n * hw + p] = 0.f;
+        return;
+    }
     long long lab = labels[n]; lab = lab < 0 ? 0 : (lab >= classes ? classes - 1 : lab);
     for (int i = threadIdx.x; i < c; i += 256) wl[i] = w[(size_t)lab * c + i];
     __syncthreads();
@@ -208,9 +212,10 @@ __global__ __launch_bounds__(256) void k_bias_res_act(float* __restrict__ x, con
 struct RoiLevels { const float* feat[4]; int H[4], W[4]; float scale[4]; };     // channels-last maps
 template <int SR /* sampling ratio known at compile time (2: the node's setting; the 4 x 4 taps of a bin are then 16 independent loads in flight), 0: run-time / adaptive */>
 __global__ __launch_bounds__(256) void k_roi_align_nhwc(RoiLevels L, int C, const float* __restrict__ rois, int roi_stride /* 5: (batch, x1, y1, x2, y2); 4: (x1, y1, x2, y2) */,
-                                                        const int* __restrict__ level /* null: level 0 */, int PH, int PW, int sampling, float* __restrict__ out)
+                                                        const int* __restrict__ level /* null: level 0 */, int PH, int PW, int sampling, float* __restrict__ out, const int* __restrict__ n_live /* null: every roi */)
 {
     extern __shared__ __attribute__((aligned(16))) float rl_tile[];
+    if (n_live && (int)blockIdx.x >= *n_live) return;                         // (uniform per workgroup, before the barrier) a roi behind the live count: its rows of `out` stay as they are
     const int i = blockIdx.x, c0 = blockIdx.y * 64, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nbin = PH * PW, pitch = nbin | 1;
     const float* r = rois + (size_t)roi_stride * i;
@@ -782,11 +787,17 @@ int vido_correlation(vido_ctx* ctx, const float* first, const float* second, int
  * slots that fail the confidence test or lie past n_det behind them in slot order), labels_out int64 [cap] (0 for those), n_live int64 [1].  cap <= 1024. */
 int vido_det_order(vido_ctx* ctx, const float* scores, const long long* labels, const int* n_det, float confidence, int cap, long long* order, long long* labels_out, long long* n_live)
 {
+    return vido_det_order_n(ctx, scores, labels, n_det, confidence, cap, order, labels_out, n_live, nullptr);
+}
+/* ... and the count once more as an int32 word (n_live32, may be NULL) for the mask head's `_n` entry points */
+int vido_det_order_n(vido_ctx* ctx, const float* scores, const long long* labels, const int* n_det, float confidence, int cap, long long* order, long long* labels_out, long long* n_live,
+                     int32_t* n_live32)
+{
     if (!ctx) return VIDO_E_INVALID;
     if (!scores || !labels || !n_det || !order || !labels_out || !n_live || cap < 1 || cap > 1024) return vido_set_error(ctx, VIDO_E_INVALID, "det_order: bad arguments (cap 1 .. 1024)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    hipLaunchKernelGGL(k_det_order, dim3(1), dim3(1024), 0, st, scores, labels, n_det, confidence, cap, order, labels_out, n_live);
+    hipLaunchKernelGGL(k_det_order, dim3(1), dim3(1024), 0, st, scores, labels, n_det, confidence, cap, order, labels_out, n_live, n_live32);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }
@@ -809,11 +820,16 @@ int vido_roi_levels(vido_ctx* ctx, const float* boxes, int n, float k_min, float
  * a bias pass, a sigmoid pass and a gather (81 x the multiply-adds, four launches).  feat [n][c][hw] f32, w [classes][c], labels int64 [n] (clamped to the class range), out [n][hw]. */
 int vido_mask_logit_select(vido_ctx* ctx, const float* feat, const float* w, const float* b, const long long* labels, float* out, int n, int c, int hw, int classes)
 {
+    return vido_mask_logit_select_n(ctx, feat, w, b, labels, out, n, c, hw, classes, nullptr);
+}
+/* ... for the first *n_live slots (DEVICE int32 word read by the kernel, NULL: all); the slots behind get ZEROS and their features are not read. */
+int vido_mask_logit_select_n(vido_ctx* ctx, const float* feat, const float* w, const float* b, const long long* labels, float* out, int n, int c, int hw, int classes, const int32_t* n_live)
+{
     if (!ctx) return VIDO_E_INVALID;
     if (!feat || !w || !labels || !out || n < 1 || c < 1 || c > 1024 || hw < 1 || classes < 1) return vido_set_error(ctx, VIDO_E_INVALID, "mask_logit_select: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    hipLaunchKernelGGL(k_mask_logit_select, dim3((unsigned)((hw + 255) / 256), (unsigned)n), dim3(256), 0, st, feat, w, b, labels, out, c, hw, classes);
+    hipLaunchKernelGGL(k_mask_logit_select, dim3((unsigned)((hw + 255) / 256), (unsigned)n), dim3(256), 0, st, feat, w, b, labels, out, c, hw, classes, n_live);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }
@@ -978,8 +994,8 @@ int vido_roi_align(vido_ctx* ctx, const float* feat, int B, int C, int H, int W,
     const size_t lds = (size_t)64 * ((pooled_h * pooled_w) | 1) * sizeof(float);
     if (lds > 150 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "roi_align: pooled size %d x %d too large", pooled_h, pooled_w);
     { int rc = roi_lds_limit(ctx, lds); if (rc) return rc; }
-    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout);
-    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout);
+    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr);
+    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
     if (!on_device) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1096,6 +1112,12 @@ int vido_roi_align_fpn(vido_ctx* ctx, const float* const feat[4], const int H[4]
 int vido_roi_align_fpn_nhwc(vido_ctx* ctx, const float* const feat[4], const int H[4], const int W[4], const float scale[4], int C, const float* boxes, const int32_t* level,
                             int n, int pooled_h, int pooled_w, int sampling_ratio, float* out)
 {
+    return vido_roi_align_fpn_nhwc_n(ctx, feat, H, W, scale, C, boxes, level, n, pooled_h, pooled_w, sampling_ratio, out, nullptr);
+}
+/* ... of the first *n_live boxes (DEVICE int32 word read by the kernel, NULL: all n); the rows of `out` behind them are not written. */
+int vido_roi_align_fpn_nhwc_n(vido_ctx* ctx, const float* const feat[4], const int H[4], const int W[4], const float scale[4], int C, const float* boxes, const int32_t* level,
+                              int n, int pooled_h, int pooled_w, int sampling_ratio, float* out, const int32_t* n_live)
+{
     if (!ctx) return VIDO_E_INVALID;
     if (!feat || !H || !W || !scale || C < 1 || n < 0 || pooled_h < 1 || pooled_w < 1 || (n && (!boxes || !level || !out))) return vido_set_error(ctx, VIDO_E_INVALID, "roi_align_fpn_nhwc: bad arguments");
     if (n == 0) return VIDO_OK;
@@ -1106,8 +1128,8 @@ int vido_roi_align_fpn_nhwc(vido_ctx* ctx, const float* const feat[4], const int
     const size_t lds = (size_t)64 * ((pooled_h * pooled_w) | 1) * sizeof(float);
     if (lds > 150 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "roi_align_fpn: pooled size %d x %d too large", pooled_h, pooled_w);
     { int rc = roi_lds_limit(ctx, lds); if (rc) return rc; }
-    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out);
-    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out);
+    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live);
+    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }

@@ -259,16 +259,19 @@ class _RPNHead(nn.Module):                 # rpn/rpn.py:74-107
         return [self.cls_logits(x) for x in t], [self.bbox_pred(x) for x in t]
 
 
-def _conv_bias_relu(conv, x, ops):
-    """relu(conv(x)); on the device the library convolution runs without its bias and the bias + ReLU are ONE in-place pass (vido_bias_act) instead of an add and a clamp."""
+def _conv_bias_relu(conv, x, ops, n_live=None):
+    """relu(conv(x)); on the device the library convolution runs without its bias and the bias + ReLU are ONE in-place pass (vido_bias_act) instead of an add and a clamp.
+    n_live (one int32 device word, the static mask head): only the first n_live images of the batch are needed.  The split-fp16 kernels then compute those alone and never
+    read the others, whose rows hold stale bytes (an infinity there would raise the range flag); the fp32 routes compute every image — garbage in, garbage out for the
+    dead ones, per image, which nothing downstream looks at."""
     if ops is None or not x.is_cuda or conv.bias is None:
         return F.relu(conv(x))
     if isinstance(conv, nn.Conv2d) and hasattr(ops, "wino3x3_conv") and not os.environ.get("VIDO_NO_WINO"):
-        y = ops.wino3x3_conv(conv, x, 0.0)              # dense 3x3: Winograd on the matrix pipe with bias + ReLU in its epilogue (csrc/wino.hip)
+        y = ops.wino3x3_conv(conv, x, 0.0, n_live=n_live) if n_live is not None else ops.wino3x3_conv(conv, x, 0.0)              # dense 3x3: Winograd on the matrix pipe with bias + ReLU in its epilogue (csrc/wino.hip)
         if y is not None:
             return y
     if isinstance(conv, nn.ConvTranspose2d) and hasattr(ops, "deconv2x2_conv"):
-        y = ops.deconv2x2_conv(conv, x, 0.0)           # the mask head's 2 x 2 stride-2 transposed convolution: one split-fp16 GEMM with a scatter epilogue (csrc/conv1x1.hip)
+        y = ops.deconv2x2_conv(conv, x, 0.0, n_live) if n_live is not None else ops.deconv2x2_conv(conv, x, 0.0)           # the mask head's 2 x 2 stride-2 transposed convolution: one split-fp16 GEMM with a scatter epilogue (csrc/conv1x1.hip)
         if y is not None:
             return y
     if isinstance(conv, nn.ConvTranspose2d):
@@ -395,14 +398,14 @@ class _Pooler(nn.Module):                  # modeling/poolers.py:11-121
         self.res, self.scales, self.sr, self.ops = resolution, scales, sampling_ratio, ops
         self.k_min = -math.log2(scales[0]); self.k_max = -math.log2(scales[-1])
 
-    def forward(self, feats, boxes):
+    def forward(self, feats, boxes, n_live=None):
         if boxes.is_cuda and boxes.dtype == torch.float32 and hasattr(self.ops, "roi_levels") and not os.environ.get("VIDO_NO_ROI_LEVELS"):
             lvl = self.ops.roi_levels(boxes, self.k_min, self.k_max)                         # one launch instead of fourteen element-wise ones (same fp32 operations)
         else:
             area = (boxes[:, 2] - boxes[:, 0] + 1) * (boxes[:, 3] - boxes[:, 1] + 1)
             lvl = torch.floor(4 + torch.log2(torch.sqrt(area) / 224 + 1e-6)).clamp(min=self.k_min, max=self.k_max).to(torch.int64) - int(self.k_min)
         if isinstance(feats, FpnMaps):                                                      # channels-last copies made once per frame (MaskRCNN.fpn_maps): lanes across channels
-            return self.ops.roi_align_fpn_nhwc(feats.nhwc, boxes, lvl, (self.res, self.res), self.scales, self.sr)
+            return self.ops.roi_align_fpn_nhwc(feats.nhwc, boxes, lvl, (self.res, self.res), self.scales, self.sr, n_live)      # (n_live: the first n_live boxes only)
         if hasattr(self.ops, "roi_align_fpn") and boxes.is_cuda and len(feats) == 4:       # one launch, no per-level nonzero / gather / scatter
             return self.ops.roi_align_fpn(feats, boxes, lvl, (self.res, self.res), self.scales, self.sr)
         rois = torch.cat([boxes.new_zeros((len(boxes), 1)), boxes], 1)
@@ -549,10 +552,10 @@ class _MaskFeatures(nn.Module):            # roi_mask_feature_extractors.py:17-6
         for i, ch in enumerate(c.mask_layers, 1):
             setattr(self, "mask_fcn%d" % i, nn.Conv2d(cin, ch, 3, 1, 1)); self.names.append("mask_fcn%d" % i); cin = ch
 
-    def forward(self, feats, boxes):
-        x = self.pooler(feats, boxes)
+    def forward(self, feats, boxes, n_live=None):
+        x = self.pooler(feats, boxes, n_live) if n_live is not None else self.pooler(feats, boxes)
         for n in self.names:
-            x = _conv_bias_relu(getattr(self, n), x, self.pooler.ops if hasattr(self.pooler.ops, "bias_act_") else None)
+            x = _conv_bias_relu(getattr(self, n), x, self.pooler.ops if hasattr(self.pooler.ops, "bias_act_") else None, n_live)
         return x
 
 
@@ -567,12 +570,12 @@ class _MaskPredictor(nn.Module):           # roi_mask_predictors.py:11-31
     def forward(self, x):
         return self.mask_fcn_logits(_conv_bias_relu(self.conv5_mask, x, self._ops))
 
-    def selected(self, x, labels):
+    def selected(self, x, labels, n_live=None):
         """sigmoid(forward(x))[arange(n), labels][:, None] with only each detection's own class channel computed (vido_mask_logit_select): 1 launch instead of the 81-channel
-        convolution, its bias pass, the sigmoid and the gather."""
-        y = _conv_bias_relu(self.conv5_mask, x, self._ops)
+        convolution, its bias pass, the sigmoid and the gather.  n_live: see _conv_bias_relu; the slots behind it come out 0 (vido_mask_logit_select_n)."""
+        y = _conv_bias_relu(self.conv5_mask, x, self._ops, n_live)
         if self._ops is not None and y.is_cuda and hasattr(self._ops, "mask_logit_select") and not os.environ.get("VIDO_NO_MASK_SELECT") and labels.dtype == torch.int64:
-            return self._ops.mask_logit_select(y.contiguous(), self.mask_fcn_logits, labels.contiguous())
+            return self._ops.mask_logit_select(y.contiguous(), self.mask_fcn_logits, labels.contiguous(), n_live)
         return self.mask_fcn_logits(y).sigmoid()[torch.arange(x.shape[0], device=labels.device), labels][:, None]
 
 
@@ -696,9 +699,13 @@ def _fpn_maps(self, feats):
 
 
 @torch.no_grad()
-def _heads_static(self, feats, logits, deltas, image_hw, cap=None):
+def _heads_static(self, feats, logits, deltas, image_hw, cap=None, confidence=None):
     """heads() with static shapes end to end (device-side RPN selection, fixed 1000 proposals, postprocess_static, the mask head on `cap` padded slots): no host
-    synchronisation anywhere, so trunk + heads + label image replay as ONE hipGraph.  Slots >= n_det hold zero boxes / label 0."""
+    synchronisation anywhere, so trunk + heads + label image replay as ONE hipGraph.  Slots >= n_det hold zero boxes / label 0.
+    confidence (analyse_image_static passes it; None: every slot gets its mask, in slot order): the slots are ORDERED first (vido_det_order: live = score > confidence and
+    slot < n_det, descending score, the others behind) and the mask head runs on boxes[order] with the live count as a device word, so that its launches — same shapes at
+    every replay — compute the live slots only.  The result then also holds `order`, `labels_ordered` (0 for the dead slots), `n_live`, and `masks` are in THAT order: a live
+    slot's mask is bit for bit the one the default call gives its box, a dead slot's is 0."""
     H, W = image_hw; c = self.config; cap = cap or c.detections_per_img
     fused = self.fused_post and hasattr(self.rpn.ops, "det_select") and c.pre_nms_top_n <= 1024 and c.rpn_min_size <= 0       # csrc/detpost.hip (False: the torch-op form of round 3's first static head)
     proposals, objectness = (self.rpn.proposals_fused if fused else self.rpn.proposals_device)(feats, logits, deltas, (W, H))
@@ -707,8 +714,14 @@ def _heads_static(self, feats, logits, deltas, image_hw, cap=None):
     lg, dl = bh.predictor(bh.feature_extractor(maps, proposals))
     boxes, scores, labels, n_det = (bh.postprocess_fused if fused else bh.postprocess_static)(lg, dl, proposals, (W, H), objectness, cap)
     mh = self.roi_heads.mask
-    masks = mh.predictor.selected(mh.feature_extractor(maps, boxes), labels)      # (only each slot's own class channel: vido_mask_logit_select)
-    return dict(boxes=boxes, scores=scores, labels=labels, masks=masks, n_det=n_det, proposals=proposals, objectness=objectness, n_proposals=(objectness >= 0).sum())
+    out = dict(boxes=boxes, scores=scores, labels=labels, n_det=n_det, proposals=proposals, objectness=objectness, n_proposals=(objectness >= 0).sum())
+    if confidence is not None:
+        order, lab, n_live, n32 = self.rpn.ops.det_order(scores.contiguous(), labels.contiguous(), n_det.reshape(1), confidence, count32=True)
+        out.update(order=order, labels_ordered=lab, n_live=n_live,
+                   masks=mh.predictor.selected(mh.feature_extractor(maps, boxes[order], n32), lab, n32))      # (a live slot keeps its own label in `lab`)
+        return out
+    out["masks"] = mh.predictor.selected(mh.feature_extractor(maps, boxes), labels)      # (only each slot's own class channel: vido_mask_logit_select)
+    return out
 
 
 MaskRCNN.fused_post = True
@@ -762,7 +775,12 @@ def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), c
     labels[id - id_base - 1] is the pixel's class."""
     _check_label_mode(label_mode)
     H, W = out_hw
-    out = net.heads_static(feats, logits, deltas, feed, cap)
+    ops = net.rpn.ops
+    c = net.config; ncap = cap or c.detections_per_img
+    fused = net.fused_post and hasattr(ops, "det_select") and c.pre_nms_top_n <= 1024 and c.rpn_min_size <= 0      # (heads_static's own test: n_det is then an int32 device word)
+    # the mask head computes only the slots that pass the confidence test (heads_static(confidence=...)); VIDO_MASK_HEAD_ALL=1: every slot, the order afterwards
+    live_first = (hasattr(ops, "det_order") and fused and ncap <= 1024 and feats[0].is_cuda and not os.environ.get("VIDO_NO_DET_ORDER") and not os.environ.get("VIDO_MASK_HEAD_ALL"))
+    out = net.heads_static(feats, logits, deltas, feed, cap, confidence) if live_first else net.heads_static(feats, logits, deltas, feed, cap)
     cap = out["boxes"].shape[0]
     rw, rh = float(W) / feed[1], float(H) / feed[0]
     cache = net.__dict__.setdefault("_const_cache", {})            # constants are made once, outside any capture: tensor-from-list is a synchronous host-to-device copy, which a hipGraph capture forbids
@@ -770,21 +788,25 @@ def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), c
     if key not in cache:
         cache[key] = out["boxes"].new_tensor([rw, rh, rw, rh])
     boxes = out["boxes"] * cache[key]
-    ops = net.rpn.ops
     nd = out["n_det"]
-    if hasattr(ops, "det_order") and cap <= 1024 and nd.dtype == torch.int32 and out["labels"].dtype == torch.int64 and not os.environ.get("VIDO_NO_DET_ORDER"):
+    if "order" in out:                                                  # ordered before the mask head: the masks are in that order already
+        order, labels, n_live = out["order"], out["labels_ordered"], out["n_live"]
+        masks = out["masks"]
+    elif hasattr(ops, "det_order") and cap <= 1024 and nd.dtype == torch.int32 and out["labels"].dtype == torch.int64 and not os.environ.get("VIDO_NO_DET_ORDER"):
         order, labels, n_live = ops.det_order(out["scores"].contiguous(), out["labels"].contiguous(), nd.reshape(1), confidence)      # one launch instead of eleven
     else:
         live = (out["scores"] > confidence) & (torch.arange(cap, device=boxes.device) < nd)
         order = torch.sort(torch.where(live, out["scores"], out["scores"].new_full((), -1.0)), descending=True, stable=True)[1]
         labels = torch.where(live, out["labels"], torch.zeros_like(out["labels"]))[order]
         n_live = live.sum()
+    if "order" not in out:
+        masks = out["masks"][order]
     if label_mode == "instance":
         if cap > 255:
             raise ValueError("label_mode='instance': %d slots, ids are u8" % cap)
-        img = ops.mask_instance_image(out["masks"][order], boxes[order], labels, H, W, id_base=id_base)
+        img = ops.mask_instance_image(masks, boxes[order], labels, H, W, id_base=id_base)
     else:
-        img = ops.mask_label_image(out["masks"][order], boxes[order], labels, H, W)
+        img = ops.mask_label_image(masks, boxes[order], labels, H, W)
     return img, labels, n_live, out["n_det"]
 
 

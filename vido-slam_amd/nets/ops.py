@@ -40,6 +40,14 @@ class HipOps:
         """True inside range_safe(): conv1x1_conv / conv1x1_bias_act callers, the direct 3x3, fc_h_linear and deconv2x2_conv take their fp32 routes."""
         return self._range_safe > 0
 
+    @staticmethod
+    def _live_ptr(n_live):
+        """The `_n` entry points' last argument: None, or a one-element int32 DEVICE tensor (the live count: read by the kernel when it runs, clamped to the batch)."""
+        if n_live is None:
+            return None
+        assert n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1, "n_live: a one-element int32 device tensor"
+        return C.c_void_p(n_live.data_ptr())
+
     def _adopt_stream(self):
         st = torch.cuda.current_stream().cuda_stream
         self.ctx._check(self.ctx.lib.vido_set_stream(self.ctx.h, C.c_void_p(st), 1))
@@ -63,9 +71,9 @@ class HipOps:
         self.ctx._check(self.ctx.lib.vido_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), N, Cc, H, W, C.c_float(slope)))
         return x
 
-    def deconv2x2_conv(self, conv, x, slope):
+    def deconv2x2_conv(self, conv, x, slope, n_live=None):
         """nn.ConvTranspose2d `conv` (2 x 2, stride 2, no padding) + bias + activation of a batch as one split-fp16 GEMM with a scatter epilogue (csrc/conv1x1.hip, RES 3), else
-        None; the packed weight is cached on the module."""
+        None; the packed weight is cached on the module.  n_live (one int32 device word): only the first n_live images are read and written (vido_deconv2x2_bias_act_n)."""
         w = conv.weight
         if (tuple(w.shape[2:]) != (2, 2) or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (0, 0) or tuple(conv.output_padding) != (0, 0) or tuple(conv.dilation) != (1, 1)
                 or conv.groups != 1 or not x.is_cuda or x.dtype != torch.float32 or os.environ.get("VIDO_NO_DECONV_H") or self._range_safe):
@@ -80,20 +88,22 @@ class HipOps:
         self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * n * cin * cout * 4 * H * W
         self._adopt_stream()
         b = conv.bias
-        self.ctx._check(self.ctx.lib.vido_deconv2x2_bias_act(self.ctx.h, C.c_void_p(x.contiguous().data_ptr()), C.c_void_p(conv._dc_w.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
-                                                             C.c_void_p(out.data_ptr()), n, cin, cout, H, W, C.c_float(slope)))
+        self.ctx._check(self.ctx.lib.vido_deconv2x2_bias_act_n(self.ctx.h, C.c_void_p(x.contiguous().data_ptr()), C.c_void_p(conv._dc_w.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
+                                                               C.c_void_p(out.data_ptr()), n, cin, cout, H, W, C.c_float(slope), self._live_ptr(n_live)))
         return out
 
-    def det_order(self, scores, labels, n_det, confidence):
+    def det_order(self, scores, labels, n_det, confidence, count32=False):
         """(order int64 [cap], labels in that order with 0 for slots that fail `scores > confidence and slot < n_det`, number of live slots) — analyse_image_static's tail
-        in one launch (csrc/nets.hip::k_det_order); the order is torch.sort(where(live, scores, -1), descending=True, stable=True)."""
+        in one launch (csrc/nets.hip::k_det_order); the order is torch.sort(where(live, scores, -1), descending=True, stable=True).
+        count32: a fourth result, the count once more as an int32 [1] tensor — the word the mask head's counted launches read (n_live= of the ops below)."""
         assert scores.is_cuda and scores.dtype == torch.float32 and labels.dtype == torch.int64 and n_det.dtype == torch.int32 and scores.is_contiguous() and labels.is_contiguous()
         cap = int(scores.shape[0]); dev = scores.device
         order = torch.empty((cap,), device=dev, dtype=torch.int64); lab = torch.empty((cap,), device=dev, dtype=torch.int64); n_live = torch.empty((), device=dev, dtype=torch.int64)
+        n32 = torch.empty((1,), device=dev, dtype=torch.int32) if count32 else None
         self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_det_order(self.ctx.h, C.c_void_p(scores.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_float(confidence), cap,
-                                                    C.c_void_p(order.data_ptr()), C.c_void_p(lab.data_ptr()), C.c_void_p(n_live.data_ptr())))
-        return order, lab, n_live
+        self.ctx._check(self.ctx.lib.vido_det_order_n(self.ctx.h, C.c_void_p(scores.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_float(confidence), cap,
+                                                      C.c_void_p(order.data_ptr()), C.c_void_p(lab.data_ptr()), C.c_void_p(n_live.data_ptr()), C.c_void_p(n32.data_ptr()) if count32 else None))
+        return (order, lab, n_live, n32) if count32 else (order, lab, n_live)
 
     def roi_levels(self, boxes, k_min, k_max):
         """LevelMapper of the FPN pooler for boxes [n, 4] f32 -> int32 [n] in 0 .. k_max - k_min, one launch (csrc/nets.hip::k_roi_levels: the torch expression's fp32 operations
@@ -105,8 +115,9 @@ class HipOps:
         self.ctx._check(self.ctx.lib.vido_roi_levels(self.ctx.h, C.c_void_p(boxes.data_ptr()), n, C.c_float(k_min), C.c_float(k_max), C.c_void_p(out.data_ptr())))
         return out
 
-    def mask_logit_select(self, feat, conv, labels):
-        """sigmoid(conv(feat))[arange(n), labels][:, None] for a 1x1 `conv` (the mask head's logits layer) computing only each detection's own class channel (csrc/nets.hip)."""
+    def mask_logit_select(self, feat, conv, labels, n_live=None):
+        """sigmoid(conv(feat))[arange(n), labels][:, None] for a 1x1 `conv` (the mask head's logits layer) computing only each detection's own class channel (csrc/nets.hip).
+        n_live (one int32 device word): the slots behind it come out 0 and their features are not read."""
         assert feat.is_cuda and feat.is_contiguous() and feat.dtype == torch.float32 and labels.dtype == torch.int64 and labels.is_contiguous()
         n, c, H, W = feat.shape; classes = int(conv.weight.shape[0])
         w = conv.weight.reshape(classes, c)
@@ -114,8 +125,8 @@ class HipOps:
             w = w.contiguous()
         out = torch.empty((n, 1, H, W), device=feat.device, dtype=torch.float32)
         self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_logit_select(self.ctx.h, C.c_void_p(feat.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(conv.bias.data_ptr()) if conv.bias is not None else None,
-                                                            C.c_void_p(labels.data_ptr()), C.c_void_p(out.data_ptr()), int(n), int(c), int(H * W), classes))
+        self.ctx._check(self.ctx.lib.vido_mask_logit_select_n(self.ctx.h, C.c_void_p(feat.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(conv.bias.data_ptr()) if conv.bias is not None else None,
+                                                            C.c_void_p(labels.data_ptr()), C.c_void_p(out.data_ptr()), int(n), int(c), int(H * W), classes, self._live_ptr(n_live)))
         return out
 
     def bias_res_act_(self, x, bias, res, slope):
@@ -348,9 +359,10 @@ class HipOps:
                                                                 C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope), int(form)))
         return out
 
-    def wino3x3_conv(self, conv, x, slope, weight=None, bias=None):
+    def wino3x3_conv(self, conv, x, slope, weight=None, bias=None, n_live=None):
         """The convolution `conv` (nn.Conv2d, or the folded weight / bias given) + bias + activation through wino3x3_bias_act when the layer has that form, else None.  The
-        packed weight is cached on the module and rebuilt when the weight tensor changes (a checkpoint loaded later)."""
+        packed weight is cached on the module and rebuilt when the weight tensor changes (a checkpoint loaded later).
+        n_live (one int32 device word): the direct split-fp16 kernel computes the first n_live images only and never reads the others; the fp32 Winograd route computes all."""
         w = conv.weight if weight is None else weight
         b = conv.bias if bias is None and weight is None else bias
         if (tuple(w.shape[2:]) != (3, 3) or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.groups != 1
@@ -370,7 +382,7 @@ class HipOps:
             key = (w.data_ptr(), w._version, str(x.device))
             if getattr(conv, "_c3h_key", None) != key:
                 conv._c3h_w = pack_conv3x3_h(w).to(x.device); conv._c3h_key = key
-            return self.conv3x3_h_bias_act(x.contiguous(), conv._c3h_w, b, int(w.shape[0]), slope)
+            return self.conv3x3_h_bias_act(x.contiguous(), conv._c3h_w, b, int(w.shape[0]), slope, n_live)
         form = self.wino3x3_form(x.shape[0], w.shape[1], w.shape[0], x.shape[2], x.shape[3])
         key = (w.data_ptr(), w._version, str(x.device))
         if getattr(conv, "_wino_key", None) != key:
@@ -379,16 +391,17 @@ class HipOps:
             conv._wino_u[form] = pack_wino3x3(w, form).to(x.device)
         return self.wino3x3_bias_act(x.contiguous(), conv._wino_u[form], b, int(w.shape[0]), slope, form)
 
-    def conv3x3_h_bias_act(self, x, w_packed, bias, cout, slope):
-        """leaky_relu(conv2d(x, w, stride 1, padding 1) + bias, slope) as one direct split-fp16 launch (csrc/conv3x3h.hip); w_packed = pack_conv3x3_h(w)."""
+    def conv3x3_h_bias_act(self, x, w_packed, bias, cout, slope, n_live=None):
+        """leaky_relu(conv2d(x, w, stride 1, padding 1) + bias, slope) as one direct split-fp16 launch (csrc/conv3x3h.hip); w_packed = pack_conv3x3_h(w).
+        n_live (one int32 device word): only the first n_live images are read and written (vido_conv3x3_h_bias_act_n); the rest of the result is uninitialised."""
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
         N, cin, H, W = x.shape
         assert w_packed.dtype == torch.int16 and w_packed.numel() == 2 * cout * ((cin + 15) // 16 * 16 * 9 + 1), "conv3x3_h: weight not packed by pack_conv3x3_h for this layer"
         out = torch.empty((N, cout, H, W), device=x.device, dtype=torch.float32)
         self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * N * cout * cin * 9 * H * W
         self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_conv3x3_h_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                                             C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope)))
+        self.ctx._check(self.ctx.lib.vido_conv3x3_h_bias_act_n(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
+                                                               C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope), self._live_ptr(n_live)))
         return out
 
     def fc_h(self, x, w_packed, bias, outs, slope=1.0):
@@ -613,8 +626,9 @@ class HipOps:
         self.ctx._check(self.ctx.lib.vido_nchw_to_nhwc(self.ctx.h, C.c_void_p(x.data_ptr()), B, Cc, H, W, C.c_void_p(out.data_ptr())))
         return out
 
-    def roi_align_fpn_nhwc(self, feats_nhwc, boxes, level, output_size, scales, sampling_ratio):
-        """Pooler.forward over channels-last maps [1,H,W,C] (to_nhwc of the 4 FPN maps, made once per frame)."""
+    def roi_align_fpn_nhwc(self, feats_nhwc, boxes, level, output_size, scales, sampling_ratio, n_live=None):
+        """Pooler.forward over channels-last maps [1,H,W,C] (to_nhwc of the 4 FPN maps, made once per frame).  n_live (one int32 device word): only the first n_live boxes
+        are pooled (vido_roi_align_fpn_nhwc_n); the other rows of the result are uninitialised."""
         n = boxes.shape[0]; ph, pw = output_size; Cc = feats_nhwc[0].shape[3]
         out = torch.empty((n, Cc, ph, pw), device=boxes.device, dtype=torch.float32)
         if n == 0:
@@ -623,8 +637,8 @@ class HipOps:
         fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats_nhwc]); Hs = (C.c_int * 4)(*[f.shape[1] for f in feats_nhwc]); Ws = (C.c_int * 4)(*[f.shape[2] for f in feats_nhwc])
         sc = (C.c_float * 4)(*[float(x) for x in scales])
         self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_roi_align_fpn_nhwc(self.ctx.h, fp, Hs, Ws, sc, Cc, C.c_void_p(boxes.data_ptr()), C.c_void_p(level.data_ptr()), n, ph, pw, sampling_ratio,
-                                                             C.c_void_p(out.data_ptr())))
+        self.ctx._check(self.ctx.lib.vido_roi_align_fpn_nhwc_n(self.ctx.h, fp, Hs, Ws, sc, Cc, C.c_void_p(boxes.data_ptr()), C.c_void_p(level.data_ptr()), n, ph, pw, sampling_ratio,
+                                                               C.c_void_p(out.data_ptr()), self._live_ptr(n_live)))
         return out
 
     def mask_label_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1):
