@@ -419,8 +419,14 @@ int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_pack
  * residual [2][h][w] or NULL, y [2][h][w]: f32 DEVICE tensors. */
 int vido_conv_kxk_c2(vido_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* y, int cin, int k, int h, int w_);
 /* 1x1 convolution with FEW input channels (even, <= 256; cout <= 256) + bias + residual + leaky ReLU for one image, no LDS: LiteFlowNet's netFeat layers
- * (layers.py:99, 125, 140), the detector's layer1.  w_packed: element (co, k) at [co / 32][k / 2][32 * (k & 1) + co % 32], cout padded to 32 with zeros. */
+ * (layers.py:99, 125, 140), the detector's layer1 and RPN heads.  w_packed: element (co, k) at [co / 32][k / 2][32 * (k & 1) + co % 32], cout padded to 32 with zeros.
+ * cout <= 32: 16 k-pairs requested ahead of the matrix instructions; VIDO_SKINNY_DEPTH=4 | 8 | 16 (read per call) selects the depth, every depth gives the same bits. */
 int vido_conv1x1_skinny(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, long long hw, float slope);
+/* The detector's stem in one launch (csrc/stem.hip): y = max_pool2d(relu(conv2d(x, w, stride 2, padding 3) + bias), 3, 2, 1) for one image, 7x7 kernel, 3 -> 64 channels.
+ * x [3][h][w], bias [64], y [64][hp][wp] with hc = (h - 1) / 2 + 1, hp = (hc - 1) / 2 + 1 (likewise w): f32 DEVICE tensors.  w_packed [2][84][64]: element (co, c, dy, dx)
+ * of the weight at [co / 32][(c * 7 + dx) * 4 + dy / 2][32 * (dy & 1) + co % 32], the dy = 7 entries zero (nets/ops.py::pack_stem7x7).  fp32 matrix instructions, fp32
+ * accumulation; the convolution's output never reaches memory.  Enqueues on the adopted stream; capturable. */
+int vido_stem7x7s2_pool(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int h, int w);
 
 /* k x k convolution (7x7, 5x5, 3x3, 7x1, 1x7, 5x1, 1x5, 1x1; strides 1-4; zero padding) + bias + leaky ReLU as a direct implicit GEMM on the fp32 matrix pipe, one launch
  * (csrc/convdirect.hip): the layers of LiteFlowNet that the library ran as im2col / transposes + GEMM + a bias pass — the 7x7 stem, the stride-2 3x3 convolutions of the

@@ -73,7 +73,11 @@ __global__ __launch_bounds__(256) void k_conv_kxk_c2(const float* __restrict__ x
 // order (lane = position & 31 + 32 * channel parity), the weights are packed in operand order [32-channel block][k-pair][64 lanes] and stay in L1 / L2; bias and the
 // activation are applied in the accumulators, a register is a 128-byte line of one output channel.
 typedef float f32x16s __attribute__((ext_vector_type(16)));
-template <int CB, bool RES>
+// D: the k-pairs a wave requests together.  For D > 4 the batch behind the one in the matrix instructions is requested BEFORE them, so D .. 2 D pairs (256 (1 + CB) bytes each) are
+// in flight per wave: with few output channels (the RPN's heads: 256 -> 15 at up to 200 x 272, CB = 1) the kernel is bound by loads in flight, not by bytes or matrix time —
+// D = 4 left ~1 KB per wave outstanding over 32 dependent round trips.  The accumulation order (k-pairs ascending into one accumulator set) does not depend on D: every depth
+// gives the same bits.
+template <int CB, bool RES, int D>
 __global__ __launch_bounds__(256) void k_conv1x1_skinny(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias, const float* __restrict__ res,
                                                         float* __restrict__ y, int Cin, int Cout, long long HW, float slope, unsigned xbytes, unsigned wbytes)
 {
@@ -93,21 +97,35 @@ __global__ __launch_bounds__(256) void k_conv1x1_skinny(const float* __restrict_
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, wbytes, 0x00020000);
     const unsigned xvo = 4u * (unsigned)((lane >> 5) * HW + p), wvo = 4u * (unsigned)lane;
     const unsigned hw8 = 8u * (unsigned)HW;
-    for (int kp0 = 0; kp0 < nkp; kp0 += 4) {                                  // four k-pairs at a time: their loads are in flight together
-        float b[4], a[4][CB];
+    float b[D], a[D][CB], bn[D], an[D][CB];
+    auto fetch = [&](int kp0, float (&fb)[D], float (&fa)[D][CB]) {           // (k-pairs past the end repeat the last one: loaded, not accumulated)
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
+        for (int u = 0; u < D; u++) {
             const int kp = min(kp0 + u, nkp - 1);
-            b[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, xvo, hw8 * (unsigned)kp, 0));
+            fb[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, xvo, hw8 * (unsigned)kp, 0));
 #pragma unroll
-            for (int cb = 0; cb < CB; cb++) a[u][cb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wr, wvo, 256u * (unsigned)(cb * nkp + kp), 0));
+            for (int cb = 0; cb < CB; cb++) fa[u][cb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wr, wvo, 256u * (unsigned)(cb * nkp + kp), 0));
         }
+    };
+    constexpr bool AHEAD = D > 4;                                             // (D = 4 is the form as it was: request four pairs, wait, accumulate)
+    if (AHEAD) fetch(0, b, a);
+    for (int kp0 = 0; kp0 < nkp; kp0 += D) {
+        if (!AHEAD) fetch(kp0, b, a);
+        else if (kp0 + D < nkp) fetch(kp0 + D, bn, an);                       // (uniform branch)
 #pragma unroll
-        for (int u = 0; u < 4; u++)
+        for (int u = 0; u < D; u++)
             if (kp0 + u < nkp) {
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][cb], b[u], acc[cb], 0, 0, 0);
             }
+        if (AHEAD) {
+#pragma unroll
+            for (int u = 0; u < D; u++) {
+                b[u] = bn[u];
+#pragma unroll
+                for (int cb = 0; cb < CB; cb++) a[u][cb] = an[u][cb];
+            }
+        }
     }
     if (p0 + (lane & 31) < HW) {
 #pragma unroll
@@ -162,11 +180,18 @@ int vido_conv1x1_skinny(vido_ctx* ctx, const float* x, const float* w_packed, co
     const dim3 grid((unsigned)((hw + 127) / 128)), blk(256);
     const int cbn = (cout + 31) / 32;
     const unsigned xb = (unsigned)(4ll * cin * hw), wb = (unsigned)(4ll * cbn * 32 * cin);
-#define SK_LAUNCH(CBV) { if (residual) hipLaunchKernelGGL((k_conv1x1_skinny<CBV, true>), grid, blk, 0, st, x, w_packed, bias, residual, y, cin, cout, hw, slope, xb, wb); \
-                         else hipLaunchKernelGGL((k_conv1x1_skinny<CBV, false>), grid, blk, 0, st, x, w_packed, bias, residual, y, cin, cout, hw, slope, xb, wb); }
+    // VIDO_SKINNY_DEPTH=4 | 8 | 16: the depth of the one-block form (cout <= 32), read per call; unset = 16 (profiles/r13/detector_stem_rpn.txt).  The wider forms keep 4.
+    int depth = 16;
+    if (const char* e = getenv("VIDO_SKINNY_DEPTH")) {
+        depth = atoi(e);
+        if (depth != 4 && depth != 8 && depth != 16) return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1_skinny: VIDO_SKINNY_DEPTH=%s (4, 8 or 16)", e);
+    }
+#define SK_LAUNCH(CBV, DV) { if (residual) hipLaunchKernelGGL((k_conv1x1_skinny<CBV, true, DV>), grid, blk, 0, st, x, w_packed, bias, residual, y, cin, cout, hw, slope, xb, wb); \
+                             else hipLaunchKernelGGL((k_conv1x1_skinny<CBV, false, DV>), grid, blk, 0, st, x, w_packed, bias, residual, y, cin, cout, hw, slope, xb, wb); }
     switch (cbn) {
-    case 1: SK_LAUNCH(1) break; case 2: SK_LAUNCH(2) break; case 3: SK_LAUNCH(3) break; case 4: SK_LAUNCH(4) break;
-    case 5: SK_LAUNCH(5) break; case 6: SK_LAUNCH(6) break; case 7: SK_LAUNCH(7) break; default: SK_LAUNCH(8) break;
+    case 1: if (depth == 4) SK_LAUNCH(1, 4) else if (depth == 8) SK_LAUNCH(1, 8) else SK_LAUNCH(1, 16) break;
+    case 2: SK_LAUNCH(2, 4) break; case 3: SK_LAUNCH(3, 4) break; case 4: SK_LAUNCH(4, 4) break;
+    case 5: SK_LAUNCH(5, 4) break; case 6: SK_LAUNCH(6, 4) break; case 7: SK_LAUNCH(7, 4) break; default: SK_LAUNCH(8, 4) break;
     }
 #undef SK_LAUNCH
     HIP_TRY(ctx, hipGetLastError());

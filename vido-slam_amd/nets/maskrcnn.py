@@ -127,6 +127,12 @@ class _Stem(nn.Module):                    # resnet.py:375-395
 
     def forward(self, x):
         if self._ep is not None and x.is_cuda:
+            ops = getattr(self._ep, "__self__", None)
+            if x.shape[0] == 1 and hasattr(ops, "stem7x7s2_pool_conv") and not os.environ.get("VIDO_NO_STEM_FUSED"):
+                # convolution + bias + ReLU + max-pool as ONE launch: the 64-channel half-resolution map (55.7 MB at 800 x 1088) never reaches memory (csrc/stem.hip)
+                y = ops.stem7x7s2_pool_conv(self, self._w1, self._b1, x)
+                if y is not None:
+                    return y
             return F.max_pool2d(self._ep(F.conv2d(x, self._w1, None, 2, 3), self._b1, None, 0.0), 3, 2, 1)
         return F.max_pool2d(F.relu(self.bn1(self.conv1(x))), 3, 2, 1)
 

@@ -340,6 +340,27 @@ class HipOps:
             conv._c1s_w = pack_conv1x1_skinny(w).to(x.device); conv._c1s_key = key
         return self.conv1x1_skinny(x, conv._c1s_w, conv.bias, cout, slope)
 
+    def stem7x7s2_pool(self, x, w_packed, bias):
+        """max_pool2d(relu(conv2d(x, w, None, 2, 3) + bias), 3, 2, 1) for one image, 7x7, 3 -> 64 channels, as ONE launch whose convolution output stays on the chip
+        (csrc/stem.hip); w_packed = pack_stem7x7(w) on the device."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] == 1 and x.shape[1] == 3 and tuple(w_packed.shape) == (2, 84, 64) and bias.numel() == 64
+        x = x.contiguous(); H, W = int(x.shape[2]), int(x.shape[3])
+        Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        out = torch.empty((1, 64, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1), device=x.device, dtype=torch.float32)
+        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * 64 * 147 * Hc * Wc
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_stem7x7s2_pool(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()), H, W))
+        return out
+
+    def stem7x7s2_pool_conv(self, mod, w, bias, x):
+        """The same for a folded stem weight `w` [64, 3, 7, 7] / `bias` [64]; None when they are not of that form.  Packed weight cached on `mod`, rebuilt when `w` changes."""
+        if tuple(w.shape) != (64, 3, 7, 7) or bias is None or bias.numel() != 64 or not x.is_cuda or x.shape[0] != 1 or x.shape[1] != 3 or x.dtype != torch.float32 or w.dtype != torch.float32:
+            return None
+        key = (w.data_ptr(), w._version, str(x.device))
+        if getattr(mod, "_stem_key", None) != key:
+            mod._stem_w = pack_stem7x7(w).to(x.device); mod._stem_b = bias.detach().to(x.device).contiguous(); mod._stem_key = key
+        return self.stem7x7s2_pool(x, mod._stem_w, mod._stem_b)
+
     def wino3x3_supported(self, cin, cout, H, W):
         return bool(self.ctx.lib.vido_wino3x3_supported(int(cin), int(cout), int(H), int(W)))
 
@@ -949,6 +970,15 @@ def pack_conv1x1_skinny(w):
     cop = (cout + 31) // 32 * 32
     wz = w.detach().reshape(cout, cin).new_zeros((cop, cin)); wz[:cout] = w.detach().reshape(cout, cin)
     return wz.reshape(cop // 32, 32, cin // 2, 2).permute(0, 2, 3, 1).contiguous().reshape(cop // 32, cin // 2, 64)
+
+
+def pack_stem7x7(w):
+    """Stem weight [64, 3, 7, 7] -> the operand order of csrc/stem.hip::k_stem7x7s2_pool, [2][84][64]: K runs over (plane c, column dx, row pair j) and the two k of a pair are
+    the rows dy = 2 j and 2 j + 1 (dy = 7: zeros); element (co, c, dy, dx) at [co / 32][(c * 7 + dx) * 4 + dy / 2][32 * (dy & 1) + co % 32]."""
+    assert tuple(w.shape) == (64, 3, 7, 7)
+    wz = w.detach().new_zeros((64, 3, 8, 7)); wz[:, :, :7] = w.detach()
+    # [cb][co][c][j][par][dx] -> [cb][c][dx][j][par][co]
+    return wz.reshape(2, 32, 3, 4, 2, 7).permute(0, 2, 5, 3, 4, 1).contiguous().reshape(2, 84, 64)
 
 
 def pack_gconv3x3(w, groups):
