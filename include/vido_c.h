@@ -212,6 +212,26 @@ int vido_frame_propagate_mask(vido_ctx* ctx, int slot_last, int slot_cur, int32_
  * n < 0: VIDO_E_INVALID; n > 127: VIDO_E_CAPACITY. */
 int vido_mask_associate(vido_ctx* ctx, const int32_t* prev /* NULL ok */, const int32_t* cur, int H, int W, const int64_t* classes /* NULL ok */, int n, int hold,
                         int32_t* state /* DEVICE i32[768], in/out */, int32_t* out, int32_t* lut_out /* i32[256], NULL ok */, int32_t* stats_out /* i32[4], NULL ok */);
+/* Split a class label image into instances: connected-component labelling (no reference counterpart: the reference's label image holds one value per class).  ALL
+ * pointers are DEVICE pointers: mask i32 [H,W], out i32 [H,W] (may be mask itself; EVERY pixel is written), classes_out i64 [cap] or NULL, area_out i32 [cap] or NULL,
+ * stats_out i32 [4] or NULL.
+ *   foreground a pixel with mask > 0; any positive i32 value is a class; anything <= 0 is background.
+ *   component  a maximal set of foreground pixels of EQUAL value joined by `connectivity` (4 or 8) neighbour steps; touching pixels of different values never join.
+ *              Its anchor is its smallest raster index y * W + x, its area its pixel count.
+ *   drop       components with area < min_area are dropped (min_area <= 1 keeps all).
+ *   order      the survivors in ascending anchor order are k = 0, 1, ...; k < cap is KEPT: out = id_base + 1 + k on its pixels, classes_out[k] = its value,
+ *              area_out[k] = its area; the rest are LEFT OUT: out = 0 (as on dropped components and background).  classes_out / area_out entries >= kept: 0.
+ *   stats_out  components found, dropped for area, left out for cap, kept.
+ * With id_base 0 and cap 127 `out` and `classes_out` are what vido_mask_associate takes as cur and classes.  Bit-exact against tests/refimpl/mask_components_np.py whatever
+ * the execution order (integer minima and sums).  One memset and seven launches on the context's adopted stream (vido_set_stream), no host synchronisation; the context's
+ * planes (8 bytes per pixel of its width x height) are allocated by the FIRST call, so one call comes before a stream capture.  One set of planes per context: calls on
+ * different streams must not overlap.  mask or out NULL, out overlapping mask without being mask, connectivity not 4 or 8, H or W outside [1, 4095], H * W > width * height
+ * of the context, id_base < 0 or cap < 1: VIDO_E_INVALID; id_base + cap > 254: VIDO_E_CAPACITY. */
+int vido_mask_components(vido_ctx* ctx, const int32_t* mask, int H, int W, int connectivity, int min_area, int id_base, int cap, int32_t* out,
+                         int64_t* classes_out /* i64[cap], NULL ok */, int32_t* area_out /* i32[cap], NULL ok */, int32_t* stats_out /* i32[4], NULL ok */);
+/* The same rule on the tracker's slot: the mask of `slot` is split in place, on the context's own stream (after vido_frame_upload of the slot; with on_device = 2 that is
+ * the buffer the slot adopted).  stats_out: HOST, 4 x i32; NULL: nothing is waited for.  A slot outside [0, vido_track_slots()): VIDO_E_INVALID; the other refusals as above. */
+int vido_frame_split_mask(vido_ctx* ctx, int slot, int connectivity, int min_area, int id_base, int cap, int32_t* stats_out /* HOST i32[4], NULL ok */);
 /* mask / depth / flow of slot `slot` at ((int)x, (int)y) of n points (host xy in, host values out; points outside the image give 0): the only map data the host-side
  * renew stages need (vido_renew_*_sampled) — a few thousand points instead of three whole maps.  Inside means 0 <= (int)x < width and 0 <= (int)y < height: x in (-1, 0)
  * truncates to column 0.  Capacity: n <= 2 * max(2 * n_features + 256, ceil(width / 4) * ceil(height / 4)); a larger n is VIDO_E_INVALID.  n == 0 is a successful no-op. */
@@ -655,7 +675,13 @@ const char* vido_system_last_error(const vido_system* sys);      /* NULL sys: er
  * n_image: StopFrame = n_image - 1.  Tcw_out: row-major 4x4 world->camera pose of this frame (identity for the first).
  * Settings key Mask.PropagateMissing: 1 (default 0): `mask` (here, and mask_dev of the device form) may be NULL on every frame but the first of a sequence; the frame's mask is
  * then the previous frame's, warped through the previous frame's flow with the nearer pre-scaled depth winning a collision (vido_frame_propagate_mask), before any list is
- * built from it; vido_system_stats.mask_propagated reports it.  With the key at 0 a NULL mask is VIDO_E_INVALID as before. */
+ * built from it; vido_system_stats.mask_propagated reports it.  With the key at 0 a NULL mask is VIDO_E_INVALID as before.
+ * Settings keys Mask.SplitInstances: 1 (default 0) and Mask.MinInstanceArea (default 1): on every frame that arrives WITH a mask, the tracker's own copy of the mask is
+ * split into its 8-connected components of equal value with at least that many pixels (vido_frame_split_mask, at most 127 per frame, in anchor order) after the upload
+ * and before any list is built from it, so that the objects of one class in a class image (the reference node's sum of mask * class index, a dataset's semantic mask)
+ * are tracked separately.  The id base alternates 0 / 127 per split frame (Tracking::UpdateMask repaints a lost label under its last-frame value); a propagated frame is
+ * not split and keeps its source's ids.  The caller's mask buffer is never written (with zero-copy maps the split goes into a tracker-owned buffer that the slot adopts).
+ * vido_system_mask_split_stats reads the frame's counters.  With the key at 0 nothing changes. */
 int         vido_system_track_rgbd(vido_system* sys, const uint8_t* im, int channels, int width, int height, float* depth, const float* flow,
                                    const int32_t* mask, double timestamp, int n_image, float Tcw_out[16]);
 /* The same with the image (u8, 1 / 3 / 4 interleaved channels) and the three maps already RESIDENT ON THE DEVICE (plain device pointers; depth is rescaled in place on the
@@ -675,6 +701,9 @@ int         vido_system_get_stats(const vido_system* sys, vido_system_stats* out
  * (n_checked: those with a distance, i.e. a seed and a position outside the extractor's edge margin) and how many of them exceeded Verify.MaxHamming (n_rejected).
  * Both 0 with the option off.  (A call of its own: vido_system_stats keeps the layout existing callers see.) */
 int         vido_system_get_verify_stats(const vido_system* sys, int* n_checked, int* n_rejected);
+/* Mask.SplitInstances: 1 — the counters of the last frame's split: components found, dropped for Mask.MinInstanceArea, left out beyond 127, kept.  Zeros when the frame was
+ * not split (the key at 0, or a propagated frame).  (A call of its own: vido_system_stats keeps the layout existing callers see.) */
+int         vido_system_mask_split_stats(const vido_system* sys, int32_t out[4]);
 /* Debug read of the same frame's per-point state, index-aligned with the frame's static list (any array may be NULL): xy [2n] the position that was checked, prev_xy [2n]
  * the last frame's point it came from, xyl [3n] = lrintf(xy / scale[level]) and the seed's level (-1 x 3: no seed), dist [n] (-1: no evidence), rejected [n], seed_desc [32n].
  * *n_out = n (0 with the option off or before the second frame); VIDO_E_CAPACITY if n > cap. */

@@ -194,6 +194,14 @@ public:
     void PropagateMissingMask();
     bool bPropagateMissingMask = false; int nMaskPropagated = 0;
     cv::Mat mPropMaskHost; int32_t* mPropMaskDev[2] = {nullptr, nullptr}; size_t mPropMaskPx = 0;      /* the placeholder mask that goes into the slot (host form) / the slots' own mask buffers (device form) */
+    /* extension (Mask.SplitInstances: 1): every frame that arrives WITH a mask has the slot's mask split into its 8-connected components of equal value of at least
+       Mask.MinInstanceArea pixels (vido_frame_split_mask, at most 127 per frame) after the upload and before UpdateMask and any list, so that same-class objects of a
+       class image track separately.  The id base alternates 0 / 127 per SPLIT frame (UpdateMask repaints a lost label under its last-frame value: it must not meet a
+       live id of this frame); a propagated frame is not split and keeps its source's ids.  The caller's buffers are never written: the host form splits the slot's own
+       copy, the zero-copy device form splits into mPropMaskDev, which the slot adopts.  nMaskSplitStats: found, dropped for area, left out, kept of the last frame; zeros
+       when it was not split.  With the key at 0 (default) nothing changes. */
+    void SplitSlotMask();
+    bool bSplitInstances = false; int nMinInstanceArea = 1, nSplitFrames = 0; int32_t nMaskSplitStats[4] = {0, 0, 0, 0}; int32_t* mSplitStatsDev = nullptr;
 
     enum eTrackingState { NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, OK = 2 };
     enum eDataState { OMD = 1, KITTI = 2, KAIST = 3 };

@@ -51,6 +51,7 @@ struct vido_ctx {
     struct PnpState* pnp = nullptr;
     struct MaskPropState* mprop = nullptr;   // maskprop.hip: key plane + counters of vido_mask_propagate / vido_frame_propagate_mask
     struct MaskAssocState* massoc = nullptr; // maskassoc.hip: count table + lookups of vido_mask_associate
+    struct MaskCCState* mcc = nullptr;       // maskcc.hip: parent plane, area / id plane and row counts of vido_mask_components / vido_frame_split_mask
     struct BaWin* bawin = nullptr;     // bawin.hip: the device-resident local-BA window
     void* detpost_buf = nullptr; size_t detpost_cap = 0; unsigned long long detpost_sig = 0;   // detpost.hip: scratch of the RPN selection (keys, histograms, state)
     void* rccl_comm = nullptr;         // ncclComm_t of vido_rccl_init (rccl.cpp): the sharded BA's all-reduce on this context's stream
@@ -85,9 +86,10 @@ int orb_mirror_async(vido_ctx* ctx, int nf);
 struct OrbView { const vido_keypoint* d_kpf; const int* d_nkp; int row_cap; const vido_keypoint* h_kpf; const uint8_t* h_descf; const int* h_frame_beg; };
 OrbView orb_view(vido_ctx* ctx);
 void track_state_destroy(vido_ctx* ctx);
-int track_slot_maps(vido_ctx* ctx, int slot, float** depth, float** flow, int32_t** mask, int* W, int* H);      // (track.hip) for maskprop.hip
+int track_slot_maps(vido_ctx* ctx, int slot, float** depth, float** flow, int32_t** mask, int* W, int* H);      // (track.hip) for maskprop.hip, maskcc.hip
 void maskprop_state_destroy(vido_ctx* ctx);
 void maskassoc_state_destroy(vido_ctx* ctx);
+void maskcc_state_destroy(vido_ctx* ctx);
 void ham_state_destroy(vido_ctx* ctx);
 void pose_state_destroy(vido_ctx* ctx);
 void ba_state_destroy(vido_ctx* ctx);

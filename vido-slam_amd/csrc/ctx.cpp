@@ -92,6 +92,7 @@ void vido_destroy(vido_ctx* ctx)
     track_state_destroy(ctx);
     maskprop_state_destroy(ctx);
     maskassoc_state_destroy(ctx);
+    maskcc_state_destroy(ctx);
     ham_state_destroy(ctx);
     pose_state_destroy(ctx);
     ba_state_destroy(ctx);

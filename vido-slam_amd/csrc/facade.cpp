@@ -885,9 +885,10 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
     bVerifyDescriptor = num(kv, "Verify.Descriptor", 0) != 0; nVerifyMaxHamming = (int)num(kv, "Verify.MaxHamming", 70);      // (70: profiles/r8/descriptor_verify.txt)
     g_verify_desc = bVerifyDescriptor;
     bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
+    bSplitInstances = num(kv, "Mask.SplitInstances", 0) != 0; nMinInstanceArea = (int)num(kv, "Mask.MinInstanceArea", 1);
     all_timing.assign(5, 0.f);
 }
-Tracking::~Tracking() { delete mpORBextractorLeft; for (int i = 0; i < 2; i++) if (mPropMaskDev[i]) (void)hipFree(mPropMaskDev[i]); }
+Tracking::~Tracking() { delete mpORBextractorLeft; for (int i = 0; i < 2; i++) if (mPropMaskDev[i]) (void)hipFree(mPropMaskDev[i]); if (mSplitStatsDev) (void)hipFree(mSplitStatsDev); }
 
 // Mask.PropagateMissing: 1 and a frame handed over without a mask (no reference counterpart: the reference segments every frame).  The frame's maps are in slot_cur_ with
 // a placeholder mask; the previous slot's mask is warped through the previous slot's flow into it (vido_frame_propagate_mask: the nearer pre-scaled depth wins a collision)
@@ -898,14 +899,22 @@ void Tracking::PropagateMissingMask()
     nMaskPropagated = 1;
 }
 
+// Mask.SplitInstances: 1 and a frame that came WITH a mask (no reference counterpart: the reference's label image holds one value per class).  The slot's own copy of the
+// mask is split in place into its connected components (vido_frame_split_mask: 8-connected, equal value, at most 127) before UpdateMask and before any list is built from
+// it.  The id base alternates 0 / 127 per split frame, as pipeline.NetNodes.ID_BASES does for the detector's instance image and for the same reason.
+void Tracking::SplitSlotMask()
+{
+    check(vido_frame_split_mask(g_ctx, slot_cur_, 8, nMinInstanceArea, (nSplitFrames & 1) ? 127 : 0, 127, nMaskSplitStats), "frame_split_mask");
+    nSplitFrames++;
+}
 
 cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Mat& imFlow, const cv::Mat& maskSEM_in, const cv::Mat&,
                                 const std::vector<std::vector<float> >&, const double& timestamp, cv::Mat&, const int& nImage)
 {
     const auto t_grab = std::chrono::steady_clock::now();
     StopFrame = nImage - 1; ms_wait_inputs = 0;
-    if (mState == NO_IMAGES_YET) f_id = 0;
-    nMaskPropagated = 0;
+    if (mState == NO_IMAGES_YET) { f_id = 0; nSplitFrames = 0; }
+    nMaskPropagated = 0; memset(nMaskSplitStats, 0, sizeof nMaskSplitStats);
     const bool propagate = bPropagateMissingMask && maskSEM_in.empty();
     if (propagate) {
         if (mState == NO_IMAGES_YET) throw std::runtime_error("GrabImageRGBD: Mask.PropagateMissing: the first frame of a sequence needs a mask");
@@ -923,6 +932,7 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
     // depth pre-scale in place on the caller's buffer (:299-322) + maps resident in the slot
     check(vido_frame_upload(c, slot_cur_, 1, imD.ptr<float>(), imFlow.ptr<float>(), maskSEM.ptr<int32_t>(), 0, &g_tp), "frame_upload");
     if (propagate) PropagateMissingMask();
+    else if (bSplitInstances) SplitSlotMask();
     if (imRGB.channels() == 1) mImGray = imRGB;
     else {                                                     // :327-340 cvtColor: done on the device by the extractor's ingest, which fills mImGray
         if (imRGB.type() != CV_8UC3 && imRGB.type() != CV_8UC4) throw std::runtime_error("GrabImageRGBD: image must be CV_8UC1 / CV_8UC3 / CV_8UC4");
@@ -944,8 +954,8 @@ cv::Mat Tracking::GrabImageRGBDDevice(const void* im_dev, int channels, int widt
 {
     const auto t_grab = std::chrono::steady_clock::now();
     StopFrame = nImage - 1;
-    if (mState == NO_IMAGES_YET) f_id = 0;
-    nMaskPropagated = 0;
+    if (mState == NO_IMAGES_YET) { f_id = 0; nSplitFrames = 0; }
+    nMaskPropagated = 0; memset(nMaskSplitStats, 0, sizeof nMaskSplitStats);
     const bool propagate = bPropagateMissingMask && !mask_dev;
     if (!im_dev || !depth_dev || !flow_dev || (!mask_dev && !propagate) || width < 1 || height < 1 || (channels != 1 && channels != 3 && channels != 4))
         throw std::runtime_error("GrabImageRGBDDevice: device image (1 / 3 / 4 channels), depth, flow and mask pointers expected");
@@ -963,7 +973,7 @@ cv::Mat Tracking::GrabImageRGBDDevice(const void* im_dev, int channels, int widt
     g_tp.dataset = mTestData == OMD ? 0 : (mTestData == KITTI ? 1 : 2); g_tp.depth_map_factor = mDepthMapFactor; g_tp.bf = mbf; g_tp.kaist_scale = mScale;
     g_tp.th_depth_bg = mThDepth; g_tp.th_depth_obj = mThDepthObj; g_tp.dense_step = 4; g_tp.fx = mK.at<float>(0, 0); g_tp.fy = mK.at<float>(1, 1); g_tp.cx = mK.at<float>(0, 2); g_tp.cy = mK.at<float>(1, 2);
     slot_cur_ = (mState == NO_IMAGES_YET) ? 0 : 1 - slot_cur_; g_slot = slot_cur_;
-    if (bPropagateMissingMask && mState == NO_IMAGES_YET) {      // the first frame of a sequence (no slot is in use): the tracker's two mask buffers for frames that come without one — allocated here, never in a later frame
+    if ((bPropagateMissingMask || bSplitInstances) && mState == NO_IMAGES_YET) {      // the first frame of a sequence (no slot is in use): the tracker's two mask buffers for frames that come without one, or whose mask is split — allocated here, never in a later frame
         const size_t px = (size_t)width * height;
         if (px != mPropMaskPx) {
             for (int i = 0; i < 2; i++) { if (mPropMaskDev[i]) (void)hipFree(mPropMaskDev[i]); mPropMaskDev[i] = nullptr; }
@@ -971,13 +981,26 @@ cv::Mat Tracking::GrabImageRGBDDevice(const void* im_dev, int channels, int widt
             for (int i = 0; i < 2; i++) if (hipMalloc((void**)&mPropMaskDev[i], px * 4) != hipSuccess) throw std::runtime_error("GrabImageRGBDDevice: no device memory for the propagated masks");
             mPropMaskPx = px;
         }
+        if (bSplitInstances && !mSplitStatsDev && hipMalloc((void**)&mSplitStatsDev, 16) != hipSuccess) throw std::runtime_error("GrabImageRGBDDevice: no device memory for the split counters");
     }
     if (propagate) {      // the slot's mask for this frame: the buffer of this slot's parity (a zero-copy slot adopts it; the previous slot may still refer to the other)
         if ((size_t)width * height != mPropMaskPx) throw std::runtime_error("GrabImageRGBDDevice: Mask.PropagateMissing: the frame size changed inside a sequence");
         mask_dev = mPropMaskDev[slot_cur_ & 1];
     }
+    const bool split = bSplitInstances && !propagate, split_adopted = split && detail::g_zero_copy_maps;
+    if (split_adopted) {      // zero-copy maps: the slot would adopt the CALLER's mask, which the split must not write — it goes into the tracker's buffer of this slot's parity, and the slot adopts that
+        if ((size_t)width * height != mPropMaskPx) throw std::runtime_error("GrabImageRGBDDevice: Mask.SplitInstances: the frame size changed inside a sequence");
+        check(vido_mask_components(c, (const int32_t*)mask_dev, height, width, 8, nMinInstanceArea, (nSplitFrames & 1) ? 127 : 0, 127, mPropMaskDev[slot_cur_ & 1], nullptr, nullptr, mSplitStatsDev), "mask_components");
+        nSplitFrames++;
+        mask_dev = mPropMaskDev[slot_cur_ & 1];
+    }
     check(vido_frame_upload(c, slot_cur_, 1, depth_dev, flow_dev, (const int32_t*)mask_dev, detail::g_zero_copy_maps ? 2 : 1, &g_tp), "frame_upload");      // device -> slot (no PCIe), or the slot adopts the buffers; depth pre-scale in place
     if (propagate) PropagateMissingMask();
+    else if (split_adopted) {      // (the context has no adopted stream: the split ran on the tracker's own)
+        check(vido_synchronize(c), "synchronize");
+        if (hipMemcpy(nMaskSplitStats, mSplitStatsDev, 16, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("GrabImageRGBDDevice: reading the split counters failed");
+    }
+    else if (split) SplitSlotMask();
     mImGray = cv::Mat(height, width, CV_8UC1);                  // size carrier: the pixels stay on the device (ORBextractor::SetDeviceSource)
     mpORBextractorLeft->SetDeviceSource(im_dev, channels, mbRGB);
     mDepthMap = cv::Mat(); mFlowMap = cv::Mat(); mSegMap = cv::Mat();
@@ -1548,6 +1571,15 @@ int vido_system_get_stats(const vido_system* s, vido_system_stats* o)
     if (T->all_timing.size() >= 5) { o->ms_cam_pose = T->all_timing[1]; o->ms_obj_tracking = T->all_timing[2]; o->ms_renew = T->all_timing[4]; }
     o->ms_obj_motion = T->ms_obj_motion_sum;
     o->ms_local_ba = M && !M->fLBA_time.empty() && T->f_id > 1 ? M->fLBA_time.back() : 0.f;
+    return VIDO_OK;
+}
+
+int vido_system_mask_split_stats(const vido_system* s, int32_t out[4])
+{
+    if (!s || !s->inited || !out) return VIDO_E_INVALID;
+    memset(out, 0, 4 * sizeof(int32_t));
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) memcpy(out, T->nMaskSplitStats, 4 * sizeof(int32_t));
     return VIDO_OK;
 }
 

@@ -66,6 +66,8 @@ def load_library():
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.vido_mask_associate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vido_mask_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vido_frame_split_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -219,6 +221,14 @@ class Context:
         st = (C.c_int32 * 3)()
         self._check(self.lib.vido_frame_propagate_mask(self.h, int(slot_last), int(slot_cur), st))
         return int(st[0]), int(st[1]), int(st[2])
+
+    def frame_split_mask(self, slot, connectivity=8, min_area=1, id_base=0, cap=127):
+        """vido_frame_split_mask: the mask of `slot` is split in place into its connected components of equal value (ids id_base + 1 + k in anchor order, at most `cap`), on
+        the context's own stream.  Returns (found, dropped for area, left out for cap, kept); the rule is include/vido_c.h's, the numpy statement
+        tests/refimpl/mask_components_np.py."""
+        st = (C.c_int32 * 4)()
+        self._check(self.lib.vido_frame_split_mask(self.h, int(slot), int(connectivity), int(min_area), int(id_base), int(cap), st))
+        return int(st[0]), int(st[1]), int(st[2]), int(st[3])
 
     def hamming_match_device(self, a_ptr, na, b_ptr, nb, idx_ptr, dist_ptr):
         self._check(self.lib.vido_hamming_match(self.h, C.c_void_p(a_ptr), na, C.c_void_p(b_ptr), nb, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), 1))

@@ -766,6 +766,50 @@ class HipOps:
         self.ctx._check(self.ctx.lib.vido_mask_associate(self.ctx.h, ptr(prev), ptr(cur), H, W, ptr(classes), n, int(hold), ptr(state), ptr(out), ptr(lut), ptr(stats)))
         return out
 
+    def mask_components(self, mask, connectivity=8, min_area=1, id_base=0, cap=127, out=None, classes=None, areas=None, stats=None):
+        """vido_mask_components on device tensors: mask int32 [H,W], a class label image (> 0: a class, <= 0: background) -> the instance image, int32 [H,W] (`out`, which
+        may be `mask`, or a new tensor).  Every connected component (4 or 8 neighbours) of pixels of EQUAL value with at least min_area pixels gets, in the order of its
+        first pixel in raster order, the id id_base + 1 + k; the first `cap` are kept, everything else is 0.  classes: int64 [>= cap] that receives the value of component
+        k (0 behind the kept ones), areas: int32 [>= cap] the pixel counts, stats: int32 [>= 4] (found, dropped for area, left out for cap, kept).  With id_base 0 and
+        cap 127 the result and `classes` are mask_associate's cur and classes.  Enqueued on torch's current stream, nothing is waited for; the first call of a context
+        allocates, so it comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out overlapping mask (other than being mask) raise."""
+        from ..host import VidoError
+        def bad(why):
+            raise VidoError(-1, "mask_components: " + why)
+        for name, t, dt in (("mask", mask, torch.int32), ("out", out, torch.int32), ("classes", classes, torch.int64), ("areas", areas, torch.int32), ("stats", stats, torch.int32)):
+            if t is None:
+                if name == "mask":
+                    bad("mask is required")
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != mask.device:
+                bad("%s is on another device than mask" % name)
+        if mask.dim() != 2:
+            bad("mask must be [H, W]")
+        H, W = int(mask.shape[0]), int(mask.shape[1])
+        if out is None:
+            out = torch.empty((H, W), device=mask.device, dtype=torch.int32)
+        elif tuple(out.shape) != (H, W):
+            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
+        if out.data_ptr() != mask.data_ptr() and out.data_ptr() < mask.data_ptr() + 4 * H * W and mask.data_ptr() < out.data_ptr() + 4 * H * W:
+            bad("out aliases mask")
+        cap = int(cap)
+        for name, t in (("classes", classes), ("areas", areas)):
+            if t is not None and t.numel() < cap:
+                bad("%s holds %d elements, cap = %d" % (name, t.numel(), cap))
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_mask_components(self.ctx.h, ptr(mask), H, W, int(connectivity), int(min_area), int(id_base), cap, ptr(out), ptr(classes), ptr(areas),
+                                                          ptr(stats)))
+        return out
+
     def mask_instance_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, id_base=None, areas=False):
         """Masker + instance image (vido_mask_instance_image): mask_label_image's inputs in priority order (highest first) -> [H,W] u8 = id_base + 1 + index of the first
         detection with a nonzero label whose pasted mask covers the pixel, 0 elsewhere.  id_base: None (0), an int, or a DEVICE int32 tensor of one element that the kernel

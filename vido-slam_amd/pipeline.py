@@ -128,7 +128,12 @@ class InstanceIds:
     with inst_mask (HipOps.mask_associate): an instance takes over the id it overlaps with IoU > 1/2, any other gets a fresh id; an id the detector misses stays in the
     image at its flow-predicted place for `hold` detector frames.  propagated(flow): a frame without a detector run, the last image warped through the flow.  Both return
     the frame's mask, one of the two images: valid until the next call.  mask is the image handed over last (writable: the next call starts from it),
-    classes_by_id an int64 [255] device tensor refreshed in stream order by detected(): [id - 1] is the class of id, 0 when the id is neither live nor held."""
+    classes_by_id an int64 [255] device tensor refreshed in stream order by detected(): [id - 1] is the class of id, 0 when the id is neither live nor held.
+
+    from_classes(class_mask, flow=None, connectivity=8, min_area=1): the same for a CLASS label image (the reference node's sum of mask * class index, a dataset's semantic
+    mask; int32 HxW, > 0 a class): it is split into its connected components of equal value (HipOps.mask_components, csrc/maskcc.hip, INTEGRATION.md §34: id base 0, at
+    most 127, in the order of their first pixel) into an image the object owns, and that image and its classes go through detected().  split_stats (int32 [4]: found,
+    dropped for area, left out, kept) are the counters of the last split."""
 
     def __init__(self, ops, h, w, hold=0):
         import numbers as _numbers
@@ -144,6 +149,11 @@ class InstanceIds:
         # the first call of either op allocates in its context (key plane, count table): here, so that a frame — or a capture — never does
         ops.mask_propagate(self._img[0], torch.zeros((self.h, self.w, 2), dtype=torch.float32, device=dev), out=self._img[1])
         ops.mask_associate(None, self._img[1], self.state, n=0, hold=self.hold, out=self._img[0], stats=self.stats)
+        # from_classes' instance image, its classes and counters; the first mask_components call allocates the context's planes: here as well
+        self._inst = torch.zeros((self.h, self.w), dtype=torch.int32, device=dev)
+        self._inst_classes = torch.zeros((127,), dtype=torch.int64, device=dev)
+        self.split_stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+        ops.mask_components(self._img[0], out=self._inst, classes=self._inst_classes, stats=self.split_stats)
 
     @property
     def mask(self):
@@ -165,6 +175,10 @@ class InstanceIds:
             out = self.ops.mask_associate(other, inst_mask, self.state, classes=classes, hold=self.hold, out=last, stats=self.stats)
         self.classes_by_id.copy_(self.state[257:512], non_blocking=True)
         return out
+
+    def from_classes(self, class_mask, flow=None, connectivity=8, min_area=1):
+        self.ops.mask_components(class_mask, connectivity=connectivity, min_area=min_area, id_base=0, cap=127, out=self._inst, classes=self._inst_classes, stats=self.split_stats)
+        return self.detected(self._inst, self._inst_classes, flow)
 
     def propagated(self, flow):
         out = self.ops.mask_propagate(self._img[self._i], flow, out=self._img[self._i ^ 1])

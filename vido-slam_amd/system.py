@@ -44,6 +44,7 @@ def _bind(lib):
     lib.vido_system_set_zero_copy_maps.argtypes = [C.c_void_p, C.c_int]
     lib.vido_system_prefetch_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.vido_system_get_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_mask_split_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.vido_system_get_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
@@ -137,6 +138,15 @@ class System:
         a, b = C.c_int(), C.c_int()
         self.lib.vido_system_get_verify_stats(self.h, C.byref(a), C.byref(b))
         return a.value, b.value
+
+    def mask_split_stats(self):
+        """(found, dropped for area, left out for the cap, kept) of the last frame's mask split (settings key Mask.SplitInstances: 1: the frame's mask is split into its
+        8-connected components of equal value of at least Mask.MinInstanceArea pixels, so that same-class objects track separately); zeros when the frame was not split."""
+        st = (C.c_int32 * 4)()
+        rc = self.lib.vido_system_mask_split_stats(self.h, st)
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_mask_split_stats")
+        return int(st[0]), int(st[1]), int(st[2]), int(st[3])
 
     def verify_points(self):
         """Debug read of the last frame's per-point verification state (vido_system_get_verify_points), index-aligned with the frame's static list:
