@@ -138,3 +138,43 @@ def test_extractor_parameter_sweep(vido, oracle, nf, scale, levels, ini, mn):
             assert np.array_equal(k[name], rk[name]), (f, name)
         assert np.array_equal(desc[f, :cnt[f]], rd)
     c.close()
+
+
+@pytest.mark.parametrize("scale,levels,last", [(1.1, 9, (149, 112)), (1.05, 16, (154, 115))])
+def test_more_than_eight_levels_take_the_per_level_resize(vido, oracle, scale, levels, last):
+    """A pyramid of more than 8 levels is not built by the one-launch tile kernel (it holds at most 8 levels in LDS): every level is resized from the one
+    before it by a launch of its own (k_resize).  Both the lean single-frame path and the event-timed batched path run that chain; pyramid, blur, keypoints and
+    descriptors must equal the oracle's bit for bit, and the single-frame result must equal frame 0 of the batch."""
+    from vido_slam_amd import synth
+    w, h, nfr = 320, 240, 3
+    imgs = np.stack([synth.make_frame(w, h, seed=21 + f) for f in range(nfr)])
+    c = vido.Context(width=w, height=h, max_batch=nfr, n_features=1000, scale_factor=scale, n_levels=levels)
+    p = oracle.orb_params(n_features=1000, scale_factor=scale, n_levels=levels)
+    ref_levels = [oracle.orb_pyramid(p, g) for g in imgs]
+    assert len(ref_levels[0]) == levels and ref_levels[0][-1].shape == (last[1], last[0])
+    ref = [oracle.orb_extract(p, g) for g in imgs]
+
+    def check_levels(f):
+        for l in range(levels):
+            got = c.orb_level(f, l)
+            assert got.shape == ref_levels[f][l].shape, (f, l)
+            assert np.array_equal(got, ref_levels[f][l]), (f, l)
+            assert np.array_equal(c.orb_level(f, l, blurred=True), oracle.gaussian_blur7(ref_levels[f][l])), (f, l)
+
+    def check_result(f, k, d):
+        rk, rd, _ = ref[f]
+        assert len(k) == len(rk) and len(rk) > 0, (f, len(k), len(rk))
+        for name in ("x", "y", "size", "angle", "response", "octave"):
+            assert np.array_equal(k[name], rk[name]), (f, name)
+        assert np.array_equal(d, rd), f
+
+    k1, d1 = c.orb_extract(imgs[0])                                   # one frame: lean, no stage events
+    check_levels(0)
+    check_result(0, k1, d1)
+    kps, desc, cnt = c.orb_extract_batch(imgs)                        # three frames: the batched form
+    for f in range(nfr):
+        check_levels(f)
+        check_result(f, kps[f, :cnt[f]], desc[f, :cnt[f]])
+    assert len(k1) == cnt[0]
+    assert np.array_equal(k1, kps[0, :cnt[0]]) and np.array_equal(d1, desc[0, :cnt[0]])
+    c.close()

@@ -24,14 +24,9 @@
 #include "common.hpp"
 #include "../../include/vido_orb_pattern.h"
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cfloat>
-#include <thread>
-#include <mutex>
-#include <condition_variable>
-#include <functional>
 
 #define EDGE_THRESHOLD 19
 #define HALF_PATCH 15
@@ -152,63 +147,9 @@ __global__ __launch_bounds__(256) void k_resize(uint8_t* __restrict__ pyr, size_
     *(uint32_t*)(base + doff + (size_t)y * dpitch + x4) = out;
 }
 
-// The whole pyramid of a frame in ONE launch (round 4; the tracker's single-frame path).  The seven k_resize launches above are a dependent chain — level l + 1 is resized
-// from level l (ORBextractor.cc:1107-1132) — of ~5 us each; beside the networks every link of that chain queues for a CU again.  Here a workgroup owns a horizontal BAND of
-// the image through all levels: it keeps, per level, the rows it owns plus the few rows the bands of the later levels need from it (PyrBand: computed on the host from the
-// monotone row tables, walking back from the last level) in LDS, computes level l + 1's rows from level l's with the same fixed-point arithmetic, and writes the rows it owns.
-// Rows near a band border are computed by both neighbours (about a third more resize work), there is no exchange between workgroups.
-#define PB_MAXL 8
-struct PyrBand { int need_lo[PB_MAXL], need_n[PB_MAXL], own_lo[PB_MAXL], own_hi[PB_MAXL], lds_off[PB_MAXL]; };      // per level: first needed row / count, owned rows [lo, hi), byte offset of the level's rows in LDS
-struct PyrBandLv { int w[PB_MAXL], h[PB_MAXL], pitch[PB_MAXL], off[PB_MAXL], xoff[PB_MAXL], yoff[PB_MAXL]; int L; };
-__global__ __launch_bounds__(256) void k_pyramid_bands(uint8_t* __restrict__ pyr, size_t slab, PyrBandLv V, const PyrBand* __restrict__ bands,
-                                                       const int2* __restrict__ xtab, const int4* __restrict__ ytab)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t pb_lds[];
-    const PyrBand& B = bands[blockIdx.x];
-    uint8_t* base = pyr + (size_t)blockIdx.y * slab;
-    const int tid = threadIdx.x;
-    {   // level 0: the needed rows of the ingested image, dword copies
-        const int ndw = V.pitch[0] >> 2, n = B.need_n[0] * ndw;
-        const uint32_t* src = (const uint32_t*)(base + V.off[0] + (size_t)B.need_lo[0] * V.pitch[0]);
-        uint32_t* dst = (uint32_t*)(pb_lds + B.lds_off[0]);
-        for (int i = tid; i < n; i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    for (int l = 1; l < V.L; l++) {
-        const int sw = V.w[l - 1], spitch = V.pitch[l - 1], dw = V.w[l], dpitch = V.pitch[l], ndw = dpitch >> 2;
-        const int2* xt = xtab + V.xoff[l]; const int4* yt = ytab + V.yoff[l];
-        const uint8_t* S0 = pb_lds + B.lds_off[l - 1] - (size_t)B.need_lo[l - 1] * spitch;      // source row r lives at S0 + r * spitch
-        uint8_t* D0 = pb_lds + B.lds_off[l];
-        const int rows = B.need_n[l], ylo = B.need_lo[l];
-        for (int i = tid; i < rows * ndw; i += 256) {
-            const int rr = i / ndw, x4 = (i - rr * ndw) * 4, y = ylo + rr;
-            const int4 ytv = yt[y];
-            const uint8_t* L0 = S0 + (size_t)ytv.x * spitch; const uint8_t* L1 = S0 + (size_t)ytv.y * spitch;
-            uint32_t out = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int x = x4 + k;
-                if (x < dw) {
-                    const int2 xv = xt[x];
-                    const int sx = xv.x & 0xffff, a0 = xv.x >> 16, a1 = xv.y;
-                    const int sx1 = sx + 1 < sw ? sx + 1 : sx;
-                    const int r0 = (int)(__umul24(L0[sx], (unsigned)a0) + __umul24(L0[sx1], (unsigned)a1));
-                    const int r1 = (int)(__umul24(L1[sx], (unsigned)a0) + __umul24(L1[sx1], (unsigned)a1));
-                    int v = (int)(((__umul24((unsigned)ytv.z, (unsigned)(r0 >> 4)) >> 16) + (__umul24((unsigned)ytv.w, (unsigned)(r1 >> 4)) >> 16) + 2u) >> 2);
-                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-                    out |= (uint32_t)v << (8 * k);
-                }
-            }
-            *(uint32_t*)(D0 + (size_t)rr * dpitch + x4) = out;
-            if (y >= B.own_lo[l] && y < B.own_hi[l]) *(uint32_t*)(base + V.off[l] + (size_t)y * dpitch + x4) = out;
-        }
-        __syncthreads();
-    }
-}
-
 // The whole pyramid of a BATCH in one launch (round 5): a workgroup owns a 2-D TILE of the image through all levels.  The seven k_resize launches are a dependent chain of
 // latency-bound kernels (three dependent global round trips per workgroup: table corners -> source window -> table rows; 167 us per 64 frames = 7.5 % of the HBM
-// roofline); the band kernel above needs the full image width in LDS (up to 150 KB: one workgroup per CU).  Here
+// roofline).  Here
 //   * the host walks back from the last level once (build_tables): per tile and level the OWNED rectangle (a partition of the level, x cuts on multiples of 4) and the
 //     NEEDED rectangle (owned + whatever the next level's needed rectangle samples), ~1.2x recomputed pixels at 128 x 60 level-0 tiles;
 //   * the workgroup stages its level-0 rectangle and its slices of the coefficient tables into LDS in ONE round trip (table entries of columns past the level's width are
@@ -228,14 +169,14 @@ struct PyrTileLv { int w[PT_MAXL], pitch[PT_MAXL], off[PT_MAXL], xoff[PT_MAXL], 
 // the ingest copy (k_ingest: 15 us per 64 frames, a full read + write of level 0) rides on the staging loads.
 __global__ __launch_bounds__(256) void k_pyramid_tiles(uint8_t* __restrict__ pyr, size_t slab, PyrTileLv V, const PyrTile* __restrict__ tiles,
                                                        const int2* __restrict__ xtab, const int4* __restrict__ ytab,
-                                                       const uint8_t* __restrict__ imgs, size_t frame_stride, int stride, int ntiles, int total, int xcd_deal)
+                                                       const uint8_t* __restrict__ imgs, size_t frame_stride, int stride, int ntiles, int total)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t pt_lds[];
     // Work item = (frame, tile), tiles of a frame in row-major order.  Workgroups go to the eight XCDs round-robin by their linear index, so with item = blockIdx two
     // tiles that meet at a column cut — whose row ends share a cache line of every level, and whose needed rectangles share halo pixels — always sit under DIFFERENT L2s:
     // the shared line leaves each L2 as a partial write and the halo is fetched from memory twice.  Dealt so that an XCD walks a contiguous range of items, the neighbours
     // run side by side on one L2 (round 6).
-    const int per = gridDim.x >> 3, item = xcd_deal ? (blockIdx.x & 7) * per + (blockIdx.x >> 3) : (int)blockIdx.x;
+    const int per = gridDim.x >> 3, item = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     if (item >= total) return;
     const int frame = item / ntiles, tile = item - frame * ntiles;
     const PyrTile& T = tiles[tile];
@@ -985,74 +926,9 @@ __global__ __launch_bounds__(256) void k_kp_write(const uint32_t* __restrict__ c
 }
 
 // ------------------------------------------------------------------------------------------------
-// K4: 7x7 sigma=2 Gaussian, reflect-101, Q0.8 taps {18,34,49,54,49,34,18}; 64x16 output tile per WG.
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) { i = i < 0 ? -i : 2 * n - 2 - i; }
-    return i;
-}
-// 128 x 32 output tile per workgroup, everything in dword units: the (32+6) x (128+8)-byte input window is staged with aligned
-// dword loads (only dwords that touch the image border take the per-byte reflect path), the horizontal pass turns three
-// LDS dwords into four u16 sums, the vertical pass reads seven 8-byte LDS words per four outputs and stores one dword.
-#define BL_TW 128
-#define BL_TH 32
-#define BL_IN_STRIDE 35            // dwords per staged row (34 used; odd stride spreads rows over the LDS banks)
-__device__ __forceinline__ uint32_t blur_load4(const uint8_t* __restrict__ row, int c, int w)
-{
-    if (c >= 0 && c + 3 < w) return *(const uint32_t*)(row + c);
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) v |= (uint32_t)row[reflect101(c + k, w)] << (8 * k);
-    return v;
-}
-__global__ __launch_bounds__(256) void k_blur7(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, size_t slab, PyrDev P,
-                                               const BlurTile* __restrict__ tiles)
-{
-    __shared__ uint32_t in[(BL_TH + 6) * BL_IN_STRIDE];
-    __shared__ uint2 hb[(BL_TH + 6) * (BL_TW / 4)];
-    int ti, fr; xcd_tile_frame(ti, fr);
-    const BlurTile t = tiles[ti];
-    const int w = P.w[t.level], h = P.h[t.level], pitch = P.pitch[t.level];
-    const uint8_t* img = pyr + (size_t)fr * slab + P.off[t.level];
-    uint8_t* out = blur + (size_t)fr * slab + P.off[t.level];
-    const int tid = threadIdx.x, x0 = t.tx * BL_TW, y0 = t.ty * BL_TH;
-    for (int r = tid >> 6; r < BL_TH + 6; r += 4) {
-        const int d = tid & 63;
-        if (d < 34) in[r * BL_IN_STRIDE + d] = blur_load4(img + (size_t)reflect101(y0 + r - 3, h) * pitch, x0 - 4 + 4 * d, w);
-    }
-    __syncthreads();
-    for (int i = tid; i < (BL_TH + 6) * (BL_TW / 4); i += 256) {
-        const int r = i >> 5, d = i & 31;
-        const uint32_t* q = in + r * BL_IN_STRIDE + d;
-        const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
-        // bytes 1..10 of the 12-byte window: output k uses bytes k+1 .. k+7
-        const int b1 = (w0 >> 8) & 255, b2 = (w0 >> 16) & 255, b3 = w0 >> 24, b4 = w1 & 255, b5 = (w1 >> 8) & 255, b6 = (w1 >> 16) & 255, b7 = w1 >> 24,
-                  b8 = w2 & 255, b9 = (w2 >> 8) & 255, b10 = (w2 >> 16) & 255;
-        const uint32_t s0 = 18 * (b1 + b7) + 34 * (b2 + b6) + 49 * (b3 + b5) + 54 * b4;
-        const uint32_t s1 = 18 * (b2 + b8) + 34 * (b3 + b7) + 49 * (b4 + b6) + 54 * b5;
-        const uint32_t s2 = 18 * (b3 + b9) + 34 * (b4 + b8) + 49 * (b5 + b7) + 54 * b6;
-        const uint32_t s3 = 18 * (b4 + b10) + 34 * (b5 + b9) + 49 * (b6 + b8) + 54 * b7;
-        hb[i] = make_uint2(s0 | (s1 << 16), s2 | (s3 << 16));
-    }
-    __syncthreads();
-    for (int i = tid; i < BL_TH * (BL_TW / 4); i += 256) {
-        const int y = i >> 5, d = i & 31;
-        if (y0 + y >= h || x0 + 4 * d >= pitch) continue;
-        uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-        const int taps[7] = {18, 34, 49, 54, 49, 34, 18};
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-            const uint2 v = hb[(y + k) * (BL_TW / 4) + d];
-            a0 += taps[k] * (v.x & 0xffff); a1 += taps[k] * (v.x >> 16); a2 += taps[k] * (v.y & 0xffff); a3 += taps[k] * (v.y >> 16);
-        }
-        *(uint32_t*)(out + (size_t)(y0 + y) * pitch + x0 + 4 * d) =
-            ((a0 + 32768) >> 16) | (((a1 + 32768) >> 16) << 8) | (((a2 + 32768) >> 16) << 16) | (((a3 + 32768) >> 16) << 24);
-    }
-}
-
-// K4w (round 5): the same blur WITHOUT LDS and without workgroup barriers — one wave per strip of BS_QUADS x 4 output columns, sliding down the rows.
-// k_blur7 above spends ~33 vector instructions per pixel (byte extraction, 32-bit multiply-adds, two LDS round trips, two barriers) and runs at 13 % of the HBM roofline;
+// K4: 7x7 sigma=2 Gaussian, reflect-101, Q0.8 taps {18,34,49,54,49,34,18}.
+// K4w (round 5): the blur WITHOUT LDS and without workgroup barriers — one wave per strip of BS_QUADS x 4 output columns, sliding down the rows.
+// Round 1's LDS tile kernel spent ~33 vector instructions per pixel (byte extraction, 32-bit multiply-adds, two LDS round trips, two barriers) and ran at 13 % of the HBM roofline;
 // this form needs ~11:
 //   * lane l owns the aligned quad of columns c = x0 - 4 + 4 l (lanes 0 and 63 are halo only) and keeps the last seven rows of it UNPACKED as two registers of two
 //     u16 (bytes 0,1 | bytes 2,3): a new row costs one dword load and two v_perm;
@@ -1062,7 +938,7 @@ __global__ __launch_bounds__(256) void k_blur7(const uint8_t* __restrict__ pyr, 
 //     byte is bits 23:16 of the accumulator (<= 255 * 65536 + 32768), picked out by two v_perm;
 //   * reflect-101 columns (left edge, right edge, a partial last quad) are built ONCE per loaded row from real lanes' dwords: every virtual byte is some real byte of
 //     at most two other lanes of the wave — two ds_bpermute + one v_perm with per-lane constants, only in waves that contain an edge; reflect-101 rows are a scalar row
-//     index.  Integer arithmetic throughout, no intermediate rounding: identical to the horizontal-then-vertical order of k_blur7 and of the CPU checker.
+//     index.  Integer arithmetic throughout, no intermediate rounding: identical to the horizontal-then-vertical order of the CPU checker.
 #define BS_QUADS 62                // output quads per wave (lanes 1 .. 62)
 // reflect-101 for an index at most n - 1 outside [0, n): one fold per side, no loop (the host only builds strips for levels where that holds); clamped, so that the rows
 // below the image a last strip still loads (and never stores an output for) stay in bounds
@@ -1370,15 +1246,14 @@ struct OrbState {
     LevelInfo lv[VIDO_MAX_LEVELS];
     PyrDev P{};
     size_t slab = 0;
-    int n_cells = 0, n_blur_tiles = 0;
+    int n_cells = 0;
     int umax[HALF_PATCH + 1]; unsigned long long umax_packed = 0;
     std::vector<int> first_cell;
     // device
     uint8_t *d_pyr = nullptr, *d_blur = nullptr;
-    CellDesc* d_cells = nullptr; BlurTile* d_btiles = nullptr;
-    BlurTile* d_bstrips = nullptr; int n_blur_strips = 0;            // k_blur7_strips: {level, first column, first row, batches of 7 input rows} per wave; 0 = the tile kernel stays
+    CellDesc* d_cells = nullptr;
+    BlurTile* d_bstrips = nullptr; int n_blur_strips = 0;            // k_blur7_strips: {level, first column, first row, batches of 7 input rows} per wave
     int2* d_xtab = nullptr; int4* d_ytab = nullptr;
-    PyrBand* d_bands = nullptr; int n_bands = 0; size_t bands_lds = 0; PyrBandLv band_lv{};      // single-launch pyramid (k_pyramid_bands)
     const uint8_t* prefetched_src = nullptr; int prefetched_w = 0, prefetched_h = 0;      // vido_orb_prefetch_color: the device image whose extraction is already on the stream
     PyrTile* d_ptiles = nullptr; int n_ptiles = 0; size_t ptiles_lds = 0; PyrTileLv ptile_lv{};  // single-launch pyramid for any batch (k_pyramid_tiles); 0 tiles = not built
     int* d_frame_tot = nullptr;                                       // per-frame candidate totals (k_scan_frames -> k_scan_apply)
@@ -1477,34 +1352,11 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
         d.rs_rows = mr; d.rs_ndw = mw | 1;                  // odd dword stride: the two source rows of a pixel fall into different banks
         if ((size_t)d.rs_rows * d.rs_ndw * 4 > 64 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "pyramid scale factor too large for the resize tile");
     }
-    // bands of the single-launch pyramid (k_pyramid_bands): per band and level the owned rows and the rows later levels need, walking back from the last level
-    std::vector<PyrBand> bands; S->n_bands = 0; S->bands_lds = 0;
-    if (L >= 2 && L <= PB_MAXL) {
-        const int NB = std::max(1, std::min(24, S->lv[L - 1].h / 4));
-        PyrBandLv& V = S->band_lv; V.L = L;
-        for (int l = 0; l < L; l++) { V.w[l] = S->lv[l].w; V.h[l] = S->lv[l].h; V.pitch[l] = S->lv[l].pitch; V.off[l] = S->lv[l].off; V.xoff[l] = S->lv[l].xtab_off; V.yoff[l] = S->lv[l].ytab_off; }
-        for (int b = 0; b < NB; b++) {
-            PyrBand pb{}; int lo[PB_MAXL], hi[PB_MAXL];
-            for (int l = 0; l < L; l++) { pb.own_lo[l] = (int)((long long)b * S->lv[l].h / NB); pb.own_hi[l] = (int)((long long)(b + 1) * S->lv[l].h / NB); }
-            lo[L - 1] = pb.own_lo[L - 1]; hi[L - 1] = pb.own_hi[L - 1];                      // needed rows [lo, hi) per level
-            for (int l = L - 2; l >= 0; l--) {
-                lo[l] = pb.own_lo[l]; hi[l] = pb.own_hi[l];
-                if (hi[l + 1] > lo[l + 1]) { const int4* yt = ytab.data() + S->lv[l + 1].ytab_off; lo[l] = std::min(lo[l], yt[lo[l + 1]].x); hi[l] = std::max(hi[l], yt[hi[l + 1] - 1].y + 1); }
-                if (l >= 1 && hi[l] <= lo[l]) { lo[l] = hi[l] = pb.own_lo[l]; }
-            }
-            size_t off = 0;
-            for (int l = 0; l < L; l++) { pb.need_lo[l] = lo[l]; pb.need_n[l] = std::max(hi[l] - lo[l], 0); pb.lds_off[l] = (int)off; off += (size_t)pb.need_n[l] * S->lv[l].pitch; off = (off + 15) & ~(size_t)15; }
-            S->bands_lds = std::max(S->bands_lds, off);
-            bands.push_back(pb);
-        }
-        if (S->bands_lds <= 150 * 1024) S->n_bands = NB;      // (else the per-level kernels stay)
-    }
     // tiles of the single-launch batched pyramid (k_pyramid_tiles): owned / needed rectangles per tile and level, walking back from the last level
     std::vector<PyrTile> ptiles; S->n_ptiles = 0; S->ptiles_lds = 0;
-    if (L >= 2 && L <= PT_MAXL && getenv("VIDO_PYR_LEVELS") == nullptr) {
-        static const int env_nx = [] { const char* e = getenv("VIDO_PYR_NX"); return e ? atoi(e) : 0; }(), env_ny = [] { const char* e = getenv("VIDO_PYR_NY"); return e ? atoi(e) : 0; }();      // (experiments)
+    if (L >= 2 && L <= PT_MAXL) {
         // ~107 x 48 level-0 tiles (640 x 480: 6 x 10 = 60 workgroups per frame, 35 KB of LDS each; measured 5 x 8 .. 12 x 20: 106 / 95 / 100 / 129 us per 64 frames incl. the ingest)
-        const int NX = std::max(1, std::min(env_nx > 0 ? env_nx : (c.width + 53) / 107, S->lv[L - 1].w / 8)), NY = std::max(1, std::min(env_ny > 0 ? env_ny : (c.height + 24) / 48, S->lv[L - 1].h / 4));
+        const int NX = std::max(1, std::min((c.width + 53) / 107, S->lv[L - 1].w / 8)), NY = std::max(1, std::min((c.height + 24) / 48, S->lv[L - 1].h / 4));
         PyrTileLv& V = S->ptile_lv; V.L = L;
         for (int l = 0; l < L; l++) { V.w[l] = S->lv[l].w; V.pitch[l] = S->lv[l].pitch; V.off[l] = S->lv[l].off; V.xoff[l] = S->lv[l].xtab_off; V.yoff[l] = S->lv[l].ytab_off; }
         bool ok = true;
@@ -1548,7 +1400,7 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
         if (ok && S->ptiles_lds <= 150 * 1024) S->n_ptiles = (int)ptiles.size();
     }
     // FAST cell table in the reference's loop order (ORBextractor.cc:759-796)
-    std::vector<CellDesc> cells; std::vector<BlurTile> btiles;
+    std::vector<CellDesc> cells;
     S->first_cell.assign(L, 0);
     for (int l = 0; l < L; l++) {
         LevelInfo& v = S->lv[l];
@@ -1574,23 +1426,19 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
             }
         }
         v.n_cells = (int)cells.size() - v.first_cell;
-        for (int ty = 0; ty < (v.h + BL_TH - 1) / BL_TH; ty++)
-            for (int tx = 0; tx < (v.w + BL_TW - 1) / BL_TW; tx++) btiles.push_back(BlurTile{l, tx, ty, 0});
     }
-    S->n_cells = (int)cells.size(); S->n_blur_tiles = (int)btiles.size();
+    S->n_cells = (int)cells.size();
     std::vector<BlurTile> bstrips;
-    {   // strips of the LDS-free blur: a level's quads split evenly over ceil(quads / BS_QUADS) waves per row band, bands of 7 nb - 6 output rows
-        static const int nb_env = [] { const char* e = getenv("VIDO_BLUR_NB"); return e ? atoi(e) : 0; }();
-        const int nb = nb_env >= 1 && nb_env <= 16 ? nb_env : 3, rows_out = 7 * nb - 6;
-        bool ok = getenv("VIDO_BLUR_TILES") == nullptr;                 // (A/B switch: the round-1 tile kernel)
-        for (int l = 0; l < L && ok; l++) {
+    {   // strips of the blur: a level's quads split evenly over ceil(quads / BS_QUADS) waves per row band, bands of 7 nb - 6 output rows
+        const int nb = 3, rows_out = 7 * nb - 6;
+        for (int l = 0; l < L; l++) {
             const LevelInfo& v = S->lv[l];
             const int nq = (v.w + 3) / 4, nt = (nq + BS_QUADS - 1) / BS_QUADS, qpt = (nq + nt - 1) / nt, x_last = 4 * qpt * (nt - 1);
-            if (v.w < 16 || v.h < 7 * nb + 8 || v.w - 8 - x_last + 4 < 0) { ok = false; break; }      // the reflected columns of the right edge must live in lanes of the last strip
+            if (v.w < 16 || v.h < 7 * nb + 8 || v.w - 8 - x_last + 4 < 0)      // the reflected columns of the right edge must live in lanes of the last strip
+                return vido_set_error(ctx, VIDO_E_INVALID, "pyramid level %d is %dx%d: no blur strip layout for it", l, v.w, v.h);
             for (int y0 = 0; y0 < v.h; y0 += rows_out)
                 for (int tx = 0; tx < nt; tx++) bstrips.push_back(BlurTile{l, 4 * qpt * tx, y0, nb});
         }
-        if (!ok) bstrips.clear();
     }
     S->n_blur_strips = (int)bstrips.size();
     // FAST strips: runs of up to FS_MAXC horizontally adjacent cells of one cell row (consecutive in the reference order), split evenly; per-cell output slots
@@ -1642,23 +1490,13 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
     HIP_TRY(ctx, hipMemcpy(S->d_slot_off, slot_off.data(), slot_off.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMalloc(&S->d_cells, cells.size() * sizeof(CellDesc)));
     HIP_TRY(ctx, hipMemcpy(S->d_cells, cells.data(), cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMalloc(&S->d_btiles, btiles.size() * sizeof(BlurTile)));
-    HIP_TRY(ctx, hipMemcpy(S->d_btiles, btiles.data(), btiles.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
-    if (!bstrips.empty()) {
-        HIP_TRY(ctx, hipMalloc(&S->d_bstrips, bstrips.size() * sizeof(BlurTile)));
-        HIP_TRY(ctx, hipMemcpy(S->d_bstrips, bstrips.data(), bstrips.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
-    }
+    HIP_TRY(ctx, hipMalloc(&S->d_bstrips, bstrips.size() * sizeof(BlurTile)));
+    HIP_TRY(ctx, hipMemcpy(S->d_bstrips, bstrips.data(), bstrips.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMalloc(&S->d_xtab, std::max<size_t>(xtab.size(), 1) * sizeof(int2)));
     HIP_TRY(ctx, hipMalloc(&S->d_ytab, std::max<size_t>(ytab.size(), 1) * sizeof(int4)));
     if (!xtab.empty()) {
         HIP_TRY(ctx, hipMemcpy(S->d_xtab, xtab.data(), xtab.size() * sizeof(int2), hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(S->d_ytab, ytab.data(), ytab.size() * sizeof(int4), hipMemcpyHostToDevice));
-    }
-    if (S->n_bands) {
-        HIP_TRY(ctx, hipMalloc(&S->d_bands, bands.size() * sizeof(PyrBand)));
-        HIP_TRY(ctx, hipMemcpy(S->d_bands, bands.data(), bands.size() * sizeof(PyrBand), hipMemcpyHostToDevice));
-        static bool battr[64] = {};                                   // per function and device, not per ctx: a second, smaller ctx must not lower the first one's limit
-        if (!battr[ctx->device & 63]) { HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_pyramid_bands, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); battr[ctx->device & 63] = true; }
     }
     if (S->n_ptiles) {
         HIP_TRY(ctx, hipMalloc(&S->d_ptiles, ptiles.size() * sizeof(PyrTile)));
@@ -1690,7 +1528,7 @@ int orb_state_create(vido_ctx* ctx)
     HIP_TRY(ctx, hipMemset(S->d_blur, 0, S->slab * B));
     HIP_TRY(ctx, hipMalloc(&S->d_slots, (size_t)S->slot_total * B * sizeof(uint32_t)));
     {   // the attribute is per (function, device), not per ctx: set ONCE to the ceiling, so that a second, smaller ctx (the local-BA helper: 64 features, one level) can never
-        // lower the limit the tracker's launches need (the same rule as k_pyramid_bands / k_pyramid_tiles above)
+        // lower the limit the tracker's launches need (the same rule as k_pyramid_tiles above)
         static bool fattr[64] = {};
         if (S->fast_lds > 64 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "orb: a FAST strip of %d rows needs %zu bytes of LDS (limit 65536)", S->fast_rows, S->fast_lds);
         if (!fattr[ctx->device & 63]) {
@@ -1747,7 +1585,7 @@ void orb_state_destroy(vido_ctx* ctx)
 {
     OrbState* S = ctx->orb;
     if (!S) return;
-    hipFree(S->d_pyr); hipFree(S->d_blur); hipFree(S->d_cells); hipFree(S->d_btiles); hipFree(S->d_bstrips); hipFree(S->d_xtab); hipFree(S->d_ytab); hipFree(S->d_bands); hipFree(S->d_ptiles);
+    hipFree(S->d_pyr); hipFree(S->d_blur); hipFree(S->d_cells); hipFree(S->d_bstrips); hipFree(S->d_xtab); hipFree(S->d_ytab); hipFree(S->d_ptiles);
     hipFree(S->d_slots); hipFree(S->d_counts); hipFree(S->d_offsets); hipFree(S->d_frame_tot); hipFree(S->d_first_cell); hipFree(S->d_lvloff); hipFree(S->d_overflow);
     hipFree(S->d_cand); hipFree(S->d_kp); hipFree(S->d_strips); hipFree(S->d_slot_off);
     hipHostFree(S->h_lvloff); hipHostFree(S->h_overflow); hipHostFree(S->h_cand);
@@ -1765,8 +1603,7 @@ void orb_state_destroy(vido_ctx* ctx)
 
 static inline void orb_launch_blur(OrbState* S, int nf, hipStream_t st)
 {
-    if (S->n_blur_strips) hipLaunchKernelGGL(k_blur7_strips, dim3(S->n_blur_strips, nf), dim3(64), 0, st, S->d_pyr, S->d_blur, S->slab, S->P, S->d_bstrips);
-    else hipLaunchKernelGGL(k_blur7, dim3(S->n_blur_tiles, nf), dim3(256), 0, st, S->d_pyr, S->d_blur, S->slab, S->P, S->d_btiles);
+    hipLaunchKernelGGL(k_blur7_strips, dim3(S->n_blur_strips, nf), dim3(64), 0, st, S->d_pyr, S->d_blur, S->slab, S->P, S->d_bstrips);
 }
 
 // Enqueues the whole extractor for nf frames on the ctx stream; nothing is synchronised.  Results land in the device
@@ -1791,9 +1628,8 @@ int orb_enqueue(vido_ctx* ctx, const uint8_t* imgs, int on_device, int nf, size_
     const bool lean = nf <= 2 && !full_timing;
 #define ORB_EV(e, s_) do { if (!lean) HIP_TRY(ctx, hipEventRecord((e), (s_))); } while (0)
     ORB_EV(S->ev[0], st);
-    static const int tiles_mode = [] { const char* e = getenv("VIDO_PYR_TILES"); return e ? atoi(e) : 1; }();        // A/B switch: 0 = the round-4 kernels (bands for one frame, per-level launches for a batch); 2 = tiles, ingest not fused
     // gray device frames that allow dword loads ride on the tile kernel's staging instead of a copy of their own
-    const bool fuse_ingest = S->n_ptiles && tiles_mode == 1 && S->in_channels == 1 && on_device && L >= 2 && (((uintptr_t)imgs | (uintptr_t)frame_stride | (uintptr_t)stride | (uintptr_t)width) & 3) == 0;
+    const bool fuse_ingest = S->n_ptiles && S->in_channels == 1 && on_device && (((uintptr_t)imgs | (uintptr_t)frame_stride | (uintptr_t)stride | (uintptr_t)width) & 3) == 0;
     // level 0 <- input
     if (S->in_channels != 1) {                          // colour frames: cvtColor fused into the ingest (set by vido_orb_extract_color for this one call)
         const int cn = S->in_channels; const uint8_t* src = imgs; size_t fs = frame_stride; int sst = stride;
@@ -1817,22 +1653,19 @@ int orb_enqueue(vido_ctx* ctx, const uint8_t* imgs, int on_device, int nf, size_
         if (S->gray_out && !S->gray_out_on_device)
             HIP_TRY(ctx, hipMemcpyAsync(S->gray_out, gdev, (size_t)nf * width * height, hipMemcpyDeviceToHost, st));
     }
-    else if (on_device && fuse_ingest) { /* level 0 is written by k_pyramid_tiles below */ }
+    else if (fuse_ingest) { /* level 0 is written by k_pyramid_tiles below */ }
     else if (on_device)
         hipLaunchKernelGGL(k_ingest, dim3((S->lv[0].pitch / 4 + 63) / 64, (height + 3) / 4, nf), dim3(256), 0, st, imgs, frame_stride, stride, width, height,
                            S->d_pyr, S->slab, S->lv[0].off, S->lv[0].pitch);
     else for (int f = 0; f < nf; f++)
         HIP_TRY(ctx, hipMemcpy2DAsync(S->d_pyr + (size_t)f * S->slab + S->lv[0].off, S->lv[0].pitch, imgs + (size_t)f * frame_stride, stride,
                                       width, height, hipMemcpyHostToDevice, st));
-    static const int bands_mode = [] { const char* e = getenv("VIDO_ORB_BANDS"); return e ? atoi(e) : -1; }();      // experiment switch: 1 = the band pyramid for every batch size, 0 = never
-    if (S->n_ptiles && tiles_mode) {
-        static const int xcd_deal = [] { const char* e = getenv("VIDO_PYR_XCD"); return e ? atoi(e) : 1; }();         // (0: item = workgroup index, the round-5 order)
+    // Tiles are not built (build_tables) when L > PT_MAXL, when a tile needs more than 150 KB of LDS or when a tile's row reciprocal is inexact: then the per-level chain runs.
+    if (S->n_ptiles) {
         const int total = S->n_ptiles * nf;
         hipLaunchKernelGGL(k_pyramid_tiles, dim3(8 * ((total + 7) / 8)), dim3(256), S->ptiles_lds, st, S->d_pyr, S->slab, S->ptile_lv, (const PyrTile*)S->d_ptiles, (const int2*)S->d_xtab, (const int4*)S->d_ytab,
-                           fuse_ingest ? imgs : (const uint8_t*)nullptr, frame_stride, stride, S->n_ptiles, total, xcd_deal);
+                           fuse_ingest ? imgs : (const uint8_t*)nullptr, frame_stride, stride, S->n_ptiles, total);
     }
-    else if (S->n_bands && (bands_mode == 1 || (bands_mode != 0 && lean)))
-        hipLaunchKernelGGL(k_pyramid_bands, dim3(S->n_bands, nf), dim3(256), S->bands_lds, st, S->d_pyr, S->slab, S->band_lv, (const PyrBand*)S->d_bands, (const int2*)S->d_xtab, (const int4*)S->d_ytab);
     else for (int l = 1; l < L; l++) {
         const LevelInfo &s = S->lv[l - 1], &d = S->lv[l];
         dim3 grid((d.pitch + RS_TW - 1) / RS_TW, (d.h + RS_TH - 1) / RS_TH, nf), block(256);
@@ -1848,18 +1681,7 @@ int orb_enqueue(vido_ctx* ctx, const uint8_t* imgs, int on_device, int nf, size_
         hipLaunchKernelGGL(k_fast_strips<FS_WIDE>, dim3(S->n_strips, nf), dim3(64), S->fast_lds, st, S->d_pyr, S->slab, S->P, S->d_strips, S->n_cells, S->d_slot_off, S->slot_total,
                            ctx->cfg.ini_th_fast, ctx->cfg.min_th_fast, S->fast_rows, S->d_slots, S->d_counts);
     ORB_EV(S->ev[7], st);
-    if (getenv("VIDO_DEBUG_SYNC")) {       // debugging aid: the FAST stage alone, then its per-cell counts against the slot capacities
-        fprintf(stderr, "[vido] k_fast_strips (%d strips x %d frames, lds %zu)...\n", S->n_strips, nf, S->fast_lds);
-        hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[vido] k_fast_strips: %s\n", hipGetErrorString(e));
-        std::vector<int> hc((size_t)S->n_cells * nf), so(S->n_cells + 1);
-        hipMemcpy(hc.data(), S->d_counts, hc.size() * sizeof(int), hipMemcpyDeviceToHost); hipMemcpy(so.data(), S->d_slot_off, so.size() * sizeof(int), hipMemcpyDeviceToHost);
-        long long tot = 0; int bad = 0;
-        for (size_t i = 0; i < hc.size(); i++) { const int c = (int)(i % S->n_cells), capc = so[c + 1] - so[c]; tot += hc[i];
-            if (hc[i] < 0 || hc[i] > capc) { if (bad++ < 8) fprintf(stderr, "[vido]   cell %d (frame %zu): count %d, capacity %d\n", c, i / S->n_cells, hc[i], capc); } }
-        fprintf(stderr, "[vido] counts: total %lld, %d out of range\n", tot, bad);
-    }
-    static const bool scan_one = getenv("VIDO_ORB_SCAN1") != nullptr;       // A/B switch: the single-workgroup scan
-    if (scan_one || nf == 1 || L > 64)
+    if (nf == 1)
         hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, S->d_counts, S->n_cells * nf, S->d_offsets, S->n_cells, nf, L, S->d_first_cell, S->d_lvloff);
     else {
         hipLaunchKernelGGL(k_scan_frames, dim3(nf), dim3(256), 0, st, S->d_counts, S->n_cells, L, S->d_first_cell, S->d_offsets, S->d_lvloff, S->d_frame_tot);
@@ -1880,16 +1702,10 @@ int orb_enqueue(vido_ctx* ctx, const uint8_t* imgs, int on_device, int nf, size_
     }
     // ---- DistributeOctTree per (frame, level) + keypoint list, all on the device
     const int n_tasks = nf * L;
-    static const bool dbg = getenv("VIDO_DEBUG_SYNC") != nullptr;
-#define DBG_SYNC(name) do { if (dbg) { fprintf(stderr, "[vido] %s...\n", name); hipStreamSynchronize(st); fprintf(stderr, "[vido] %s ok\n", name); } } while (0)
-    DBG_SYNC("fast+gather");
     hipLaunchKernelGGL(k_quadtree, dim3(n_tasks), dim3(QT_NT), S->qt_lds, st, S->d_cand, S->d_lvloff, S->P, L, S->d_budget, S->qcap, S->d_qt_slot, S->d_sel, S->d_selcnt, S->d_overflow, (int)S->cand_cap);
-    DBG_SYNC("k_quadtree");
     hipLaunchKernelGGL(k_kp_offsets, dim3(1), dim3(1024), 0, st, S->d_selcnt, n_tasks, L, S->d_kpoff, S->d_frame_beg, nf);
-    DBG_SYNC("k_kp_offsets");
     hipLaunchKernelGGL(k_kp_write, dim3(n_tasks), dim3(256), 0, st, S->d_cand, S->d_lvloff, S->d_sel, S->d_selcnt, S->d_kpoff, S->qcap, L, S->d_kp, (int)S->kp_cap,
                        S->d_kpf, S->row_cap, S->d_nkp, S->kpl);
-    DBG_SYNC("k_kp_write");
     ORB_EV(S->ev_qt, st);
     if (with_desc && !lean) HIP_TRY(ctx, hipStreamWaitEvent(st, S->ev[4], 0));
     ORB_EV(S->ev[5], st);
@@ -1906,7 +1722,6 @@ int orb_enqueue(vido_ctx* ctx, const uint8_t* imgs, int on_device, int nf, size_
         }
         S->half_frames = fh < nf ? fh : 0;
     }
-    DBG_SYNC("k_orient_brief");
     ORB_EV(S->ev[6], st);
     S->lean_last = lean;
     S->last_frames = nf;

@@ -346,8 +346,7 @@ int vido_frame_upload(vido_ctx* ctx, int slot0, int n_frames, float* depth, cons
     return VIDO_OK;
 }
 
-// threads of the one-workgroup-per-frame list kernels.  (VIDO_LISTS_NT: experiment switch)
-static int lists_nt() { static const int v = [] { const char* e = getenv("VIDO_LISTS_NT"); const int t = e ? atoi(e) : 1024; return (t == 64 || t == 128 || t == 256 || t == 512) ? t : 1024; }(); return v; }
+constexpr int LISTS_NT = 1024;      // threads of the one-workgroup-per-frame list kernels
 
 int vido_frame_features(vido_ctx* ctx, int slot0, int n_frames, const vido_keypoint* kps, const int32_t* n_kps, int max_kp,
                         const vido_track_params* p, vido_frame_lists* out)
@@ -380,14 +379,14 @@ int vido_frame_features(vido_ctx* ctx, int slot0, int n_frames, const vido_keypo
     } }
     for (int f = 1; f < n_frames; f++) if (T->sdepth[slot0 + f] != T->sdepth[slot0] + f * px) return vido_set_error(ctx, VIDO_E_INVALID, "frame_features: slots [%d,%d) do not hold one contiguous batch", slot0, slot0 + n_frames);
     { VidoProfScope ps("frame_features: k_static_filter", st, true);
-    hipLaunchKernelGGL(k_static_filter, dim3(n_frames), dim3(lists_nt()), 0, st, T->d_kps, T->d_nobj, T->max_kp, T->max_kp,
+    hipLaunchKernelGGL(k_static_filter, dim3(n_frames), dim3(LISTS_NT), 0, st, T->d_kps, T->d_nobj, T->max_kp, T->max_kp,
                        T->sdepth[slot0], T->sflow[slot0], T->smask[slot0], T->W, T->H, p->th_depth_bg,
                        T->d_sidx, T->d_scorr, T->d_sflow, T->d_sdepth, T->d_nstat); }
     const int step = p->dense_step > 0 ? p->dense_step : 4;
     const int lattice = ((T->W + step - 1) / step) * ((T->H + step - 1) / step);
     if (lattice > T->max_obj) return vido_set_error(ctx, VIDO_E_INVALID, "frame_features: dense_step %d gives %d probes > %d", step, lattice, T->max_obj);
     { VidoProfScope ps("frame_features: k_dense_sample", st, true);
-    hipLaunchKernelGGL(k_dense_sample, dim3(n_frames), dim3(lists_nt()), 0, st, T->sdepth[slot0], T->sflow[slot0], T->smask[slot0],
+    hipLaunchKernelGGL(k_dense_sample, dim3(n_frames), dim3(LISTS_NT), 0, st, T->sdepth[slot0], T->sflow[slot0], T->smask[slot0],
                        T->W, T->H, p->th_depth_obj, step, T->max_obj, T->d_okeys, T->d_ocorr, T->d_odepth, T->d_olabel, T->d_oflow, T->d_nobj); }
     { VidoProfScope ps("frame_features: counts download + wait", st, false);
     HIP_TRY(ctx, hipMemcpyAsync(T->h_cnt, T->d_nstat, n_frames * 4, hipMemcpyDeviceToHost, st));
