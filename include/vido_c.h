@@ -94,6 +94,11 @@ int vido_orb_read_level(vido_ctx* ctx, int frame, int level, int blurred, uint8_
 /* FAST candidates of the last call for (frame, level) in reference order: packed x | y<<12 | score<<24
  * (level coordinates).  Returns count (or <0). */
 int vido_orb_read_candidates(vido_ctx* ctx, int frame, int level, uint32_t* out, int cap);
+/* Which kernel forms the context's tables (built at creation from the frame size) select; reads the tables only: nothing is launched, no state changes.
+ * out: [0] n_levels [1] tiles of the single-launch pyramid (0: no tile launch — one level, or the per-level resize chain) [2] [3] its tile grid NX, NY (0 0: none laid out)
+ * [4] interior width of the FAST strip kernel's instantiation (37 or 74) [5] rows a FAST strip holds [6] widest FAST cell interior [7] FAST strips per frame
+ * [8] FAST cells per frame [9] blur strips per frame [10] most blur strips in one row of any level [11] candidate slots per frame */
+int vido_orb_geometry(const vido_ctx* ctx, int32_t out[12]);
 /* per-stage time of the last batch call (HIP events on the ctx stream), ms: [0] pyramid (level-0 copy + resize
  * launches) [1] k_fast_cells alone [2] device quadtree + keypoint list [3] blur [4] orient/rBRIEF
  * [5] total wall [6] scan+gather [7] number of FAST candidates in the batch */

@@ -1256,6 +1256,7 @@ struct OrbState {
     int2* d_xtab = nullptr; int4* d_ytab = nullptr;
     const uint8_t* prefetched_src = nullptr; int prefetched_w = 0, prefetched_h = 0;      // vido_orb_prefetch_color: the device image whose extraction is already on the stream
     PyrTile* d_ptiles = nullptr; int n_ptiles = 0; size_t ptiles_lds = 0; PyrTileLv ptile_lv{};  // single-launch pyramid for any batch (k_pyramid_tiles); 0 tiles = not built
+    int ptile_nx = 0, ptile_ny = 0;                                   // the tile grid build_tables laid out (0 x 0: none was, L < 2 or L > PT_MAXL); reported by vido_orb_geometry
     int* d_frame_tot = nullptr;                                       // per-frame candidate totals (k_scan_frames -> k_scan_apply)
     uint32_t* d_slots = nullptr; int *d_counts = nullptr, *d_offsets = nullptr, *d_first_cell = nullptr, *d_lvloff = nullptr, *d_overflow = nullptr;
     uint32_t* d_cand = nullptr; size_t cand_cap = 0;
@@ -1267,6 +1268,7 @@ struct OrbState {
     std::chrono::steady_clock::time_point t_start;
     int last_frames = 0; bool lean_last = false;
     int fast_rows = 0, fast_iw = FS_NARROW; size_t fast_lds = 0;
+    int fast_max_interior = 0, blur_row_strips = 0;                   // widest FAST cell interior, most blur strips in one row of any level (vido_orb_geometry)
     FastStrip* d_strips = nullptr; int n_strips = 0; int* d_slot_off = nullptr; int slot_total = 0;      // FAST strips (<= 4 cells each), per-cell output slot offsets, slots per frame
     // device quadtree / keypoint assembly
     uint16_t* d_qt_slot = nullptr; int *d_sel = nullptr, *d_selcnt = nullptr, *d_kpoff = nullptr, *d_frame_beg = nullptr, *d_budget = nullptr;
@@ -1353,10 +1355,11 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
         if ((size_t)d.rs_rows * d.rs_ndw * 4 > 64 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "pyramid scale factor too large for the resize tile");
     }
     // tiles of the single-launch batched pyramid (k_pyramid_tiles): owned / needed rectangles per tile and level, walking back from the last level
-    std::vector<PyrTile> ptiles; S->n_ptiles = 0; S->ptiles_lds = 0;
+    std::vector<PyrTile> ptiles; S->n_ptiles = 0; S->ptiles_lds = 0; S->ptile_nx = S->ptile_ny = 0;
     if (L >= 2 && L <= PT_MAXL) {
         // ~107 x 48 level-0 tiles (640 x 480: 6 x 10 = 60 workgroups per frame, 35 KB of LDS each; measured 5 x 8 .. 12 x 20: 106 / 95 / 100 / 129 us per 64 frames incl. the ingest)
         const int NX = std::max(1, std::min((c.width + 53) / 107, S->lv[L - 1].w / 8)), NY = std::max(1, std::min((c.height + 24) / 48, S->lv[L - 1].h / 4));
+        S->ptile_nx = NX; S->ptile_ny = NY;
         PyrTileLv& V = S->ptile_lv; V.L = L;
         for (int l = 0; l < L; l++) { V.w[l] = S->lv[l].w; V.pitch[l] = S->lv[l].pitch; V.off[l] = S->lv[l].off; V.xoff[l] = S->lv[l].xtab_off; V.yoff[l] = S->lv[l].ytab_off; }
         bool ok = true;
@@ -1431,6 +1434,7 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
     std::vector<BlurTile> bstrips;
     {   // strips of the blur: a level's quads split evenly over ceil(quads / BS_QUADS) waves per row band, bands of 7 nb - 6 output rows
         const int nb = 3, rows_out = 7 * nb - 6;
+        S->blur_row_strips = 0;
         for (int l = 0; l < L; l++) {
             const LevelInfo& v = S->lv[l];
             const int nq = (v.w + 3) / 4, nt = (nq + BS_QUADS - 1) / BS_QUADS, qpt = (nq + nt - 1) / nt, x_last = 4 * qpt * (nt - 1);
@@ -1438,6 +1442,7 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
                 return vido_set_error(ctx, VIDO_E_INVALID, "pyramid level %d is %dx%d: no blur strip layout for it", l, v.w, v.h);
             for (int y0 = 0; y0 < v.h; y0 += rows_out)
                 for (int tx = 0; tx < nt; tx++) bstrips.push_back(BlurTile{l, 4 * qpt * tx, y0, nb});
+            S->blur_row_strips = std::max(S->blur_row_strips, nt);
         }
     }
     S->n_blur_strips = (int)bstrips.size();
@@ -1453,7 +1458,7 @@ static int build_tables(vido_ctx* ctx, OrbState* S)
                 return vido_set_error(ctx, VIDO_E_INVALID, "FAST cell %dx%d at level %d exceeds the strip tile (%dx63 interior)", cd.sw, cd.sh, cd.level, FS_WIDE);
         }
         const int FS_MAXIW = max_iw <= FS_NARROW ? FS_NARROW : FS_WIDE;      // which instantiation of k_fast_strips this configuration runs
-        S->fast_iw = FS_MAXIW;
+        S->fast_iw = FS_MAXIW; S->fast_max_interior = max_iw;
         size_t c0 = 0;
         while (c0 < cells.size()) {
             size_t c1 = c0 + 1;                                       // [c0, c1): the cells of one cell row (same level and y0, x adjacent)
@@ -1967,6 +1972,16 @@ int vido_orb_read_candidates(vido_ctx* ctx, int frame, int level, uint32_t* out,
         memcpy(out, S->h_cand, (size_t)m * sizeof(uint32_t));
     }
     return n;
+}
+
+int vido_orb_geometry(const vido_ctx* ctx, int32_t out[12])
+{
+    if (!ctx || !ctx->orb || !out) return VIDO_E_INVALID;
+    const OrbState* S = ctx->orb;
+    const int32_t g[12] = {S->L, S->n_ptiles, S->ptile_nx, S->ptile_ny, S->fast_iw, S->fast_rows, S->fast_max_interior, S->n_strips, S->n_cells, S->n_blur_strips,
+                           S->blur_row_strips, S->slot_total};
+    memcpy(out, g, sizeof g);
+    return VIDO_OK;
 }
 
 int vido_orb_last_timing(const vido_ctx* ctx, float ms[8])

@@ -60,6 +60,7 @@ def load_library():
     lib.vido_orb_read_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.vido_orb_read_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.vido_orb_last_timing.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vido_orb_geometry.argtypes = [C.c_void_p, C.c_void_p]
     lib.vido_hamming_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
@@ -183,6 +184,12 @@ class Context:
         self._check(self.lib.vido_orb_read_candidates(self.h, frame, level, _ptr(out), n))
         out = out[:n]
         return (out & 0xfff).astype(np.int32), ((out >> 12) & 0xfff).astype(np.int32), (out >> 24).astype(np.int32)
+
+    def orb_geometry(self):
+        """vido_orb_geometry: the kernel forms the context's tables select (read-only), as a dict."""
+        g = np.zeros(12, np.int32)
+        self._check(self.lib.vido_orb_geometry(self.h, _ptr(g)))
+        return dict(zip(["n_levels", "n_ptiles", "nx", "ny", "fast_iw", "fast_rows", "max_interior", "n_strips", "n_cells", "n_blur_strips", "max_blur_row_strips", "slot_total"], g.tolist()))
 
     def orb_describe_points(self, frame, xyl, ref_desc=None):
         """Orientation + rBRIEF at given points of pyramid slab `frame` (vido_orb_describe_points): xyl (n,3) i32 = x, y in level coordinates, level.
