@@ -497,6 +497,16 @@ int vido_conv3x3_h_workgroups(int n, int cout, int h, int w);
 int vido_conv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope);
 /* ... of the first *n_live images only (see vido_mask_logit_select_n); the live workgroups are dealt over the chip as a launch of n_live images would deal them. */
 int vido_conv3x3_h_bias_act_n(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live);
+/* Layers of >= 128 output channels: the counted launch is ONE kernel that picks its form from the count when it runs — a fine form (fewer channels per workgroup, so more
+ * and shorter-lived workgroups) while the live images leave most of the chip idle, the uncounted launch's form otherwise; every form gives the same bits.
+ * vido_conv3x3_h_live_form: what a count word `live` (clamped to [0, n] like the kernel's) selects — returns 1 for the fine form, 0 for the coarse one, and stores the form's
+ * output channels per workgroup and rows per position block (either pointer may be NULL).
+ * vido_mask_head_coarse: 1 when VIDO_MASK_HEAD_COARSE=1 is set (read once per process): the counted launches of the mask head (this one, vido_roi_align_fpn_nhwc_n,
+ * vido_mask_logit_select_n, vido_mask_label_image_n) then keep the launch shapes of the uncounted calls — an attribution switch, same results.
+ * vido_conv3x3_h_bias_act_form: measurement only — the uncounted launch forced into the form <rpw, cg> (32 rpw cg channels per workgroup, 16 / cg block rows). */
+int vido_conv3x3_h_live_form(int n, int cout, int h, int w, int live, int* channels, int* block_rows);
+int vido_mask_head_coarse(void);
+int vido_conv3x3_h_bias_act_form(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, int rpw, int cg);
 long long vido_wino3x3_packed_floats_form(int cin, int cout, int form);
 int vido_wino3x3_pack_form(const float* w, int cin, int cout, int form, float* u_packed);
 int vido_wino3x3_bias_act_form(vido_ctx* ctx, const float* x, const float* u_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, int form);
@@ -574,6 +584,10 @@ int vido_det_select(vido_ctx* ctx, const float* prob, const float* seg_boxes, co
  * label image (src/run_mask_rcnn.py:112-118: blank_mask += mask * class_index): masks [n,1,M,M] f32, boxes [n,4] f32 in the output image, labels [n] i64,
  * all DEVICE, detections in the order the node adds them; out [H,W] u8 = (sum over detections of pasted mask * class index) mod 256. */
 int vido_mask_label_image(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W, uint8_t* out);
+/* ... for a list whose slots behind *n_live (DEVICE int32 word read by the kernel, clamped to [0, n]; NULL: none) all have label 0, as the static head's ordered list has:
+ * the walk over the list stops at the count; the image is the same. */
+int vido_mask_label_image_n(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W, uint8_t* out,
+                            const int32_t* n_live);
 /* Masker + INSTANCE image: same inputs as vido_mask_label_image (device pointers; detections in the caller's priority order, highest first).
  * out[y,x] = id_base + 1 + (index of the FIRST detection with labels[i] != 0 whose pasted mask probability at (x,y) > thresh), 0 if none: the footprint of every
  * detection is the one vido_mask_label_image adds its class to, overlaps go to the earlier detection instead of summing.  labels[i] == 0 (an unused slot of the

@@ -11,14 +11,17 @@
         per-kernel medians of the mask head's launches inside the detector graph (the last block's replays), and the graph's span from the first to the last kernel of a replay.
 
     python tools/prof_mask_head_live.py forms
-        the mask head's 3x3 layer (256 -> 256 on 100 x 14 x 14) with a live count of 1, 5, 25, 100 in the 16-row form <4,1>; the 8-row form <2,2> is timed on a batch of
-        exactly that many images, which runs the same live workgroups (VIDO_CONV3X3_H_ROWS forces a form per process, so the two forms are two calls of this mode)."""
+        the mask head's 3x3 layer (256 -> 256 on 14 x 14) at live counts 1, 2, 5, 10, 17, 25, 50, 100: every candidate form forced on a batch of exactly that many
+        images (vido_conv3x3_h_bias_act_form: <4,1> is the coarse form the host picks for 100 images), and the counted launch on a batch of 100 with the form its rule
+        picks (vido_conv3x3_h_live_form): the table of profiles/r14/mask_head_forms.txt.
+
+    VIDO_MASK_HEAD_COARSE=1 in the environment (any mode): the counted launches of the mask head keep the parent's launch shapes."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-MASK_HEAD = ("k_roi_align_nhwc", "k_conv3x3_h", "k_conv1x1_b3<3", "k_conv1x1_b3ILi3", "k_mask_logit_select", "k_paste_label", "k_det_order")
+MASK_HEAD = ("k_roi_align_nhwc", "k_conv3x3_h", "k_conv3x3_h_live", "k_conv1x1_b3<3", "k_conv1x1_b3ILi3", "k_mask_logit_select", "k_paste_label", "k_det_order")
 
 
 def det(argv):
@@ -88,34 +91,49 @@ def parse(d):
 
 
 def forms():
+    import ctypes as C
     import torch
     import __graft_entry__ as ge
     ge.build()
     import vido_slam_amd as V
     from vido_slam_amd import nets
     from vido_slam_amd.nets.ops import pack_conv3x3_h
-    ctx = V.Context(width=640, height=480, max_batch=1); ops = nets.HipOps(ctx)
+    ctx = V.Context(width=640, height=480, max_batch=1); ops = nets.HipOps(ctx); lib = ctx.lib
     g = torch.Generator().manual_seed(1)
     w = torch.randn(256, 256, 3, 3, generator=g) / 48; b = torch.randn(256, generator=g).cuda(); wp = pack_conv3x3_h(w).cuda()
     x = torch.randn(100, 256, 14, 14, generator=g).cuda()
+    y = torch.empty(100, 256, 14, 14, device="cuda")
+    P = lambda t: C.c_void_p(t.data_ptr())
 
-    def timed(fn, n=200):
+    def timed(fn, n=200, blocks=3):
         for _ in range(20):
             fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(); e0.record()
-        for _ in range(n):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        return 1e3 * e0.elapsed_time(e1) / n
-    print("## conv3x3_h 256 -> 256 at 14 x 14, VIDO_CONV3X3_H_ROWS=%s: us per launch (back to back, 200 launches)" % os.environ.get("VIDO_CONV3X3_H_ROWS", "unset"))
-    for live in (1, 5, 25, 100):
+        t = []
+        for _ in range(blocks):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(n):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            t.append(1e3 * e0.elapsed_time(e1) / n)
+        return min(t), max(t)
+
+    def forced(live, rpw, cg):
+        ops._adopt_stream()
+        ctx._check(lib.vido_conv3x3_h_bias_act_form(ctx.h, P(x), P(wp), P(b), P(y), live, 256, 256, 14, 14, C.c_float(0.0), rpw, cg))
+    CAND = ((4, 1), (2, 2), (2, 1), (1, 2))
+    print("## conv3x3_h 256 -> 256 at 14 x 14: us per launch (back to back, 3 blocks of 200 launches: min / max of the blocks), VIDO_MASK_HEAD_COARSE=%s" % os.environ.get("VIDO_MASK_HEAD_COARSE", "unset"))
+    print("## form <rpw, cg> forced on a batch of exactly `live` images (the workgroups a device-side choice of that form runs; <4,1>: the coarse form of 100 images) | the counted launch on batch 100")
+    print("live | " + " | ".join("<%d,%d> %3d ch x %2d rows" % (r, c, 32 * r * c, 16 // c) for r, c in CAND) + " | counted launch: time, form the rule picks")
+    for live in (1, 2, 5, 10, 17, 25, 50, 100):
+        cells = []
+        for r, c in CAND:
+            lo, hi = timed(lambda: forced(live, r, c))
+            cells.append("%6.1f /%6.1f" % (lo, hi))
         word = torch.tensor([live], dtype=torch.int32, device="cuda")
-        t_count = timed(lambda: ops.conv3x3_h_bias_act(x, wp, b, 256, 0.0, word))
-        xs = x[:live].contiguous()
-        t_batch = timed(lambda: ops.conv3x3_h_bias_act(xs, wp, b, 256, 0.0))
-        print("live %3d: batch 100 with the count %6.1f (%d workgroups launched) | a batch of %3d %6.1f (%d workgroups)" % (
-            live, t_count, ops.ctx.lib.vido_conv3x3_h_workgroups(100, 256, 14, 14), live, t_batch, ops.ctx.lib.vido_conv3x3_h_workgroups(live, 256, 14, 14)))
+        lo, hi = timed(lambda: ops.conv3x3_h_bias_act(x, wp, b, 256, 0.0, word))
+        fine, ch, br = ops.conv3x3_h_live_form(100, 256, 14, 14, live)
+        print("%4d | " % live + " | ".join(cells) + " | %6.1f /%6.1f  %s %d ch x %d rows" % (lo, hi, "fine" if fine else "coarse", ch, br))
     ctx.close()
 
 

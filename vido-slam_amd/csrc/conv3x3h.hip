@@ -38,6 +38,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 //   <4, 1> 128 channels x 16 x 16 positions (the form above);   <2, 2> 128 channels x 8 x 16: half the K loop's length per workgroup for launches that would not fill the
 //   chip with the larger block;   <2, 1> 64 channels x 16 x 16 and <1, 2> 64 channels x 8 x 16 for 64-channel layers;   <1, 1> 32 channels x 16 x 16 for 32-channel layers.
 // (The weight ring always holds four row blocks per step: the blocks a form does not own are out-of-range copies — zeros, no traffic.)
+// A form also serves a layer with MORE channels than its workgroup owns (m0 = mtile * MT): k_conv3x3_h_live runs <1, 2> on the mask head's 256-channel layers when few of
+// the batch's images are live.
 #define C3_WPIX(BR) (((BR) + 2) * 18)                            // pixels of the window
 #define C3_XP(BR) ((16 * C3_WPIX(BR) + 511) / 512)               // window pieces per wave: 11 / 6
 #define C3_RAW(BR) (C3_XP(BR) * 8 * 256)                         // the fp32 window, padded to whole pieces per wave
@@ -47,22 +49,22 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct C3Args { const float* x; const void* wp; const float* bias; float* y; int N, Cin, Cout, H, W, nby, nbx, mt, total, nchunk; float slope; unsigned wbytes; unsigned* range_flag; const int* n_live; };      // n_live (may be null): device word, the first n_live images of the batch are computed
 
+// The body of every kernel below: the workgroup's item of a launch whose geometry (blocks per image nby x nbx, channel tiles mt = Cout / MT, items `total`, items per XCD
+// `per`) the caller states.  Any MT serves any Cout that is a multiple of it: m0 = mtile * MT, and the row blocks a form does not own are out-of-range copies.
 template <int RPW, int CG>
-__global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
+__device__ __forceinline__ void c3_body(const C3Args& A, const int nby, const int nbx, const int mt, const int total, const int per)
 {
     constexpr int BR = 16 / CG, MT = 32 * RPW * CG, WPIX = C3_WPIX(BR), XP = C3_XP(BR), RAWB = C3_RAW(BR), PLANE = C3_PLANE(BR), PBUF = C3_PBUF(BR), CK = (WPIX * 8 + 511) / 512, NMM = 9 * RPW, NRD = 2 * RPW + 2;
     extern __shared__ __attribute__((aligned(16))) char c3_lds[];
     char* L = c3_lds;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // an XCD walks a contiguous range of items, the channel block fastest.  With a live count (read here, i.e. at every replay of a captured graph) the items are those of a
+    // an XCD walks a contiguous range of items, the channel block fastest.  With a live count (read by the kernel, i.e. at every replay of a captured graph) the items are those of a
     // launch over the first n_live images — the same round-robin over the XCDs, the workgroups behind them leave before their first copy and barrier — so an image past the
     // count is neither computed nor READ (its rows may hold stale bytes: an infinity there would raise the range flag)
-    int total = A.total, per = gridDim.x >> 3;
-    if (A.n_live) { const int nl = min(max(*A.n_live, 0), A.N); total = nl * A.nby * A.nbx * A.mt; per = (total + 7) >> 3; }
     const int q8 = blockIdx.x >> 3, item = (blockIdx.x & 7) * per + q8;
     if (q8 >= per || item >= total) return;
-    const int nt = item / A.mt, mtile = item - nt * A.mt, m0 = mtile * MT;
-    const int bpi = A.nby * A.nbx, n = nt / bpi, brem = nt - n * bpi, by = brem / A.nbx, bx = brem - by * A.nbx, Y0 = by * BR, X0 = bx * 16;
+    const int nt = item / mt, mtile = item - nt * mt, m0 = mtile * MT;
+    const int bpi = nby * nbx, n = nt / bpi, brem = nt - n * bpi, by = brem / nbx, bx = brem - by * nbx, Y0 = by * BR, X0 = bx * 16;
     const int rp = CG == 1 ? w : (w & 3), rb0 = CG == 1 ? 0 : RPW * (w >> 2);      // the wave's row pair of the block, its first row block of 32 channels
     const int hw = A.H * A.W, nsteps = A.nchunk * 3;
 
@@ -218,6 +220,32 @@ __global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
         }
     }
 }
+
+template <int RPW, int CG>
+__global__ __launch_bounds__(512) void k_conv3x3_h(C3Args A)
+{
+    int total = A.total, per = gridDim.x >> 3;
+    if (A.n_live) { const int nl = min(max(*A.n_live, 0), A.N); total = nl * A.nby * A.nbx * A.mt; per = (total + 7) >> 3; }
+    c3_body<RPW, CG>(A, A.nby, A.nbx, A.mt, total, per);
+}
+
+// The counted launch of a layer of >= 128 output channels: ONE kernel holds two bodies, the coarse form <RPWC, CGC> (the host's choice for all N images, 128 channels per
+// workgroup) and the fine form C3_FINE (64 channels x 8 rows per workgroup: four times the workgroups, each with a wave's 9 matrix instructions per step instead of 36).
+// The count is read once; while the fine form's workgroups over the live images number at most fine_max the fine body runs — on a chip the coarse form's handful of
+// workgroups would leave idle the launch's time is one workgroup's K loop —, else the coarse one.  The branch is uniform over the
+// whole grid and taken before the first copy and barrier; the geometry of the chosen form comes from the count here (A.nby, A.nbx, A.mt, A.total are not used).  Every
+// output's sum runs over (chunk, dy, dx, term) in that order in every form, from the same weight pieces and the same window values: the forms agree bit for bit.
+#define C3_FINE_RPW 1
+#define C3_FINE_CG 2
+template <int RPWC, int CGC>
+__global__ __launch_bounds__(512) void k_conv3x3_h_live(C3Args A, int fine_max)
+{
+    constexpr int BRF = 16 / C3_FINE_CG, MTF = 32 * C3_FINE_RPW * C3_FINE_CG, BRC = 16 / CGC, MTC = 32 * RPWC * CGC;
+    const int nl = min(max(*A.n_live, 0), A.N), nbx = (A.W + 15) >> 4;
+    const int nbyf = (A.H + BRF - 1) / BRF, mtf = A.Cout / MTF, tf = nl * nbyf * nbx * mtf;
+    if (tf <= fine_max) c3_body<C3_FINE_RPW, C3_FINE_CG>(A, nbyf, nbx, mtf, tf, (tf + 7) >> 3);
+    else { const int nbyc = (A.H + BRC - 1) / BRC, mtc = A.Cout / MTC, tc = nl * nbyc * nbx * mtc; c3_body<RPWC, CGC>(A, nbyc, nbx, mtc, tc, (tc + 7) >> 3); }
+}
 }  // namespace
 
 extern "C" {
@@ -246,6 +274,46 @@ static int c3_block_rows(int n, int cout, int h, int w)
 /* workgroups of a launch (the caller keeps the Winograd kernel for launches that would leave most of the chip idle) */
 int vido_conv3x3_h_workgroups(int n, int cout, int h, int w) { const int br = c3_block_rows(n, cout, h, w); return n * ((h + br - 1) / br) * ((w + 15) / 16) * (cout >= 128 ? cout / 128 : 1); }
 
+/* VIDO_MASK_HEAD_COARSE=1 (read once per process): the counted launches of the mask head — this file's, and the mask pooler, the logit kernel and the label image in
+ * csrc/nets.hip — keep the launch shapes they had before the forms that follow the live count: an attribution switch, the results are the same bits. */
+int vido_mask_head_coarse(void)
+{
+    static const int v = [] { const char* e = getenv("VIDO_MASK_HEAD_COARSE"); return e && atoi(e) != 0 ? 1 : 0; }();
+    return v;
+}
+
+/* The fine form of a counted launch serves the counts whose fine workgroups number at most C3_FINE_MAX = two per CU of the chip's 256 (one is resident per CU at a time): a
+ * fine workgroup's K loop takes 0.4 of a coarse one's (256 -> 256 at 14 x 14: 31 us against 76), so one round and two rounds of them end before the coarse form's single
+ * round, three do not (profiles/r14/mask_head_forms.txt). */
+#define C3_FINE_MAX 512
+static bool c3_live_has_fine(int cout) { return cout >= 128 && !vido_mask_head_coarse(); }
+/* What vido_conv3x3_h_bias_act_n runs for a count word `live` (clamped to [0, n] as the kernel clamps it): returns 1 for the fine form, 0 for the coarse one (the
+ * uncounted launch's form), and stores the form's output channels per workgroup and rows per position block. */
+int vido_conv3x3_h_live_form(int n, int cout, int h, int w, int live, int* channels, int* block_rows)
+{
+    const int nl = live < 0 ? 0 : (live > n ? n : live);
+    constexpr int BRF = 16 / C3_FINE_CG, MTF = 32 * C3_FINE_RPW * C3_FINE_CG;
+    const bool fine = c3_live_has_fine(cout) && (long long)nl * ((h + BRF - 1) / BRF) * ((w + 15) / 16) * (cout / MTF) <= C3_FINE_MAX;
+    if (channels) *channels = fine ? MTF : (cout >= 128 ? 128 : cout);
+    if (block_rows) *block_rows = fine ? BRF : c3_block_rows(n, cout, h, w);
+    return fine ? 1 : 0;
+}
+
+/* the dynamic-LDS limits of every kernel of this file, once per device */
+static int c3_set_attrs(vido_ctx* ctx)
+{
+    static bool attr[64] = {};
+    if (!attr[ctx->device & 63]) {
+#define C3_ATTR(RPW_, CG_) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h<RPW_, CG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3_LDS(16 / CG_)))
+        C3_ATTR(4, 1); C3_ATTR(2, 2); C3_ATTR(2, 1); C3_ATTR(1, 2); C3_ATTR(1, 1);
+#undef C3_ATTR
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h_live<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(C3_LDS(16), C3_LDS(16 / C3_FINE_CG))));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h_live<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(C3_LDS(8), C3_LDS(16 / C3_FINE_CG))));
+        attr[ctx->device & 63] = true;
+    }
+    return VIDO_OK;
+}
+
 /* y = leaky_relu(conv2d(x, w, stride 1, padding 1) + bias, slope): x [n][cin][h][w], y [n][cout][h][w] f32 DEVICE tensors (4-byte aligned, y != x), bias [cout] or NULL;
  * w_packed: the weight [cout][cin][3][3] as two fp16 planes of its output channels scaled by powers of two, plane p of element (co, ci, dy, dx) at
  * [co / 32][ci / 16][dy][dx][p][32 ((ci % 16) / 8) + co % 32][ci % 8] (input channels padded to a multiple of 16 with zeros), followed by [cout] floats: the inverse scales
@@ -269,18 +337,47 @@ int vido_conv3x3_h_bias_act_n(vido_ctx* ctx, const float* x, const void* w_packe
     const int nby = (h + br - 1) / br, nbx = (w + 15) / 16, mt = cout >= 128 ? cout / 128 : 1, total = n * nby * nbx * mt;
     const int nchunk = (cin + 15) / 16;
     C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag, n_live};
-    static bool attr[64] = {};
-    if (!attr[ctx->device & 63]) {
-#define C3_ATTR(RPW_, CG_) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv3x3_h<RPW_, CG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3_LDS(16 / CG_)))
-        C3_ATTR(4, 1); C3_ATTR(2, 2); C3_ATTR(2, 1); C3_ATTR(1, 2); C3_ATTR(1, 1);
-#undef C3_ATTR
-        attr[ctx->device & 63] = true;
+    { int rc = c3_set_attrs(ctx); if (rc) return rc; }
+    if (n_live && c3_live_has_fine(cout)) {
+        // one launch, the form picked by the kernel: the grid covers the coarse form at n images and the fine form at the largest count the rule sends to it, the LDS is
+        // the larger form's (the coarse form's block is never the smaller one)
+        constexpr int BRF = 16 / C3_FINE_CG, MTF = 32 * C3_FINE_RPW * C3_FINE_CG;
+        static_assert(MTF <= 128 && 128 % MTF == 0, "the fine form's channels divide the coarse form's 128");
+        const long long fpi = (long long)((h + BRF - 1) / BRF) * nbx * (cout / MTF);              // fine workgroups per image
+        const long long tfine = std::min<long long>(n, C3_FINE_MAX / fpi) * fpi;
+        const dim3 grid((unsigned)(8 * ((std::max<long long>(total, tfine) + 7) / 8)));
+        if (br == 16) hipLaunchKernelGGL((k_conv3x3_h_live<4, 1>), grid, dim3(512), std::max(C3_LDS(16), C3_LDS(BRF)), st, A, (int)C3_FINE_MAX);
+        else hipLaunchKernelGGL((k_conv3x3_h_live<2, 2>), grid, dim3(512), std::max(C3_LDS(8), C3_LDS(BRF)), st, A, (int)C3_FINE_MAX);
+        HIP_TRY(ctx, hipGetLastError());
+        return VIDO_OK;
     }
     const dim3 grid(8 * ((total + 7) / 8));
 #define C3_LAUNCH(RPW_, CG_) hipLaunchKernelGGL((k_conv3x3_h<RPW_, CG_>), grid, dim3(512), C3_LDS(16 / CG_), st, A)
     if (cout >= 128) { if (br == 16) C3_LAUNCH(4, 1); else C3_LAUNCH(2, 2); }
     else if (cout == 64) { if (br == 16) C3_LAUNCH(2, 1); else C3_LAUNCH(1, 2); }
     else C3_LAUNCH(1, 1);
+#undef C3_LAUNCH
+    HIP_TRY(ctx, hipGetLastError());
+    return VIDO_OK;
+}
+
+/* Measurement only (tools/prof_mask_head_live.py forms): the uncounted launch in the form <rpw, cg> whatever the host rule says — 32 rpw cg channels per workgroup (cout a
+ * multiple of that, at most 128), 16 / cg block rows.  The kernels are those of the entry points above. */
+int vido_conv3x3_h_bias_act_form(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, int rpw, int cg)
+{
+    if (!ctx) return VIDO_E_INVALID;
+    const int MT = 32 * rpw * cg, form = rpw * 10 + cg;
+    if (!x || !w_packed || !y || x == y || !vido_conv3x3_h_supported(n, cin, cout, h, w) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y) & 3) || ((uintptr_t)w_packed & 15)
+        || (form != 41 && form != 22 && form != 21 && form != 12 && form != 11) || cout % MT)
+        return vido_set_error(ctx, VIDO_E_INVALID, "conv3x3_h_form: no kernel <%d, %d> for %d x %d -> %d channels at %d x %d", rpw, cg, n, cin, cout, h, w);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rc = c3_set_attrs(ctx); if (rc) return rc; }
+    hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
+    const int br = 16 / cg, nby = (h + br - 1) / br, nbx = (w + 15) / 16, mt = cout / MT, total = n * nby * nbx * mt, nchunk = (cin + 15) / 16;
+    C3Args A{x, w_packed, bias, y, n, cin, cout, h, w, nby, nbx, mt, total, nchunk, slope, (unsigned)(36ll * 16 * nchunk * cout), ctx->c1_range_flag, nullptr};
+    const dim3 grid(8 * ((total + 7) / 8));
+#define C3_LAUNCH(RPW_, CG_) hipLaunchKernelGGL((k_conv3x3_h<RPW_, CG_>), grid, dim3(512), C3_LDS(16 / CG_), st, A)
+    if (form == 41) C3_LAUNCH(4, 1); else if (form == 22) C3_LAUNCH(2, 2); else if (form == 21) C3_LAUNCH(2, 1); else if (form == 12) C3_LAUNCH(1, 2); else C3_LAUNCH(1, 1);
 #undef C3_LAUNCH
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;

@@ -108,7 +108,7 @@ __global__ void k_roi_levels(const float* __restrict__ boxes, int n, float k_min
 
 // one thread per pixel of one detection: 256 (c) multiply-adds down the channels, the detection's weight row in LDS; reads are coalesced over the pixels
 __global__ __launch_bounds__(256) void k_mask_logit_select(const float* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ b, const long long* __restrict__ labels,
-                                                           float* __restrict__ out, int c, int hw, int classes, const int* __restrict__ n_live)
+                                                           float* __restrict__ out, int c, int hw, int classes, const int* __restrict__ n_live, int batch)
 {
     __shared__ float wl[1024];
     const int n = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
@@ -124,6 +124,17 @@ __global__ __launch_bounds__(256) void k_mask_logit_select(const float* __restri
     // (float64 sums: the kernel is bound by its 80 MB of reads, and its result then differs from the library's convolution by the LIBRARY's rounding only)
     double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
     int i = 0;
+    // batch (the counted launch: a few slots on an idle chip, where the chain of strided loads is the kernel's time): 32 loads requested before the first add, then the
+    // adds of the loop below in its order — the same addends into the same four sums, so the same bits, with c / 32 round trips to memory instead of c / 4
+    if (batch) {
+        for (; i + 32 <= c; i += 32) {
+            float v[32];
+#pragma unroll
+            for (int k = 0; k < 32; k++) v[k] = f[(size_t)(i + k) * hw];
+#pragma unroll
+            for (int k = 0; k < 32; k += 4) { a0 += (double)wl[i + k] * v[k]; a1 += (double)wl[i + k + 1] * v[k + 1]; a2 += (double)wl[i + k + 2] * v[k + 2]; a3 += (double)wl[i + k + 3] * v[k + 3]; }
+        }
+    }
     for (; i + 4 <= c; i += 4) { a0 += (double)wl[i] * f[(size_t)i * hw]; a1 += (double)wl[i + 1] * f[(size_t)(i + 1) * hw]; a2 += (double)wl[i + 2] * f[(size_t)(i + 2) * hw]; a3 += (double)wl[i + 3] * f[(size_t)(i + 3) * hw]; }
     for (; i < c; i++) a0 += (double)wl[i] * f[(size_t)i * hw];
     const float v = (float)((a0 + a1) + (a2 + a3) + (b ? (double)b[lab] : 0.0));
@@ -209,15 +220,19 @@ __global__ __launch_bounds__(256) void k_bias_res_act(float* __restrict__ x, con
 //  * per channel the arithmetic order is the reference's — w1*v1 + w2*v2 + w3*v3 + w4*v4 per sample, samples accumulated row-major, one division by the sample count —
 //    so the result is bit-identical to the oracle's restatement;
 //  * results go to an LDS tile [64 channels][bins] (odd pitch) and leave as ONE contiguous run of out[roi][c0 .. c0+63][PH][PW]: full-line stores although lanes run over channels.
+//  * SPLIT (the counted mask pooler: a few live rois of 14 x 14 bins): a roi's bins are dealt over blockIdx.z, seg_bins per workgroup, so that a wave walks seg_bins / 4 bins
+//    one after the other instead of PH PW / 4; the tile holds the segment and leaves as one contiguous run of bins PER CHANNEL.  Each element is computed as above.
 struct RoiLevels { const float* feat[4]; int H[4], W[4]; float scale[4]; };     // channels-last maps
-template <int SR /* sampling ratio known at compile time (2: the node's setting; the 4 x 4 taps of a bin are then 16 independent loads in flight), 0: run-time / adaptive */>
+template <int SR /* sampling ratio known at compile time (2: the node's setting; the 4 x 4 taps of a bin are then 16 independent loads in flight), 0: run-time / adaptive */,
+          bool SPLIT /* a roi's bins are dealt over blockIdx.z, seg_bins each (the counted mask pooler); false: one workgroup per (roi, channel group), seg_bins unused */>
 __global__ __launch_bounds__(256) void k_roi_align_nhwc(RoiLevels L, int C, const float* __restrict__ rois, int roi_stride /* 5: (batch, x1, y1, x2, y2); 4: (x1, y1, x2, y2) */,
-                                                        const int* __restrict__ level /* null: level 0 */, int PH, int PW, int sampling, float* __restrict__ out, const int* __restrict__ n_live /* null: every roi */)
+                                                        const int* __restrict__ level /* null: level 0 */, int PH, int PW, int sampling, float* __restrict__ out, const int* __restrict__ n_live /* null: every roi */,
+                                                        int seg_bins /* SPLIT: blockIdx.z owns bins [z seg_bins, (z + 1) seg_bins) of the roi */)
 {
     extern __shared__ __attribute__((aligned(16))) float rl_tile[];
     if (n_live && (int)blockIdx.x >= *n_live) return;                         // (uniform per workgroup, before the barrier) a roi behind the live count: its rows of `out` stay as they are
     const int i = blockIdx.x, c0 = blockIdx.y * 64, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nbin = PH * PW, pitch = nbin | 1;
+    const int nbin = PH * PW, b0 = SPLIT ? blockIdx.z * seg_bins : 0, nsb = SPLIT ? min(seg_bins, nbin - b0) : nbin, pitch = (SPLIT ? seg_bins : nbin) | 1;      // (the last segment may be ragged)
     const float* r = rois + (size_t)roi_stride * i;
     const int l = level ? level[i] : 0, bi = roi_stride == 5 ? (int)r[0] : 0;
     const float* box = r + (roi_stride == 5 ? 1 : 0);
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(256) void k_roi_align_nhwc(RoiLevels L, int C, cons
         w1 = hy * hx; w2 = hy * lx; w3 = ly * hx; w4 = ly * lx;
         return out;
     };
-    for (int bin = wave; bin < nbin; bin += 4) {
+    for (int bin = b0 + wave; bin < b0 + nsb; bin += 4) {
         const int ph = bin / PW, pw = bin - ph * PW;
         float acc = 0.f;
         if (SR == 2) {
@@ -271,12 +286,13 @@ __global__ __launch_bounds__(256) void k_roi_align_nhwc(RoiLevels L, int C, cons
                 }
             }
         }
-        rl_tile[lane * pitch + bin] = acc / count;
+        rl_tile[lane * pitch + (bin - b0)] = acc / count;
     }
     __syncthreads();
-    const int nc = min(64, C - c0), total = nc * nbin;
-    float* o = out + ((size_t)i * C + c0) * nbin;
-    for (int e = threadIdx.x; e < total; e += 256) { const int cc = e / nbin; o[e] = rl_tile[cc * pitch + (e - cc * nbin)]; }
+    const int nc = min(64, C - c0), total = nc * nsb;                         // per channel a contiguous run of the segment's bins
+    float* o = out + ((size_t)i * C + c0) * nbin + b0;
+    if (SPLIT) for (int e = threadIdx.x; e < total; e += 256) { const int cc = e / nsb, k = e - cc * nsb; o[(size_t)cc * nbin + k] = rl_tile[cc * pitch + k]; }
+    else for (int e = threadIdx.x; e < total; e += 256) { const int cc = e / nbin; o[e] = rl_tile[cc * pitch + (e - cc * nbin)]; }      // ONE contiguous run
 }
 // [B][C][H][W] -> [B][H][W][C] through a 64 x 64 LDS tile: coalesced 256-byte runs on both sides
 __global__ __launch_bounds__(256) void k_nchw_to_nhwc(const float* __restrict__ src, int C, int HW, float* __restrict__ dst)
@@ -453,11 +469,12 @@ __global__ __launch_bounds__(256) void k_paste_prepare(const float* __restrict__
     det[i] = d;
 }
 __global__ __launch_bounds__(256) void k_paste_label(const float* __restrict__ masks /*[n,1,M,M]*/, const PasteDet* __restrict__ det, int n, int M, int padding, float thresh,
-                                                     int H, int W, uint8_t* __restrict__ out)
+                                                     int H, int W, uint8_t* __restrict__ out, const int* __restrict__ n_live /* null: all n */)
 {
     __shared__ PasteDet sd[128];
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     const int Mp = M + 2 * padding;
+    if (n_live) n = min(max(*n_live, 0), n);                          // the walk stops at the live count: the slots behind it have label 0 and add nothing
     unsigned acc = 0;
     for (int d0 = 0; d0 < n; d0 += 128) {
         __syncthreads();
@@ -736,12 +753,15 @@ __global__ __launch_bounds__(256) void k_deconv4s2_dw(const float* __restrict__ 
 
 // dynamic-LDS limit of k_roi_align_nhwc: raised only when a call needs more than any earlier one (the attribute call is kept out of hipGraph captures, whose
 // replays run with the limit the warm-up calls have set)
+#define ROI_SEG_BINS 16
 static int roi_lds_limit(vido_ctx* ctx, size_t lds)
 {
     static size_t have = 48 * 1024;
     if (lds <= have) return VIDO_OK;
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_roi_align_nhwc<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     have = lds;
     return VIDO_OK;
 }
@@ -829,7 +849,8 @@ int vido_mask_logit_select_n(vido_ctx* ctx, const float* feat, const float* w, c
     if (!feat || !w || !labels || !out || n < 1 || c < 1 || c > 1024 || hw < 1 || classes < 1) return vido_set_error(ctx, VIDO_E_INVALID, "mask_logit_select: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    hipLaunchKernelGGL(k_mask_logit_select, dim3((unsigned)((hw + 255) / 256), (unsigned)n), dim3(256), 0, st, feat, w, b, labels, out, c, hw, classes, n_live);
+    hipLaunchKernelGGL(k_mask_logit_select, dim3((unsigned)((hw + 255) / 256), (unsigned)n), dim3(256), 0, st, feat, w, b, labels, out, c, hw, classes, n_live,
+                       n_live && !vido_mask_head_coarse() ? 1 : 0);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }
@@ -994,8 +1015,8 @@ int vido_roi_align(vido_ctx* ctx, const float* feat, int B, int C, int H, int W,
     const size_t lds = (size_t)64 * ((pooled_h * pooled_w) | 1) * sizeof(float);
     if (lds > 150 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "roi_align: pooled size %d x %d too large", pooled_h, pooled_w);
     { int rc = roi_lds_limit(ctx, lds); if (rc) return rc; }
-    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr);
-    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr);
+    if (sampling_ratio == 2) hipLaunchKernelGGL((k_roi_align_nhwc<2, false>), dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr, 0);
+    else hipLaunchKernelGGL((k_roi_align_nhwc<0, false>), dim3(n_rois, (C + 63) / 64), dim3(256), lds, st, L, C, dr, 5, (const int*)nullptr, pooled_h, pooled_w, sampling_ratio, dout, (const int*)nullptr, 0);
     HIP_TRY(ctx, hipGetLastError());
     if (!on_device) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1128,8 +1149,16 @@ int vido_roi_align_fpn_nhwc_n(vido_ctx* ctx, const float* const feat[4], const i
     const size_t lds = (size_t)64 * ((pooled_h * pooled_w) | 1) * sizeof(float);
     if (lds > 150 * 1024) return vido_set_error(ctx, VIDO_E_CAPACITY, "roi_align_fpn: pooled size %d x %d too large", pooled_h, pooled_w);
     { int rc = roi_lds_limit(ctx, lds); if (rc) return rc; }
-    if (sampling_ratio == 2) hipLaunchKernelGGL(k_roi_align_nhwc<2>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live);
-    else hipLaunchKernelGGL(k_roi_align_nhwc<0>, dim3(n, (C + 63) / 64), dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live);
+    // a counted launch (the mask pooler: a few live rois of 14 x 14 bins on an otherwise idle chip) splits a roi's bins over blockIdx.z, ROI_SEG_BINS per workgroup: a wave
+    // walks 4 bins one after the other instead of 49, and each element is computed as before.  VIDO_ROI_SEG_BINS (read once) moves the split for measurements.
+    static const int seg_env = [] { const char* e = getenv("VIDO_ROI_SEG_BINS"); return e ? atoi(e) : 0; }();
+    const int nbin = pooled_h * pooled_w, sb = n_live && !vido_mask_head_coarse() ? std::min(nbin, seg_env > 0 ? seg_env : ROI_SEG_BINS) : nbin, nseg = (nbin + sb - 1) / sb;
+    const dim3 grid(n, (C + 63) / 64, nseg);
+    if (nseg > 1) {
+        if (sampling_ratio == 2) hipLaunchKernelGGL((k_roi_align_nhwc<2, true>), grid, dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live, sb);
+        else hipLaunchKernelGGL((k_roi_align_nhwc<0, true>), grid, dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live, sb);
+    } else if (sampling_ratio == 2) hipLaunchKernelGGL((k_roi_align_nhwc<2, false>), grid, dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live, 0);
+    else hipLaunchKernelGGL((k_roi_align_nhwc<0, false>), grid, dim3(256), lds, st, L, C, boxes, 4, level, pooled_h, pooled_w, sampling_ratio, out, n_live, 0);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }
@@ -1139,8 +1168,15 @@ int vido_roi_align_fpn_nhwc_n(vido_ctx* ctx, const float* const feat[4], const i
  * (pasted mask) * class index, modulo 256.  n may be 0 (out is cleared). */
 int vido_mask_label_image(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W, uint8_t* out)
 {
+    return vido_mask_label_image_n(ctx, masks, boxes, labels, n, M, padding, thresh, H, W, out, nullptr);
+}
+/* ... for a list whose slots behind *n_live (DEVICE int32 word read by the kernel, clamped to [0, n]; NULL: none) all have label 0 — the static head orders the live slots
+ * first —: the walk over the list stops at the count, the image is the same. */
+int vido_mask_label_image_n(vido_ctx* ctx, const float* masks, const float* boxes, const int64_t* labels, int n, int M, int padding, float thresh, int H, int W, uint8_t* out,
+                            const int32_t* n_live)
+{
     if (!ctx) return VIDO_E_INVALID;
-    if (!out || H < 1 || W < 1 || n < 0 || M < 1 || padding < 0 || (n && (!masks || !boxes || !labels))) return vido_set_error(ctx, VIDO_E_INVALID, "mask_label_image: bad arguments");
+    if (!out || H < 1 || W < 1 || n < 0 || M < 1 || padding < 0 || (n && (!masks || !boxes || !labels)) || ((uintptr_t)n_live & 3)) return vido_set_error(ctx, VIDO_E_INVALID, "mask_label_image: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
     if (n == 0) { HIP_TRY(ctx, hipMemsetAsync(out, 0, (size_t)H * W, st)); return VIDO_OK; }
@@ -1148,7 +1184,7 @@ int vido_mask_label_image(vido_ctx* ctx, const float* masks, const float* boxes,
     int rc = net_scratch(ctx, al256((size_t)n * sizeof(PasteDet)), &S); if (rc) return rc;
     PasteDet* det = (PasteDet*)S->d;
     hipLaunchKernelGGL(k_paste_prepare, dim3((n + 255) / 256), dim3(256), 0, st, boxes, labels, n, M, padding, det);
-    hipLaunchKernelGGL(k_paste_label, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, st, masks, det, n, M, padding, thresh, H, W, out);
+    hipLaunchKernelGGL(k_paste_label, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, st, masks, det, n, M, padding, thresh, H, W, out, vido_mask_head_coarse() ? (const int*)nullptr : (const int*)n_live);
     HIP_TRY(ctx, hipGetLastError());
     return VIDO_OK;
 }

@@ -723,7 +723,7 @@ def _heads_static(self, feats, logits, deltas, image_hw, cap=None, confidence=No
     out = dict(boxes=boxes, scores=scores, labels=labels, n_det=n_det, proposals=proposals, objectness=objectness, n_proposals=(objectness >= 0).sum())
     if confidence is not None:
         order, lab, n_live, n32 = self.rpn.ops.det_order(scores.contiguous(), labels.contiguous(), n_det.reshape(1), confidence, count32=True)
-        out.update(order=order, labels_ordered=lab, n_live=n_live,
+        out.update(order=order, labels_ordered=lab, n_live=n_live, n_live32=n32,
                    masks=mh.predictor.selected(mh.feature_extractor(maps, boxes[order], n32), lab, n32))      # (a live slot keeps its own label in `lab`)
         return out
     out["masks"] = mh.predictor.selected(mh.feature_extractor(maps, boxes), labels)      # (only each slot's own class channel: vido_mask_logit_select)
@@ -812,7 +812,7 @@ def analyse_image_static(net, feats, logits, deltas, out_hw, feed=(1088, 800), c
             raise ValueError("label_mode='instance': %d slots, ids are u8" % cap)
         img = ops.mask_instance_image(masks, boxes[order], labels, H, W, id_base=id_base)
     else:
-        img = ops.mask_label_image(masks, boxes[order], labels, H, W)
+        img = ops.mask_label_image(masks, boxes[order], labels, H, W, n_live=out["n_live32"]) if "n_live32" in out else ops.mask_label_image(masks, boxes[order], labels, H, W)
     return img, labels, n_live, out["n_det"]
 
 

@@ -425,6 +425,12 @@ class HipOps:
                                                                C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope), self._live_ptr(n_live)))
         return out
 
+    def conv3x3_h_live_form(self, n, cout, h, w, live):
+        """(fine, channels per workgroup, block rows) of the form the counted conv3x3_h launch runs at the count word `live` (vido_conv3x3_h_live_form)"""
+        ch, br = C.c_int(), C.c_int()
+        fine = self.ctx.lib.vido_conv3x3_h_live_form(int(n), int(cout), int(h), int(w), int(live), C.byref(ch), C.byref(br))
+        return bool(fine), ch.value, br.value
+
     def fc_h(self, x, w_packed, bias, outs, slope=1.0):
         """leaky_relu(x @ w.T + bias, slope) for x [rows, k] f32 as a split-fp16 matrix-pipe GEMM split over k (csrc/fch.hip); w_packed = pack_conv1x1(w[:, :, None, None], 3).
         None when the library does not take the shape."""
@@ -662,15 +668,16 @@ class HipOps:
                                                                C.c_void_p(out.data_ptr()), self._live_ptr(n_live)))
         return out
 
-    def mask_label_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1):
-        """Masker + label image: masks [n,1,M,M], boxes [n,4] (output image), labels [n] int64 -> [H,W] u8."""
+    def mask_label_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, n_live=None):
+        """Masker + label image: masks [n,1,M,M], boxes [n,4] (output image), labels [n] int64 -> [H,W] u8.  n_live (one int32 device word): the slots behind it all have
+        label 0 (the static head's ordered list) and the walk stops there (vido_mask_label_image_n); the image is the same."""
         out = torch.empty((H, W), device=masks.device, dtype=torch.uint8)
         n = masks.shape[0]
         masks = masks.contiguous().float(); boxes = boxes.contiguous().float(); labels = labels.contiguous().to(torch.int64)
         self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_label_image(self.ctx.h, C.c_void_p(masks.data_ptr()) if n else None, C.c_void_p(boxes.data_ptr()) if n else None,
-                                                           C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
-                                                           C.c_void_p(out.data_ptr())))
+        self.ctx._check(self.ctx.lib.vido_mask_label_image_n(self.ctx.h, C.c_void_p(masks.data_ptr()) if n else None, C.c_void_p(boxes.data_ptr()) if n else None,
+                                                             C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
+                                                             C.c_void_p(out.data_ptr()), self._live_ptr(n_live)))
         return out
 
     def mask_propagate(self, mask, flow, depth=None, out=None, stats=None):
