@@ -121,6 +121,33 @@ int vido_orb_describe_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n
  * pointers and the call only enqueues on the ctx stream. */
 int vido_hamming_match(vido_ctx* ctx, const uint8_t* a, int na, const uint8_t* b, int nb,
                        int32_t* idx_out, int32_t* dist_out, int on_device);
+/* Windowed matcher: for each of the nq queries (256-bit descriptor q_desc[32 i ..], position q_xy[2 i ..] in pixels, pyramid level q_level[i]) the best and second best of
+ * the nt train entries (t_desc, t_xy, t_level) inside a spatial window and a level gate, an acceptance verdict, and optionally a one-to-one rule.  No reference call site
+ * (as above); bit-exact against tests/refimpl/hamming_window_np.py.
+ *   candidates of query i: the train entries j with  fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius  (one fp32 subtraction and one compare per term: a SQUARE window,
+ *             edge included, independent of contraction and evaluation order)  and  level_tol < 0 || |t_level[j] - q_level[i]| <= level_tol.  A NaN or infinite
+ *             coordinate fails the window test: such a query has no candidates, such a train entry is nobody's candidate.
+ *   best      the candidate with the smallest Hamming distance, lowest j on ties; dist_out[i] = that distance, -1 with no candidate.
+ *   second    dist2_out[i] = the smallest distance among the candidates other than the best one (a duplicate descriptor gives dist2 == dist), -1 with fewer than two.
+ *   status_out[i], the first test that fires decides:
+ *             1  no candidate
+ *             2  dist > max_dist
+ *             3  the ratio test failed.  It applies only when ratio_num > 0 and dist2 >= 0, and passes iff dist * ratio_den < dist2 * ratio_num (integers).
+ *             4  only with unique != 0: among the queries that reached this point with the same best j, the one with the smallest (dist, i) keeps it; the others get 4
+ *                (they do not fall back to their second candidate)
+ *             0  matched
+ *   idx_out[i] = j for status 0, otherwise -1.  stats_out[s] = number of queries with status s (5 x i32; may be NULL).  Every element of every output is written.
+ * ratio_num == 0 switches the ratio test off (ratio_den is then ignored); otherwise 0 < ratio_num <= ratio_den <= 1024.  A ratio outside that, a radius that is negative,
+ * NaN or infinite, a negative count or a null array with a non-zero count: VIDO_E_INVALID.  nq == 0 is a successful no-op (stats_out, when given, is zeroed); nt == 0
+ * gives status 1 everywhere.  Results depend neither on the order in which train entries are processed nor on launch geometry: integer minima and integer sums decide
+ * everything (the one-to-one rule is a 64-bit atomic minimum of dist << 32 | i into an owner plane the context owns, then a resolve pass).
+ * on_device != 0: every pointer, stats_out included, is a device pointer (4-byte aligned) and the call only enqueues on the ctx stream (two launches, three with unique; no
+ * memset); the context's buffers grow on demand, so a first call of the largest size comes before a stream capture.  Otherwise the call returns with the results in the
+ * caller's arrays.  One set of buffers per context: calls on one context do not overlap. */
+int vido_hamming_match_window(vido_ctx* ctx, const uint8_t* q_desc, const float* q_xy, const int32_t* q_level, int nq,
+                              const uint8_t* t_desc, const float* t_xy, const int32_t* t_level, int nt,
+                              float radius, int level_tol, int max_dist, int ratio_num, int ratio_den, int unique,
+                              int32_t* idx_out, int32_t* dist_out, int32_t* dist2_out, int32_t* status_out, int32_t stats_out[5], int on_device);
 
 /* ---- Tracking front-end, data-parallel stages ---------------------------------------------------------
  * Frame maps (depth f32, flow f32x2, mask i32; width*height of the ctx) live in device "slots"
@@ -727,6 +754,18 @@ int         vido_system_mask_split_stats(const vido_system* sys, int32_t out[4])
  * the last frame's point it came from, xyl [3n] = lrintf(xy / scale[level]) and the seed's level (-1 x 3: no seed), dist [n] (-1: no evidence), rejected [n], seed_desc [32n].
  * *n_out = n (0 with the option off or before the second frame); VIDO_E_CAPACITY if n > cap. */
 int         vido_system_get_verify_points(const vido_system* sys, float* xy, float* prev_xy, int32_t* xyl, int32_t* dist, uint8_t* rejected, uint8_t* seed_desc, int cap, int* n_out);
+/* Verify.Recover: 1 (needs Verify.Descriptor: 1): the static points the verification has just rejected are searched among the frame's own static
+ * keypoints with vido_hamming_match_window (one call per frame, unique = 1; keys Verify.RecoverRadius / RecoverLevelTol / RecoverMaxHamming / RecoverRatio); a re-found
+ * point moves onto its keypoint and is no longer rejected, so vido_system_get_verify_stats' n_rejected counts what STAYS rejected.  n_tried: the points searched on the last
+ * frame, n_recovered: those re-found.  Both 0 with the option off. */
+int         vido_system_get_recover_stats(const vido_system* sys, int* n_tried, int* n_recovered);
+/* Debug read of the same frame's per-point state, index-aligned with vido_system_get_verify_points (any array may be NULL): status [n] (-1: not searched, else the op's
+ * status, 0 = re-found), idx [n] the matched entry of the train list (-1: none), match_xy [2n] its position ((-1, -1): none), dist / dist2 [n] (-1: none), after [5n] per
+ * point x, y, depth and the last frame's flow x, y as the step left them (what the pose stages read).  The train list of the frame's call — the frame's static candidate
+ * list as Frame::Frame built it — comes back as train_xy [2 nt], train_level [nt], train_desc [32 nt], train_depth [nt], so that a caller can recompute the call.
+ * *n_out = n, *n_train_out = nt (both 0 with the option off or before the second frame); VIDO_E_CAPACITY if n > cap or nt > train_cap. */
+int         vido_system_get_recover_points(const vido_system* sys, int32_t* status, int32_t* idx, float* match_xy, int32_t* dist, int32_t* dist2, float* after, int cap, int* n_out,
+                                           float* train_xy, int32_t* train_level, uint8_t* train_desc, float* train_depth, int train_cap, int* n_train_out);
 int         vido_system_save_results(vido_system* sys, const char* prefix);
 /* the vido_ctx the system's tracker runs on (NULL before the first frame): lets a caller share the device / query timings */
 vido_ctx*   vido_system_context(vido_system* sys);

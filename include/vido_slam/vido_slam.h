@@ -103,6 +103,11 @@ public:
     std::vector<int> mvStatSeedLevelTmp, mvStatSeedLevel; std::vector<unsigned char> mvStatSeedDescTmp, mvStatSeedDesc;
     std::vector<int> mvStatVerifyXYL, mvStatVerifyDist; std::vector<unsigned char> mvStatVerifyRejected;
     std::vector<float> mvStatVerifyXY;      /* per point: its position when it was checked (x, y) and the last frame's point it came from (x, y) */
+    /* extension (Verify.Recover: 1), index-aligned with mvStatKeys: mvStatRecoverStatus -1 = not searched (the point was not rejected), else the status of
+       vido_hamming_match_window (0 = re-found); mvStatRecoverIdx the matched entry of the frame's static candidate list (mvStatKeysTmp as Frame::Frame built it), -1 none;
+       mvStatRecoverXY (x, y) that keypoint's position, (-1, -1) none; mvStatRecoverDist / Dist2 best and second-best distance (-1: none); mvStatRecoverAfter per point
+       (x, y, depth, last frame's flow x, y) as the step left them: for a re-found point the keypoint, its depth and keypoint - last position, else unchanged. */
+    std::vector<int> mvStatRecoverStatus, mvStatRecoverIdx, mvStatRecoverDist, mvStatRecoverDist2; std::vector<float> mvStatRecoverXY, mvStatRecoverAfter;
     Frame *mpPrevFrame = nullptr, *mpNextFrame = nullptr;
 };
 
@@ -188,6 +193,16 @@ public:
     void VerifyStaticDescriptors();
     void GetVerifyStats(int* n_checked, int* n_rejected) const { if (n_checked) *n_checked = nVerifyChecked; if (n_rejected) *n_rejected = nVerifyRejected; }
     bool bVerifyDescriptor = false; int nVerifyMaxHamming = 64, nVerifyChecked = 0, nVerifyRejected = 0;
+    /* extension (Verify.Recover: 1, needs Verify.Descriptor: 1): the points VerifyStaticDescriptors has just rejected are searched among the frame's own static keypoints
+       (mvStatKeysTmp with their descriptors and levels) in a window around the flow-predicted position: one vido_hamming_match_window call per frame, unique = 1.  A
+       re-found point moves to the keypoint (mvStatKeys[i].pt), takes its depth (mvStatDepth[i]), is no longer rejected (nVerifyRejected counts what stays rejected) and
+       the last frame's mvCorres[i] / mvFlowNext[i] follow; seed descriptor and level stay.  nRecoverTried / nRecovered: counts of the last frame; mvRecoverTrain*: the
+       train list of the last call (read-back).  Keys Verify.RecoverRadius (px at level 0), Verify.RecoverLevelTol, Verify.RecoverMaxHamming, Verify.RecoverRatio
+       (taken as round(1024 r) / 1024, 0 = off): defaults from profiles/r15/descriptor_recover.txt. */
+    void RecoverRejectedStatic();
+    void GetRecoverStats(int* n_tried, int* n_recovered) const { if (n_tried) *n_tried = nRecoverTried; if (n_recovered) *n_recovered = nRecovered; }
+    bool bVerifyRecover = false; float fRecoverRadius = 32.f; int nRecoverLevelTol = 1, nRecoverMaxHamming = 50, nRecoverRatioNum = 0, nRecoverTried = 0, nRecovered = 0;
+    std::vector<float> mvRecoverTrainXY, mvRecoverTrainDepth; std::vector<int> mvRecoverTrainLevel; std::vector<unsigned char> mvRecoverTrainDesc;
     /* extension (Mask.PropagateMissing: 1): a GrabImageRGBD call with an EMPTY mask, or a GrabImageRGBDDevice call with a null mask pointer, takes the frame's mask from
        the previous frame: its mask warped through its flow, the nearer (pre-scaled) depth winning a collision (vido_frame_propagate_mask), before any list is built.
        The first frame of a sequence needs a mask.  nMaskPropagated: 1 when the last frame's mask was propagated.  With the key at 0 (default) nothing changes. */

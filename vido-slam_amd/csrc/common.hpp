@@ -46,6 +46,7 @@ struct vido_ctx {
     TrackState* trk = nullptr;
     BaState* ba = nullptr;
     struct HamState* ham = nullptr;
+    struct HamWinState* hamwin = nullptr;    // hamwin.hip: chunk partials, owner plane and staging of vido_hamming_match_window
     struct PoseState* pose = nullptr;
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
@@ -91,6 +92,7 @@ void maskprop_state_destroy(vido_ctx* ctx);
 void maskassoc_state_destroy(vido_ctx* ctx);
 void maskcc_state_destroy(vido_ctx* ctx);
 void ham_state_destroy(vido_ctx* ctx);
+void hamwin_state_destroy(vido_ctx* ctx);
 void pose_state_destroy(vido_ctx* ctx);
 void ba_state_destroy(vido_ctx* ctx);
 // device-resident inputs of the local-window solve (bawin.hip assembles them, ba.hip solves): observations sorted by camera, landmark-major slot tables, points (in / out)

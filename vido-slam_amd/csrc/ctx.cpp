@@ -94,6 +94,7 @@ void vido_destroy(vido_ctx* ctx)
     maskassoc_state_destroy(ctx);
     maskcc_state_destroy(ctx);
     ham_state_destroy(ctx);
+    hamwin_state_destroy(ctx);
     pose_state_destroy(ctx);
     ba_state_destroy(ctx);
     net_state_destroy(ctx);

@@ -884,6 +884,11 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
     if (kv.count("RansacSeed")) ransac_seed = (unsigned)num(kv, "RansacSeed");
     bVerifyDescriptor = num(kv, "Verify.Descriptor", 0) != 0; nVerifyMaxHamming = (int)num(kv, "Verify.MaxHamming", 70);      // (70: profiles/r8/descriptor_verify.txt)
     g_verify_desc = bVerifyDescriptor;
+    bVerifyRecover = bVerifyDescriptor && num(kv, "Verify.Recover", 0) != 0;      // (the defaults of the four keys: profiles/r15/descriptor_recover.txt)
+    fRecoverRadius = (float)num(kv, "Verify.RecoverRadius", 32); nRecoverLevelTol = (int)num(kv, "Verify.RecoverLevelTol", 1); nRecoverMaxHamming = (int)num(kv, "Verify.RecoverMaxHamming", 50);
+    nRecoverRatioNum = (int)lrint(1024.0 * num(kv, "Verify.RecoverRatio", 0));
+    if (bVerifyRecover && (!(fRecoverRadius >= 0.f) || !(fRecoverRadius < 1e9f) || nRecoverRatioNum < 0 || nRecoverRatioNum > 1024))
+        throw std::runtime_error("Tracking: Verify.RecoverRadius must be finite and >= 0, Verify.RecoverRatio in [0, 1]");
     bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
     bSplitInstances = num(kv, "Mask.SplitInstances", 0) != 0; nMinInstanceArea = (int)num(kv, "Mask.MinInstanceArea", 1);
     all_timing.assign(5, 0.f);
@@ -1037,10 +1042,11 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
         for (int i = 0; i < no; i++) { oxy[2 * i] = F->mvObjKeys[i].pt.x; oxy[2 * i + 1] = F->mvObjKeys[i].pt.y; }
         if (no) check(vido_gather_object_depth_label(c, slot_cur_, oxy.data(), no, mThDepthObj, F->mvObjDepth.data(), F->vSemObjLabel.data()), "gather_object");
         TemperalMatch.assign(F->N_s, -1);
-        nVerifyChecked = nVerifyRejected = 0;
+        nVerifyChecked = nVerifyRejected = 0; nRecoverTried = nRecovered = 0;
         if (bVerifyDescriptor) {                               // the seeds travel with the points (last.mvCorres is index-aligned with last.mvStatKeysTmp); then one launch for the frame
             F->mvStatSeedLevel = mpLastFrame->mvStatSeedLevelTmp; F->mvStatSeedDesc = mpLastFrame->mvStatSeedDescTmp;
             VerifyStaticDescriptors();
+            if (bVerifyRecover) RecoverRejectedStatic();
         }
     }
     mpCurrentFrame->vObjLabel.assign(mpCurrentFrame->mvObjKeys.size(), -2);
@@ -1084,6 +1090,55 @@ void Tracking::VerifyStaticDescriptors()
         if (dist[k] < 0) continue;
         nVerifyChecked++;
         if (dist[k] > nVerifyMaxHamming) { F->mvStatVerifyRejected[which[k]] = 1; nVerifyRejected++; }
+    }
+}
+
+// Verify.Recover (no reference counterpart).  Straight after the verdicts: the rejected points are the queries (seed descriptor, flow-predicted position, seed level), the
+// frame's own static candidates — the keypoints that passed Frame::Frame's mask / depth / flow filter, with the descriptors and levels Frame::Frame kept as their seeds —
+// the train set, one vido_hamming_match_window call with unique = 1.  A status-0 point moves onto its keypoint; everything that carries the correspondence follows:
+// this frame's mvStatKeys[i].pt / mvStatDepth[i] (GetInitModelCam, PoseOptimizationNew, RenewFrameInfo read them) and the last frame's mvCorres[i] / mvFlowNext[i]
+// (PoseOptimizationFlow2Cam and Frame::ObtainFlowDepthCamera read the flow).  The seed stays the original one.  Two re-found points never share a keypoint (unique); a
+// re-found point may coincide with a point that was never rejected and sits on the same keypoint: that is left alone.
+void Tracking::RecoverRejectedStatic()
+{
+    Frame *F = mpCurrentFrame, *L = mpLastFrame; const int n = F->N_s;
+    F->mvStatRecoverStatus.assign(n, -1); F->mvStatRecoverIdx.assign(n, -1); F->mvStatRecoverDist.assign(n, -1); F->mvStatRecoverDist2.assign(n, -1); F->mvStatRecoverXY.assign(2 * (size_t)n, -1.f);
+    int nt = (int)F->mvStatKeysTmp.size();
+    if ((int)F->mvStatSeedLevelTmp.size() != nt || (int)F->mvStatSeedDescTmp.size() != 32 * nt || (int)F->mvStatDepthTmp.size() != nt) nt = 0;
+    mvRecoverTrainXY.resize(2 * (size_t)nt); mvRecoverTrainDepth.assign(F->mvStatDepthTmp.begin(), F->mvStatDepthTmp.begin() + nt);
+    mvRecoverTrainLevel.assign(F->mvStatSeedLevelTmp.begin(), F->mvStatSeedLevelTmp.begin() + nt); mvRecoverTrainDesc.assign(F->mvStatSeedDescTmp.begin(), F->mvStatSeedDescTmp.begin() + 32 * (size_t)nt);
+    for (int j = 0; j < nt; j++) { mvRecoverTrainXY[2 * (size_t)j] = F->mvStatKeysTmp[j].pt.x; mvRecoverTrainXY[2 * (size_t)j + 1] = F->mvStatKeysTmp[j].pt.y; }
+    std::vector<int> which;
+    if ((int)F->mvStatVerifyRejected.size() == n && (int)F->mvStatSeedLevel.size() == n && (int)L->mvCorres.size() == n && (int)L->mvFlowNext.size() == n && (int)L->mvStatKeys.size() == n)
+        for (int i = 0; i < n; i++) if (F->mvStatVerifyRejected[i]) which.push_back(i);
+    const int m = (int)which.size();
+    nRecoverTried = m;
+    if (m > 0) {
+        std::vector<uint8_t> qd(32 * (size_t)m); std::vector<float> qxy(2 * (size_t)m); std::vector<int32_t> ql(m), idx(m), dist(m), dist2(m), status(m); int32_t stats[5];
+        for (int k = 0; k < m; k++) {
+            const int i = which[k];
+            memcpy(&qd[32 * (size_t)k], &F->mvStatSeedDesc[32 * (size_t)i], 32); qxy[2 * (size_t)k] = F->mvStatKeys[i].pt.x; qxy[2 * (size_t)k + 1] = F->mvStatKeys[i].pt.y; ql[k] = F->mvStatSeedLevel[i];
+        }
+        vido_ctx* c = g_ctx;
+        if (timed_call([&]() -> int { return vido_hamming_match_window(c, qd.data(), qxy.data(), ql.data(), m, mvRecoverTrainDesc.data(), mvRecoverTrainXY.data(), mvRecoverTrainLevel.data(), nt,
+                                                                       fRecoverRadius, nRecoverLevelTol, nRecoverMaxHamming, nRecoverRatioNum, 1024, 1, idx.data(), dist.data(), dist2.data(),
+                                                                       status.data(), stats, 0); }, "hamming_match_window") != VIDO_OK) throw std::runtime_error(vido_last_error(c));
+        for (int k = 0; k < m; k++) {
+            const int i = which[k], j = idx[k];
+            F->mvStatRecoverStatus[i] = status[k]; F->mvStatRecoverIdx[i] = j; F->mvStatRecoverDist[i] = dist[k]; F->mvStatRecoverDist2[i] = dist2[k];
+            if (status[k] != 0 || j < 0 || j >= nt) continue;
+            const cv::Point2f pt = F->mvStatKeysTmp[j].pt;
+            F->mvStatRecoverXY[2 * (size_t)i] = pt.x; F->mvStatRecoverXY[2 * (size_t)i + 1] = pt.y;
+            F->mvStatKeys[i].pt = pt; F->mvStatDepth[i] = F->mvStatDepthTmp[j];
+            L->mvCorres[i].pt = pt; L->mvFlowNext[i] = cv::Point2f(pt.x - L->mvStatKeys[i].pt.x, pt.y - L->mvStatKeys[i].pt.y);
+            F->mvStatVerifyRejected[i] = 0; nVerifyRejected--; nRecovered++;
+        }
+    }
+    F->mvStatRecoverAfter.resize(5 * (size_t)n);
+    const bool flows = (int)L->mvFlowNext.size() == n;
+    for (int i = 0; i < n; i++) {
+        float* o = &F->mvStatRecoverAfter[5 * (size_t)i];
+        o[0] = F->mvStatKeys[i].pt.x; o[1] = F->mvStatKeys[i].pt.y; o[2] = F->mvStatDepth[i]; o[3] = flows ? L->mvFlowNext[i].x : 0.f; o[4] = flows ? L->mvFlowNext[i].y : 0.f;
     }
 }
 
@@ -1611,6 +1666,44 @@ int vido_system_get_verify_points(const vido_system* s, float* xy, float* prev_x
         if (dist) dist[i] = F->mvStatVerifyDist[i];
         if (rejected) rejected[i] = F->mvStatVerifyRejected[i];
         if (seed_desc) memcpy(seed_desc + 32 * (size_t)i, &F->mvStatSeedDesc[32 * (size_t)i], 32);
+    }
+    return VIDO_OK;
+}
+
+int vido_system_get_recover_stats(const vido_system* s, int* n_tried, int* n_recovered)
+{
+    if (!s || !s->inited) return VIDO_E_INVALID;
+    if (n_tried) *n_tried = 0;
+    if (n_recovered) *n_recovered = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) T->GetRecoverStats(n_tried, n_recovered);
+    return VIDO_OK;
+}
+
+int vido_system_get_recover_points(const vido_system* s, int32_t* status, int32_t* idx, float* match_xy, int32_t* dist, int32_t* dist2, float* after, int cap, int* n_out,
+                                   float* train_xy, int32_t* train_level, uint8_t* train_desc, float* train_depth, int train_cap, int* n_train_out)
+{
+    if (!s || !s->inited || !n_out || !n_train_out) return VIDO_E_INVALID;
+    *n_out = 0; *n_train_out = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (!T || !T->mpCurrentFrame || !T->bVerifyRecover) return VIDO_OK;
+    const VIDO_SLAM::Frame* F = T->mpCurrentFrame;
+    const int n = (int)F->mvStatRecoverStatus.size(), nt = n > 0 ? (int)T->mvRecoverTrainLevel.size() : 0;
+    *n_out = n; *n_train_out = nt;
+    if (n > cap || nt > train_cap) return VIDO_E_CAPACITY;
+    if (n == 0) return VIDO_OK;
+    if ((int)F->mvStatRecoverAfter.size() != 5 * n || (int)F->mvStatRecoverXY.size() != 2 * n) return VIDO_E_INVALID;
+    if (status) memcpy(status, F->mvStatRecoverStatus.data(), sizeof(int32_t) * n);
+    if (idx) memcpy(idx, F->mvStatRecoverIdx.data(), sizeof(int32_t) * n);
+    if (dist) memcpy(dist, F->mvStatRecoverDist.data(), sizeof(int32_t) * n);
+    if (dist2) memcpy(dist2, F->mvStatRecoverDist2.data(), sizeof(int32_t) * n);
+    if (match_xy) memcpy(match_xy, F->mvStatRecoverXY.data(), sizeof(float) * 2 * n);
+    if (after) memcpy(after, F->mvStatRecoverAfter.data(), sizeof(float) * 5 * n);
+    if (nt > 0) {
+        if (train_xy) memcpy(train_xy, T->mvRecoverTrainXY.data(), sizeof(float) * 2 * nt);
+        if (train_level) memcpy(train_level, T->mvRecoverTrainLevel.data(), sizeof(int32_t) * nt);
+        if (train_desc) memcpy(train_desc, T->mvRecoverTrainDesc.data(), 32 * (size_t)nt);
+        if (train_depth) memcpy(train_depth, T->mvRecoverTrainDepth.data(), sizeof(float) * nt);
     }
     return VIDO_OK;
 }

@@ -62,6 +62,8 @@ def load_library():
     lib.vido_orb_last_timing.argtypes = [C.c_void_p, C.c_void_p]
     lib.vido_orb_geometry.argtypes = [C.c_void_p, C.c_void_p]
     lib.vido_hamming_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_hamming_match_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -220,6 +222,40 @@ class Context:
         idx = np.empty(len(a), np.int32); dist = np.empty(len(a), np.int32)
         self._check(self.lib.vido_hamming_match(self.h, _ptr(a), len(a), _ptr(b), len(b), _ptr(idx), _ptr(dist), 0))
         return idx, dist
+
+    @staticmethod
+    def _ratio(ratio):
+        """None / 0 -> off; (num, den) as given; a float r -> round(1024 r) / 1024"""
+        if ratio is None or (np.isscalar(ratio) and ratio == 0):
+            return 0, 1
+        if np.isscalar(ratio):
+            return int(round(1024.0 * float(ratio))), 1024
+        return int(ratio[0]), int(ratio[1])
+
+    def hamming_match_window(self, q_desc, q_xy, q_level, t_desc, t_xy, t_level, radius, level_tol=1, max_dist=256, ratio=None, unique=False):
+        """vido_hamming_match_window: best and second best train entry of every query inside a square window of +-radius px and a level gate, with max_dist, ratio
+        (None: off; (num, den); or a float, taken as round(1024 r) / 1024) and one-to-one tests.  Returns (idx, dist, dist2, status, stats[5]); the rule is
+        include/vido_c.h's, the numpy statement tests/refimpl/hamming_window_np.py."""
+        q_desc = np.ascontiguousarray(q_desc, np.uint8).reshape(-1, 32); t_desc = np.ascontiguousarray(t_desc, np.uint8).reshape(-1, 32)
+        q_xy = np.ascontiguousarray(q_xy, np.float32).reshape(-1, 2); t_xy = np.ascontiguousarray(t_xy, np.float32).reshape(-1, 2)
+        q_level = np.ascontiguousarray(q_level, np.int32).reshape(-1); t_level = np.ascontiguousarray(t_level, np.int32).reshape(-1)
+        nq, nt = len(q_desc), len(t_desc)
+        if len(q_xy) != nq or len(q_level) != nq or len(t_xy) != nt or len(t_level) != nt:
+            raise VidoError(-1, "hamming_match_window: descriptor, position and level arrays of different lengths")
+        num, den = self._ratio(ratio)
+        idx = np.empty(nq, np.int32); dist = np.empty(nq, np.int32); dist2 = np.empty(nq, np.int32); status = np.empty(nq, np.int32); stats = np.zeros(5, np.int32)
+        self._check(self.lib.vido_hamming_match_window(self.h, _ptr(q_desc), _ptr(q_xy), _ptr(q_level), nq, _ptr(t_desc), _ptr(t_xy), _ptr(t_level), nt, float(radius),
+                                                       int(level_tol), int(max_dist), num, den, int(bool(unique)), _ptr(idx), _ptr(dist), _ptr(dist2), _ptr(status), _ptr(stats), 0))
+        return idx, dist, dist2, status, stats
+
+    def hamming_match_window_device(self, q_desc_ptr, q_xy_ptr, q_level_ptr, nq, t_desc_ptr, t_xy_ptr, t_level_ptr, nt, radius, level_tol, max_dist, ratio, unique,
+                                    idx_ptr, dist_ptr, dist2_ptr, status_ptr, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; stats_ptr (5 x i32 on the device) may be None."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        num, den = self._ratio(ratio)
+        self._check(self.lib.vido_hamming_match_window(self.h, vp(q_desc_ptr), vp(q_xy_ptr), vp(q_level_ptr), int(nq), vp(t_desc_ptr), vp(t_xy_ptr), vp(t_level_ptr), int(nt),
+                                                       float(radius), int(level_tol), int(max_dist), num, den, int(bool(unique)), vp(idx_ptr), vp(dist_ptr), vp(dist2_ptr),
+                                                       vp(status_ptr), vp(stats_ptr), 1))
 
     # ---- label-image propagation ---------------------------------------------------------------------
     def frame_propagate_mask(self, slot_last, slot_cur):

@@ -46,6 +46,9 @@ def _bind(lib):
     lib.vido_system_get_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vido_system_mask_split_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.vido_system_get_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.vido_system_get_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_get_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
 
@@ -160,6 +163,29 @@ class System:
         if rc != VIDO_OK:
             raise VidoError(rc, "vido_system_get_verify_points")
         return dict(xy=xy[:n], prev_xy=pxy[:n], xyl=xyl[:n], dist=dist[:n], rejected=rej[:n].astype(bool), seed_desc=seed[:n])
+
+    def recover_stats(self):
+        """(n_tried, n_recovered) of the last frame's Verify.Recover search (both 0 with the option off): the rejected points searched, and those re-found."""
+        a, b = C.c_int(), C.c_int()
+        self.lib.vido_system_get_recover_stats(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def recover_points(self):
+        """Debug read of the last frame's Verify.Recover state (vido_system_get_recover_points), index-aligned with verify_points(): dict of status (n,) i32 (-1: not
+        searched; else vido_hamming_match_window's status, 0 = re-found), idx (n,) i32, match_xy (n,2) f32, dist / dist2 (n,) i32, after (n,5) f32 = x, y, depth and the
+        last frame's flow x, y as the step left them, and the train list of the frame's call: train_xy (nt,2) f32, train_level (nt,) i32, train_desc (nt,32) u8,
+        train_depth (nt,) f32."""
+        n, nt = C.c_int(), C.c_int()
+        self.lib.vido_system_get_recover_points(self.h, None, None, None, None, None, None, 0, C.byref(n), None, None, None, None, 0, C.byref(nt))
+        n, nt = n.value, nt.value; m, mt = max(n, 1), max(nt, 1)
+        status = np.empty(m, np.int32); idx = np.empty(m, np.int32); mxy = np.empty((m, 2), np.float32); dist = np.empty(m, np.int32); dist2 = np.empty(m, np.int32)
+        after = np.empty((m, 5), np.float32); txy = np.empty((mt, 2), np.float32); tlv = np.empty(mt, np.int32); tds = np.empty((mt, 32), np.uint8); tdp = np.empty(mt, np.float32)
+        rc = self.lib.vido_system_get_recover_points(self.h, status.ctypes.data, idx.ctypes.data, mxy.ctypes.data, dist.ctypes.data, dist2.ctypes.data, after.ctypes.data, m,
+                                                     C.byref(C.c_int()), txy.ctypes.data, tlv.ctypes.data, tds.ctypes.data, tdp.ctypes.data, mt, C.byref(C.c_int()))
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_get_recover_points")
+        return dict(status=status[:n], idx=idx[:n], match_xy=mxy[:n], dist=dist[:n], dist2=dist2[:n], after=after[:n],
+                    train_xy=txy[:nt], train_level=tlv[:nt], train_desc=tds[:nt], train_depth=tdp[:nt])
 
     def SaveResultsIJRR2020(self, filename=""):
         rc = self.lib.vido_system_save_results(self.h, os.fsencode(filename))
