@@ -115,6 +115,20 @@ int vido_orb_last_timing(const vido_ctx* ctx, float ms[8]);
  * neither on n nor on the order of the points.  Needs compute_descriptors != 0 for desc_out / dist_out (the blurred pyramid). */
 int vido_orb_describe_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, const uint8_t* ref_desc, float* angle_out, uint8_t* desc_out, int32_t* dist_out, int on_device);
 
+/* The 8 x 8 grey patch at CALLER-GIVEN points of pyramid slab `frame`, and its zero-mean normalised cross-correlation with a caller-given reference patch as an integer
+ * verdict (no reference call site; defined by tests/refimpl/patch_points_np.py, exact to the bit).  xyl [n*3] as for vido_orb_describe_points; blurred != 0 reads the
+ * blurred pyramid (needs compute_descriptors != 0), 0 the unblurred one.  The patch of point i is rows y-4 .. y+3, columns x-4 .. x+3 of its level, row-major, 64 bytes at
+ * patch_out[64 i ..].  With a = ref_patch[64 i ..], b = that patch, S1 = sum a, S2 = sum b, S11 = sum a^2, S22 = sum b^2, S12 = sum a b:
+ *   sums_out[3 i ..] = cov, var_ref, var_cur = 64 S12 - S1 S2, 64 S11 - S1^2, 64 S22 - S2^2          (each fits i32: at most 66 585 600)
+ *   status_out[i]    = 2 (no texture) if var_ref < min_var or var_cur < min_var; else 0 (accepted) iff cov > 0 and cov^2 * 1024^2 >= min_zncc_q10^2 * var_ref * var_cur,
+ *                      compared as exact 128-bit integers (no float, no square root, no division: equality accepts); else 1 (rejected).
+ * A point whose level is outside [0, n_levels) or whose patch is not wholly inside its level (x < 4, x + 3 >= w, likewise y) is INVALID: status -1, sums 0 0 0, zero
+ * patch, and nothing is read for it.  Any output may be NULL; sums_out / status_out need ref_patch, min_var >= 0 and 0 <= min_zncc_q10 <= 1024 (VIDO_E_INVALID otherwise).
+ * n == 0 is a successful no-op.  on_device != 0: every pointer is a device pointer (4-byte aligned) and the call only enqueues on the ctx stream; otherwise it returns
+ * when the results are in the caller's arrays.  Results depend neither on n nor on the order of the points. */
+int vido_orb_patch_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int min_var, int min_zncc_q10,
+                          uint8_t* patch_out, int32_t* sums_out, int32_t* status_out, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device
@@ -766,6 +780,13 @@ int         vido_system_get_recover_stats(const vido_system* sys, int* n_tried, 
  * *n_out = n, *n_train_out = nt (both 0 with the option off or before the second frame); VIDO_E_CAPACITY if n > cap or nt > train_cap. */
 int         vido_system_get_recover_points(const vido_system* sys, int32_t* status, int32_t* idx, float* match_xy, int32_t* dist, int32_t* dist2, float* after, int cap, int* n_out,
                                            float* train_xy, int32_t* train_level, uint8_t* train_desc, float* train_depth, int train_cap, int* n_train_out);
+/* Verify.ObjectPatch (default 0): counts of the last tracked frame's dense object points — n_checked (textured on both sides: accepted or rejected), n_rejected (taken off
+ * their object before the scene flow), n_no_texture (kept for lack of evidence).  All 0 with the key off.  vido_system_stats keeps its layout. */
+int         vido_system_get_object_verify_stats(const vido_system* sys, int* n_checked, int* n_rejected, int* n_no_texture);
+/* Debug read of the same frame's per-point state, index-aligned with the object points the frame carried over from the last one (any array may be NULL): xyl [n*3] where
+ * each was evaluated (level 0), sums [n*3] and status [n] as vido_orb_patch_points returned them, prev_xy [n*2] the last frame's point, ref_patch [n*64] the last frame's
+ * patch it was compared with.  *n_out = the number of points (0 with the key off or on a frame that verified nothing); VIDO_E_CAPACITY if cap is smaller. */
+int         vido_system_get_object_verify_points(const vido_system* sys, int32_t* xyl, int32_t* sums, int32_t* status, float* prev_xy, uint8_t* ref_patch, int cap, int* n_out);
 int         vido_system_save_results(vido_system* sys, const char* prefix);
 /* the vido_ctx the system's tracker runs on (NULL before the first frame): lets a caller share the device / query timings */
 vido_ctx*   vido_system_context(vido_system* sys);

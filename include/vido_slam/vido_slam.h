@@ -108,6 +108,11 @@ public:
        mvStatRecoverXY (x, y) that keypoint's position, (-1, -1) none; mvStatRecoverDist / Dist2 best and second-best distance (-1: none); mvStatRecoverAfter per point
        (x, y, depth, last frame's flow x, y) as the step left them: for a re-found point the keypoint, its depth and keypoint - last position, else unchanged. */
     std::vector<int> mvStatRecoverStatus, mvStatRecoverIdx, mvStatRecoverDist, mvStatRecoverDist2; std::vector<float> mvStatRecoverXY, mvStatRecoverAfter;
+    /* extension (Verify.ObjectPatch: 1; without the key none of these vectors exists): mvObjPatch — the 8 x 8 patch (64 bytes, row-major) of the blurred level 0 around
+       lrintf(mvObjKeys[i].pt) in THIS frame, index-aligned with mvObjKeys as RenewFrameInfo (or the first frame) left it.  mvObjVerify*: index-aligned with the points
+       this frame carried over (mvObjKeys = last->mvObjCorres): XYL where each was evaluated, Sums (cov, var_ref, var_cur) and Status of vido_orb_patch_points (0 kept,
+       1 rejected: vSemObjLabel[i] = 0, 2 no texture, -1 patch outside), PrevXY the last frame's point, Ref the last frame's patch it was compared with. */
+    std::vector<uint8_t> mvObjPatch, mvObjVerifyRef; std::vector<int32_t> mvObjVerifyXYL, mvObjVerifySums, mvObjVerifyStatus; std::vector<float> mvObjVerifyPrevXY;
     Frame *mpPrevFrame = nullptr, *mpNextFrame = nullptr;
 };
 
@@ -200,6 +205,16 @@ public:
        train list of the last call (read-back).  Keys Verify.RecoverRadius (px at level 0), Verify.RecoverLevelTol, Verify.RecoverMaxHamming, Verify.RecoverRatio
        (taken as round(1024 r) / 1024, 0 = off): defaults from profiles/r15/descriptor_recover.txt. */
     void RecoverRejectedStatic();
+    /* extension (Verify.ObjectPatch: 1, independent of Verify.Descriptor): the dense object points carry the 8 x 8 patch of the blurred level 0 of the frame that produced
+       them (TakeObjectPatches: end of RenewFrameInfo and the first frame); in the next frame VerifyObjectPatches compares it with the patch at the flow-predicted position
+       (vido_orb_patch_points, one call) and takes a rejected point off its object (vSemObjLabel = 0) before the scene flow.  Keys Verify.PatchMinZncc (in [0, 1], kept as
+       Q10) and Verify.PatchMinStd (grey levels, kept as min_var = 64^2 std^2); defaults from profiles/r16/patch_verify.txt.  GetObjectVerifyStats: the last frame's
+       counts — checked (status 0 or 1), rejected (1), no texture (2). */
+    void TakeObjectPatches(Frame* F);
+    void VerifyObjectPatches();
+    void GetObjectVerifyStats(int* n_checked, int* n_rejected, int* n_no_texture) const
+    { if (n_checked) *n_checked = nObjVerifyChecked; if (n_rejected) *n_rejected = nObjVerifyRejected; if (n_no_texture) *n_no_texture = nObjVerifyNoTexture; }
+    bool bVerifyObjectPatch = false; int nPatchMinZnccQ10 = 920, nPatchMinVar = 147456, nObjVerifyChecked = 0, nObjVerifyRejected = 0, nObjVerifyNoTexture = 0;
     void GetRecoverStats(int* n_tried, int* n_recovered) const { if (n_tried) *n_tried = nRecoverTried; if (n_recovered) *n_recovered = nRecovered; }
     bool bVerifyRecover = false; float fRecoverRadius = 32.f; int nRecoverLevelTol = 1, nRecoverMaxHamming = 50, nRecoverRatioNum = 0, nRecoverTried = 0, nRecovered = 0;
     std::vector<float> mvRecoverTrainXY, mvRecoverTrainDepth; std::vector<int> mvRecoverTrainLevel; std::vector<unsigned char> mvRecoverTrainDesc;

@@ -887,6 +887,13 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
     bVerifyRecover = bVerifyDescriptor && num(kv, "Verify.Recover", 0) != 0;      // (the defaults of the four keys: profiles/r15/descriptor_recover.txt)
     fRecoverRadius = (float)num(kv, "Verify.RecoverRadius", 32); nRecoverLevelTol = (int)num(kv, "Verify.RecoverLevelTol", 1); nRecoverMaxHamming = (int)num(kv, "Verify.RecoverMaxHamming", 50);
     nRecoverRatioNum = (int)lrint(1024.0 * num(kv, "Verify.RecoverRatio", 0));
+    bVerifyObjectPatch = num(kv, "Verify.ObjectPatch", 0) != 0;      // (independent of Verify.Descriptor; the defaults of the two keys: profiles/r16/patch_verify.txt)
+    {
+        const double z = num(kv, "Verify.PatchMinZncc", 920.0 / 1024.0), sd = num(kv, "Verify.PatchMinStd", 6);
+        if (bVerifyObjectPatch && (!(z >= 0.0) || !(z <= 1.0) || !(sd >= 0.0) || !(sd <= 128.0)))      // (127.5 is the largest std a patch of bytes can have: above it every point is "no texture")
+            throw std::runtime_error("Tracking: Verify.PatchMinZncc must be in [0, 1], Verify.PatchMinStd in [0, 128] grey levels");
+        if (bVerifyObjectPatch) { nPatchMinZnccQ10 = (int)lrint(1024.0 * z); nPatchMinVar = (int)lrint(4096.0 * sd * sd); }      // var = 64 S11 - S1^2 = 64^2 std^2
+    }
     if (bVerifyRecover && (!(fRecoverRadius >= 0.f) || !(fRecoverRadius < 1e9f) || nRecoverRatioNum < 0 || nRecoverRatioNum > 1024))
         throw std::runtime_error("Tracking: Verify.RecoverRadius must be finite and >= 0, Verify.RecoverRatio in [0, 1]");
     bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
@@ -1041,6 +1048,8 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
         std::vector<float> oxy(2 * std::max(no, 1));
         for (int i = 0; i < no; i++) { oxy[2 * i] = F->mvObjKeys[i].pt.x; oxy[2 * i + 1] = F->mvObjKeys[i].pt.y; }
         if (no) check(vido_gather_object_depth_label(c, slot_cur_, oxy.data(), no, mThDepthObj, F->mvObjDepth.data(), F->vSemObjLabel.data()), "gather_object");
+        nObjVerifyChecked = nObjVerifyRejected = nObjVerifyNoTexture = 0;
+        if (bVerifyObjectPatch) VerifyObjectPatches();
         TemperalMatch.assign(F->N_s, -1);
         nVerifyChecked = nVerifyRejected = 0; nRecoverTried = nRecovered = 0;
         if (bVerifyDescriptor) {                               // the seeds travel with the points (last.mvCorres is index-aligned with last.mvStatKeysTmp); then one launch for the frame
@@ -1056,6 +1065,50 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
     mImGrayLast = mImGray; mSegMapLast = mSegMap; mFlowMapLast = mFlowMap;      // :777-780
     ms_total = ms_since(t_grab);
     return mpCurrentFrame->mTcw.clone();
+}
+
+// Verify.ObjectPatch (no reference counterpart).  The dense object points have no keypoint and no level, but a neighbourhood of grey values: each carries the 8 x 8 patch
+// of the blurred level 0 around its (integer) position in the frame that produced it.  TakeObjectPatches fills F->mvObjPatch, index-aligned with F->mvObjKeys, from slab 0
+// of the tracker's context — which holds F's pyramids from Frame::Frame's collect until Track() returns: the next extraction (a prefetch included) is enqueued by the
+// caller's next call, never inside this one.
+void Tracking::TakeObjectPatches(Frame* F)
+{
+    const int n = (int)F->mvObjKeys.size();
+    F->mvObjPatch.assign(64 * (size_t)n, 0);
+    if (n == 0) return;
+    std::vector<int32_t> xyl(3 * (size_t)n);
+    for (int i = 0; i < n; i++) { xyl[3 * (size_t)i] = (int32_t)lrintf(F->mvObjKeys[i].pt.x); xyl[3 * (size_t)i + 1] = (int32_t)lrintf(F->mvObjKeys[i].pt.y); xyl[3 * (size_t)i + 2] = 0; }
+    vido_ctx* c = g_ctx;
+    if (timed_call([&]() -> int { return vido_orb_patch_points(c, 0, xyl.data(), n, 1, nullptr, 0, 0, F->mvObjPatch.data(), nullptr, nullptr, 0); }, "orb_patch_points(take)") != VIDO_OK)
+        throw std::runtime_error(vido_last_error(c));
+}
+
+// The carried points (F->mvObjKeys = last->mvObjCorres) have just been given depth and label; before anything reads them, one call compares the last frame's patch of
+// every point with this frame's patch at lrintf of the predicted position.  Status 1 (textured on both sides, ZNCC below Verify.PatchMinZncc) takes the point out:
+// vSemObjLabel = 0, the state vido_gather_object_depth_label gives a point that the flow carried off its object onto the background — vido_scene_flow labels it -1,
+// vido_dyn_obj_tracking groups no such point, so it reaches no RANSAC set, no motion optimisation and no inlier list, and RenewFrameInfo's top-up replaces it.  Status 0,
+// 2 (no texture) and -1 (patch not inside the image) keep the point: no evidence is not evidence against.
+void Tracking::VerifyObjectPatches()
+{
+    Frame *F = mpCurrentFrame, *L = mpLastFrame; const int n = (int)F->mvObjKeys.size();
+    F->mvObjVerifyXYL.assign(3 * (size_t)n, 0); F->mvObjVerifySums.assign(3 * (size_t)n, 0); F->mvObjVerifyStatus.assign(n, -1); F->mvObjVerifyPrevXY.assign(2 * (size_t)n, 0.f);
+    F->mvObjVerifyRef.clear();
+    if (n == 0 || L->mvObjPatch.size() != 64 * (size_t)n || (int)L->mvObjKeys.size() != n) return;
+    F->mvObjVerifyRef = L->mvObjPatch;
+    for (int i = 0; i < n; i++) {
+        F->mvObjVerifyXYL[3 * (size_t)i] = (int32_t)lrintf(F->mvObjKeys[i].pt.x); F->mvObjVerifyXYL[3 * (size_t)i + 1] = (int32_t)lrintf(F->mvObjKeys[i].pt.y);
+        F->mvObjVerifyPrevXY[2 * (size_t)i] = L->mvObjKeys[i].pt.x; F->mvObjVerifyPrevXY[2 * (size_t)i + 1] = L->mvObjKeys[i].pt.y;
+    }
+    vido_ctx* c = g_ctx;
+    if (timed_call([&]() -> int { return vido_orb_patch_points(c, 0, F->mvObjVerifyXYL.data(), n, 1, L->mvObjPatch.data(), nPatchMinVar, nPatchMinZnccQ10, nullptr, F->mvObjVerifySums.data(),
+                                                               F->mvObjVerifyStatus.data(), 0); }, "orb_patch_points(verify)") != VIDO_OK)
+        throw std::runtime_error(vido_last_error(c));
+    for (int i = 0; i < n; i++) {
+        const int st = F->mvObjVerifyStatus[i];
+        if (st == 0 || st == 1) nObjVerifyChecked++;
+        if (st == 2) nObjVerifyNoTexture++;
+        if (st == 1) { nObjVerifyRejected++; F->vSemObjLabel[i] = 0; }
+    }
 }
 
 // Verify.Descriptor (no reference counterpart: the reference believes every flow vector).  The extraction of the current frame has just been collected,
@@ -1163,6 +1216,7 @@ void Tracking::Initialization()                               // Tracking.cc:151
     mpMap->vmCameraPose.push_back(cv::Mat::eye(4, 4, CV_32F)); mpMap->vmCameraPose_RF.push_back(cv::Mat::eye(4, 4, CV_32F)); mpMap->vmCameraPose_GT.push_back(cv::Mat::eye(4, 4, CV_32F));
     F->SetPose(cv::Mat::eye(4, 4, CV_32F));
     mpLastFrame = F; mpLastFrame->mvStatKeys = F->mvStatKeysTmp; mpLastFrame->mvStatDepth = F->mvStatDepthTmp; mpLastFrame->N_s = F->N_s_tmp;
+    if (bVerifyObjectPatch) TakeObjectPatches(F);
     mState = OK;
 }
 
@@ -1403,6 +1457,7 @@ void Tracking::RenewFrameInfo(const std::vector<int>& TM_sta)  // Tracking.cc:29
     cv::Mat::batch3x1(oxyz3.data(), on, o3d);
     C->mvObjKeys = std::move(okeys); C->mvObjDepth = std::move(odepth); C->mvObj3DPoint = std::move(o3d); C->mvObjCorres = std::move(ocorr); C->mvObjFlowNext = std::move(oflow);
     C->vSemObjLabel.assign(osem.begin(), osem.begin() + on); C->nDynInlierID.assign(oinl.begin(), oinl.begin() + on); C->vObjLabel.assign(olab.begin(), olab.begin() + on);
+    if (bVerifyObjectPatch) TakeObjectPatches(C);          // the frame's final object list stands: kept inliers at their pixel + top-up samples
 }
 
 void Tracking::Track()                                        // Tracking.cc:1081-1509
@@ -1667,6 +1722,37 @@ int vido_system_get_verify_points(const vido_system* s, float* xy, float* prev_x
         if (rejected) rejected[i] = F->mvStatVerifyRejected[i];
         if (seed_desc) memcpy(seed_desc + 32 * (size_t)i, &F->mvStatSeedDesc[32 * (size_t)i], 32);
     }
+    return VIDO_OK;
+}
+
+int vido_system_get_object_verify_stats(const vido_system* s, int* n_checked, int* n_rejected, int* n_no_texture)
+{
+    if (!s || !s->inited) return VIDO_E_INVALID;
+    if (n_checked) *n_checked = 0;
+    if (n_rejected) *n_rejected = 0;
+    if (n_no_texture) *n_no_texture = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) T->GetObjectVerifyStats(n_checked, n_rejected, n_no_texture);
+    return VIDO_OK;
+}
+
+int vido_system_get_object_verify_points(const vido_system* s, int32_t* xyl, int32_t* sums, int32_t* status, float* prev_xy, uint8_t* ref_patch, int cap, int* n_out)
+{
+    if (!s || !s->inited || !n_out) return VIDO_E_INVALID;
+    *n_out = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (!T || !T->mpCurrentFrame || !T->bVerifyObjectPatch) return VIDO_OK;
+    const VIDO_SLAM::Frame* F = T->mpCurrentFrame;
+    const int n = F->mvObjVerifyRef.empty() ? 0 : (int)F->mvObjVerifyStatus.size();      // (no reference patches: the frame verified nothing)
+    *n_out = n;
+    if (n > cap) return VIDO_E_CAPACITY;
+    if (n == 0) return VIDO_OK;
+    if ((int)F->mvObjVerifyXYL.size() != 3 * n || (int)F->mvObjVerifySums.size() != 3 * n || (int)F->mvObjVerifyPrevXY.size() != 2 * n || F->mvObjVerifyRef.size() != 64 * (size_t)n) return VIDO_E_INVALID;
+    if (xyl) memcpy(xyl, F->mvObjVerifyXYL.data(), sizeof(int32_t) * 3 * n);
+    if (sums) memcpy(sums, F->mvObjVerifySums.data(), sizeof(int32_t) * 3 * n);
+    if (status) memcpy(status, F->mvObjVerifyStatus.data(), sizeof(int32_t) * n);
+    if (prev_xy) memcpy(prev_xy, F->mvObjVerifyPrevXY.data(), sizeof(float) * 2 * n);
+    if (ref_patch) memcpy(ref_patch, F->mvObjVerifyRef.data(), 64 * (size_t)n);
     return VIDO_OK;
 }
 

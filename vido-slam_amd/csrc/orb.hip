@@ -1814,6 +1814,15 @@ int orb_mirror_async(vido_ctx* ctx, int nf)
     return VIDO_OK;
 }
 
+// patchpts.hip: one frame's slabs (unblurred, blurred) and the level geometry; 0 when `frame` is outside the context's batch
+int orb_frame_planes(vido_ctx* ctx, int frame, const uint8_t** pyr, const uint8_t** blur, PyrDev* P)
+{
+    OrbState* S = ctx->orb;
+    if (!S || frame < 0 || frame >= S->B) return 0;
+    *pyr = S->d_pyr + (size_t)frame * S->slab; *blur = S->d_blur ? S->d_blur + (size_t)frame * S->slab : nullptr; *P = S->P;      // (no blurred pyramid without compute_descriptors)
+    return S->B;
+}
+
 OrbView orb_view(vido_ctx* ctx)
 {
     OrbState* S = ctx->orb;

@@ -65,6 +65,7 @@ def load_library():
     lib.vido_hamming_match_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_orb_patch_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -73,6 +74,11 @@ def load_library():
     lib.vido_frame_split_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
+
+
+# defaults of vido_orb_patch_points' verdict = the tracker's Verify.PatchMinStd 6 / Verify.PatchMinZncc 920 / 1024 (profiles/r16/patch_verify.txt)
+PATCH_MIN_VAR = 64 * 64 * 6 * 6
+PATCH_MIN_ZNCC_Q10 = 920
 
 
 def default_config(**kw):
@@ -210,6 +216,26 @@ class Context:
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
         vp = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.vido_orb_describe_points(self.h, frame, vp(xyl_ptr), n, vp(ref_ptr), vp(angle_ptr), vp(desc_ptr), vp(dist_ptr), 1))
+
+    def orb_patch_points(self, frame, xyl, ref_patch=None, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10):
+        """8 x 8 patches at given points of pyramid slab `frame` and their integer ZNCC verdict against ref_patch (vido_orb_patch_points): xyl (n,3) i32 = x, y in level
+        coordinates, level.  Returns (patch (n,64) u8, sums (n,3) i32 = cov, var_ref, var_cur, status (n,) i32: 0 accepted, 1 rejected, 2 no texture, -1 invalid); sums and
+        status are None without ref_patch (n,64) u8."""
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3); n = len(xyl)
+        if ref_patch is not None:
+            ref_patch = np.ascontiguousarray(ref_patch, np.uint8).reshape(-1, 64)
+            if len(ref_patch) != n:
+                raise VidoError(-1, "orb_patch_points: %d reference patches for %d points" % (len(ref_patch), n))
+        patch = np.empty((n, 64), np.uint8)
+        sums = np.empty((n, 3), np.int32) if ref_patch is not None else None; status = np.empty(n, np.int32) if ref_patch is not None else None
+        self._check(self.lib.vido_orb_patch_points(self.h, frame, _ptr(xyl), n, int(blurred), _ptr(ref_patch) if ref_patch is not None else None, int(min_var), int(min_zncc_q10),
+                                                   _ptr(patch), _ptr(sums) if sums is not None else None, _ptr(status) if status is not None else None, 0))
+        return patch, sums, status
+
+    def orb_patch_points_device(self, frame, xyl_ptr, n, ref_ptr=None, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, patch_ptr=None, sums_ptr=None, status_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_orb_patch_points(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(min_var), int(min_zncc_q10), vp(patch_ptr), vp(sums_ptr), vp(status_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

@@ -49,6 +49,8 @@ def _bind(lib):
     lib.vido_system_get_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vido_system_get_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.vido_system_get_object_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_get_object_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
 
@@ -186,6 +188,25 @@ class System:
             raise VidoError(rc, "vido_system_get_recover_points")
         return dict(status=status[:n], idx=idx[:n], match_xy=mxy[:n], dist=dist[:n], dist2=dist2[:n], after=after[:n],
                     train_xy=txy[:nt], train_level=tlv[:nt], train_desc=tds[:nt], train_depth=tdp[:nt])
+
+    def object_verify_stats(self):
+        """(n_checked, n_rejected, n_no_texture) of the last frame's patch verification of the dense object points (Verify.ObjectPatch: 1; all 0 otherwise)."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self.lib.vido_system_get_object_verify_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def object_verify_points(self):
+        """Debug read of the last frame's Verify.ObjectPatch state (vido_system_get_object_verify_points), index-aligned with the object points the frame carried over
+        from the last one: dict of xyl (n,3) i32, sums (n,3) i32 = cov, var_ref, var_cur, status (n,) i32 (0 kept, 1 rejected, 2 no texture, -1 patch outside the image),
+        prev_xy (n,2) f32 = the last frame's point, ref_patch (n,64) u8 = the last frame's patch."""
+        n = C.c_int()
+        self.lib.vido_system_get_object_verify_points(self.h, None, None, None, None, None, 0, C.byref(n))
+        n = n.value; m = max(n, 1)
+        xyl = np.empty((m, 3), np.int32); sums = np.empty((m, 3), np.int32); status = np.empty(m, np.int32); pxy = np.empty((m, 2), np.float32); ref = np.empty((m, 64), np.uint8)
+        rc = self.lib.vido_system_get_object_verify_points(self.h, xyl.ctypes.data, sums.ctypes.data, status.ctypes.data, pxy.ctypes.data, ref.ctypes.data, m, C.byref(C.c_int()))
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_get_object_verify_points")
+        return dict(xyl=xyl[:n], sums=sums[:n], status=status[:n], prev_xy=pxy[:n], ref_patch=ref[:n])
 
     def SaveResultsIJRR2020(self, filename=""):
         rc = self.lib.vido_system_save_results(self.h, os.fsencode(filename))
