@@ -129,6 +129,29 @@ int vido_orb_describe_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n
 int vido_orb_patch_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int min_var, int min_zncc_q10,
                           uint8_t* patch_out, int32_t* sums_out, int32_t* status_out, int on_device);
 
+/* The offset inside a square window at which the 8 x 8 patch of pyramid slab `frame` correlates best with a caller-given reference patch, the runner-up outside the
+ * winner's own peak, and an integer verdict (no reference call site; defined by tests/refimpl/patch_search_np.py, exact to the bit).  xyl [n*3], blurred, the patch, the
+ * three sums and "wholly inside the level" as for vido_orb_patch_points; a = ref_patch[64 i ..] (required).  0 <= radius <= 16, 1 <= excl <= 16, min_var >= 0,
+ * 0 <= min_zncc_q10 <= 1024, 0 <= peak_ratio_q10 <= 1024 (0: no peak test); VIDO_E_INVALID otherwise.  In the order the rules apply, per point:
+ *   candidates  the offsets (dx, dy), |dx| <= radius, |dy| <= radius, whose patch at (x + dx, y + dy) lies wholly inside the level
+ *   status -1   level outside [0, n_levels) or no candidate: every output of the point is 0
+ *   status  2   var_ref < min_var: nothing is searched; sums = 0, var_ref, 0 and the rest 0.  A point of status -1 or 2 reads nothing of the slab
+ *   eligible    a candidate with var_cur >= min_var and cov > 0
+ *   order       p before q iff cov_p^2 var_q > cov_q^2 var_p (exact 128-bit integers: ZNCC^2 without a division); on equality the smaller dx^2 + dy^2, then the
+ *               smaller dy, then the smaller dx
+ *   best        the first eligible candidate in that order; none: status 1, dxy = 0, sums = 0, var_ref, 0, second = 0
+ *   dxy_out[2 i ..] = dx, dy of the best; sums_out[3 i ..] = its cov, var_ref, var_cur
+ *   second_out[2 i ..] = cov, var_cur of the first eligible candidate in that order with max(|dx - dx1|, |dy - dy1|) > excl, 0 0 if there is none (reported whenever
+ *               there is a best, whatever the status)
+ *   status  1   the best fails cov^2 * 1024^2 >= min_zncc_q10^2 * var_ref * var_cur (equality accepts)
+ *   status  3   else, with peak_ratio_q10 > 0 and a second: cov2^2 * var1 * 1024^2 > peak_ratio_q10^2 * cov1^2 * var2 (ZNCC2 > r ZNCC1: ambiguous)
+ *   status  0   otherwise: found
+ * stats_out[0..3] count the statuses 0..3 of this call, stats_out[4] status -1.  Any output may be NULL; every element of a given output is written.  n == 0 is a
+ * successful no-op that zeroes stats_out.  on_device != 0: every pointer is a device pointer (4-byte aligned) and the call only enqueues on the ctx stream; otherwise it
+ * returns when the results are in the caller's arrays.  Results depend neither on n nor on the order of the points. */
+int vido_orb_patch_search(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int radius, int excl, int min_var, int min_zncc_q10,
+                          int peak_ratio_q10, int32_t* dxy_out, int32_t* sums_out, int32_t* second_out, int32_t* status_out, int32_t* stats_out, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device
@@ -787,6 +810,16 @@ int         vido_system_get_object_verify_stats(const vido_system* sys, int* n_c
  * each was evaluated (level 0), sums [n*3] and status [n] as vido_orb_patch_points returned them, prev_xy [n*2] the last frame's point, ref_patch [n*64] the last frame's
  * patch it was compared with.  *n_out = the number of points (0 with the key off or on a frame that verified nothing); VIDO_E_CAPACITY if cap is smaller. */
 int         vido_system_get_object_verify_points(const vido_system* sys, int32_t* xyl, int32_t* sums, int32_t* status, float* prev_xy, uint8_t* ref_patch, int cap, int* n_out);
+/* Verify.ObjectRecover (default 0; needs Verify.ObjectPatch: 1): of the last tracked frame, n_tried = the object points the patch verification rejected and the search
+ * looked for, n_recovered = those put back on their object at a re-found pixel (they no longer count in n_rejected of vido_system_get_object_verify_stats).  Both 0 with
+ * the key off.  vido_system_stats keeps its layout. */
+int         vido_system_get_object_recover_stats(const vido_system* sys, int* n_tried, int* n_recovered);
+/* Debug read of the same step, index-aligned with vido_system_get_object_verify_points (any array may be NULL): status [n] of vido_orb_patch_search (-2: the point was
+ * not searched), dxy [n*2], sums [n*3], second [n*2] as the call returned them (0 where not searched); gather [n*2] = depth, label the frame's maps hold at the re-found
+ * pixel (-1 -1 where status != 0); after [n*6] = x, y, depth, label, last frame's flow x, y of every point as the step left them.  With xyl and ref_patch of
+ * vido_system_get_object_verify_points a caller can recompute the call.  *n_out = n (0 with the key off or on a frame that verified nothing); VIDO_E_CAPACITY if cap is
+ * smaller. */
+int         vido_system_get_object_recover_points(const vido_system* sys, int32_t* status, int32_t* dxy, int32_t* sums, int32_t* second, float* gather, float* after, int cap, int* n_out);
 int         vido_system_save_results(vido_system* sys, const char* prefix);
 /* the vido_ctx the system's tracker runs on (NULL before the first frame): lets a caller share the device / query timings */
 vido_ctx*   vido_system_context(vido_system* sys);

@@ -113,6 +113,11 @@ public:
        this frame carried over (mvObjKeys = last->mvObjCorres): XYL where each was evaluated, Sums (cov, var_ref, var_cur) and Status of vido_orb_patch_points (0 kept,
        1 rejected: vSemObjLabel[i] = 0, 2 no texture, -1 patch outside), PrevXY the last frame's point, Ref the last frame's patch it was compared with. */
     std::vector<uint8_t> mvObjPatch, mvObjVerifyRef; std::vector<int32_t> mvObjVerifyXYL, mvObjVerifySums, mvObjVerifyStatus; std::vector<float> mvObjVerifyPrevXY;
+    /* extension (Verify.ObjectRecover: 1; without the key none of these vectors exists): index-aligned with mvObjVerify*.  Status of vido_orb_patch_search for the points
+       the verification rejected (0 found, 1 not found, 2 no texture, 3 ambiguous, -1 invalid) and -2 for a point that was not searched; DXY, Sums, Second as the call
+       returned them (0 where not searched); Gather = (depth, label) the slot holds at the re-found pixel (-1, -1 where status != 0); After per point (x, y, depth, label,
+       last frame's flow x, y) as the step left them: for an accepted point the re-found pixel, its depth and label and pixel - last position, else unchanged. */
+    std::vector<int32_t> mvObjRecoverStatus, mvObjRecoverDXY, mvObjRecoverSums, mvObjRecoverSecond; std::vector<float> mvObjRecoverGather, mvObjRecoverAfter;
     Frame *mpPrevFrame = nullptr, *mpNextFrame = nullptr;
 };
 
@@ -215,6 +220,14 @@ public:
     void GetObjectVerifyStats(int* n_checked, int* n_rejected, int* n_no_texture) const
     { if (n_checked) *n_checked = nObjVerifyChecked; if (n_rejected) *n_rejected = nObjVerifyRejected; if (n_no_texture) *n_no_texture = nObjVerifyNoTexture; }
     bool bVerifyObjectPatch = false; int nPatchMinZnccQ10 = 920, nPatchMinVar = 147456, nObjVerifyChecked = 0, nObjVerifyRejected = 0, nObjVerifyNoTexture = 0;
+    /* extension (Verify.ObjectRecover: 1, needs Verify.ObjectPatch: 1 and is off without it): straight after VerifyObjectPatches the rejected points are searched for in
+       a window around the position that was verified (vido_orb_patch_search, ONE call: blurred level 0, reference = the last frame's patch).  A found point moves to the
+       re-found pixel if the slot's label there is the last frame's and its depth is usable (one vido_gather_object_depth_label call); this frame's mvObjKeys / mvObjDepth /
+       vSemObjLabel and the last frame's mvObjCorres / mvObjFlowNext follow.  Keys Verify.ObjectRecoverRadius (0 .. 16), Verify.ObjectRecoverExcl (1 .. 16),
+       Verify.ObjectRecoverMinZncc and Verify.ObjectRecoverPeakRatio (in [0, 1], kept as Q10; ratio 0 = off): defaults from profiles/r17/patch_recover.txt. */
+    void RecoverRejectedObjects();
+    void GetObjectRecoverStats(int* n_tried, int* n_recovered) const { if (n_tried) *n_tried = nObjRecoverTried; if (n_recovered) *n_recovered = nObjRecovered; }
+    bool bVerifyObjectRecover = false; int nObjRecoverRadius = 8, nObjRecoverExcl = 2, nObjRecoverMinZnccQ10 = 976, nObjRecoverPeakRatioQ10 = 0, nObjRecoverTried = 0, nObjRecovered = 0;
     void GetRecoverStats(int* n_tried, int* n_recovered) const { if (n_tried) *n_tried = nRecoverTried; if (n_recovered) *n_recovered = nRecovered; }
     bool bVerifyRecover = false; float fRecoverRadius = 32.f; int nRecoverLevelTol = 1, nRecoverMaxHamming = 50, nRecoverRatioNum = 0, nRecoverTried = 0, nRecovered = 0;
     std::vector<float> mvRecoverTrainXY, mvRecoverTrainDepth; std::vector<int> mvRecoverTrainLevel; std::vector<unsigned char> mvRecoverTrainDesc;

@@ -96,6 +96,7 @@ void vido_destroy(vido_ctx* ctx)
     ham_state_destroy(ctx);
     hamwin_state_destroy(ctx);
     patchpts_state_destroy(ctx);
+    patchsearch_state_destroy(ctx);
     pose_state_destroy(ctx);
     ba_state_destroy(ctx);
     net_state_destroy(ctx);

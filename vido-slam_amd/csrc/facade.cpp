@@ -894,6 +894,13 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
             throw std::runtime_error("Tracking: Verify.PatchMinZncc must be in [0, 1], Verify.PatchMinStd in [0, 128] grey levels");
         if (bVerifyObjectPatch) { nPatchMinZnccQ10 = (int)lrint(1024.0 * z); nPatchMinVar = (int)lrint(4096.0 * sd * sd); }      // var = 64 S11 - S1^2 = 64^2 std^2
     }
+    bVerifyObjectRecover = bVerifyObjectPatch && num(kv, "Verify.ObjectRecover", 0) != 0;      // (off without Verify.ObjectPatch, as Verify.Recover without Verify.Descriptor; defaults: profiles/r17/patch_recover.txt)
+    if (bVerifyObjectRecover) {
+        const double r = num(kv, "Verify.ObjectRecoverRadius", 8), e = num(kv, "Verify.ObjectRecoverExcl", 2), z = num(kv, "Verify.ObjectRecoverMinZncc", 976.0 / 1024.0), pr = num(kv, "Verify.ObjectRecoverPeakRatio", 0);
+        if (!(r >= 0.0) || !(r <= 16.0) || !(e >= 1.0) || !(e <= 16.0) || !(z >= 0.0) || !(z <= 1.0) || !(pr >= 0.0) || !(pr <= 1.0))
+            throw std::runtime_error("Tracking: Verify.ObjectRecoverRadius must be in [0, 16], Verify.ObjectRecoverExcl in [1, 16], Verify.ObjectRecoverMinZncc and Verify.ObjectRecoverPeakRatio in [0, 1]");
+        nObjRecoverRadius = (int)lrint(r); nObjRecoverExcl = (int)lrint(e); nObjRecoverMinZnccQ10 = (int)lrint(1024.0 * z); nObjRecoverPeakRatioQ10 = (int)lrint(1024.0 * pr);
+    }
     if (bVerifyRecover && (!(fRecoverRadius >= 0.f) || !(fRecoverRadius < 1e9f) || nRecoverRatioNum < 0 || nRecoverRatioNum > 1024))
         throw std::runtime_error("Tracking: Verify.RecoverRadius must be finite and >= 0, Verify.RecoverRatio in [0, 1]");
     bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
@@ -1050,6 +1057,8 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
         if (no) check(vido_gather_object_depth_label(c, slot_cur_, oxy.data(), no, mThDepthObj, F->mvObjDepth.data(), F->vSemObjLabel.data()), "gather_object");
         nObjVerifyChecked = nObjVerifyRejected = nObjVerifyNoTexture = 0;
         if (bVerifyObjectPatch) VerifyObjectPatches();
+        nObjRecoverTried = nObjRecovered = 0;
+        if (bVerifyObjectRecover) RecoverRejectedObjects();
         TemperalMatch.assign(F->N_s, -1);
         nVerifyChecked = nVerifyRejected = 0; nRecoverTried = nRecovered = 0;
         if (bVerifyDescriptor) {                               // the seeds travel with the points (last.mvCorres is index-aligned with last.mvStatKeysTmp); then one launch for the frame
@@ -1108,6 +1117,66 @@ void Tracking::VerifyObjectPatches()
         if (st == 0 || st == 1) nObjVerifyChecked++;
         if (st == 2) nObjVerifyNoTexture++;
         if (st == 1) { nObjVerifyRejected++; F->vSemObjLabel[i] = 0; }
+    }
+}
+
+// Verify.ObjectRecover (no reference counterpart).  Straight after the verdicts: the points of status 1 — textured on both sides, ZNCC below the gate at the predicted
+// pixel — are looked for in the (2 R + 1)^2 window around that pixel, ONE vido_orb_patch_search call on the blurred level 0 with the last frame's patch as the reference.
+// A status-0 point has a new pixel p' = centre + (dx, dy); one vido_gather_object_depth_label call over those gives what the frame's maps hold there, and the point is
+// accepted only onto its own object: label == the last frame's vSemObjLabel[i], depth usable (> 0).  Everything that carries the correspondence then follows: this frame's
+// mvObjKeys[i].pt / mvObjDepth[i] / vSemObjLabel[i] (the scene flow, vido_dyn_obj_tracking, the object RANSAC and motion optimisation, RenewFrameInfo read them) and the
+// last frame's mvObjCorres[i] / mvObjFlowNext[i] = p' - the last position (Frame::ObtainFlowDepthObject and the flow handed to PoseOptimizationFlow2 read the flow).
+// UpdateMask has already run for this frame with the flow-predicted pixels and is not run again: it wrote the point's label where the flow sent it, as it does with the
+// verification alone.  A point that is not accepted stays rejected (vSemObjLabel = 0).  Two points may end on one pixel; that is left alone.
+void Tracking::RecoverRejectedObjects()
+{
+    Frame *F = mpCurrentFrame, *L = mpLastFrame; const int n = (int)F->mvObjKeys.size();
+    F->mvObjRecoverStatus.assign(n, -2); F->mvObjRecoverDXY.assign(2 * (size_t)n, 0); F->mvObjRecoverSums.assign(3 * (size_t)n, 0); F->mvObjRecoverSecond.assign(2 * (size_t)n, 0);
+    F->mvObjRecoverGather.assign(2 * (size_t)n, -1.f);
+    std::vector<int> which;
+    if (n > 0 && F->mvObjVerifyRef.size() == 64 * (size_t)n && (int)F->mvObjVerifyStatus.size() == n && (int)L->mvObjKeys.size() == n && (int)L->mvObjCorres.size() == n &&
+        (int)L->mvObjFlowNext.size() == n && (int)L->vSemObjLabel.size() == n)
+        for (int i = 0; i < n; i++) if (F->mvObjVerifyStatus[i] == 1) which.push_back(i);
+    const int m = (int)which.size();
+    nObjRecoverTried = m;
+    if (m > 0) {
+        std::vector<int32_t> xyl(3 * (size_t)m), dxy(2 * (size_t)m), sums(3 * (size_t)m), second(2 * (size_t)m), status(m); std::vector<uint8_t> ref(64 * (size_t)m); int32_t stats[5];
+        for (int k = 0; k < m; k++) {
+            const int i = which[k];
+            memcpy(&xyl[3 * (size_t)k], &F->mvObjVerifyXYL[3 * (size_t)i], 3 * sizeof(int32_t)); memcpy(&ref[64 * (size_t)k], &F->mvObjVerifyRef[64 * (size_t)i], 64);
+        }
+        vido_ctx* c = g_ctx;
+        if (timed_call([&]() -> int { return vido_orb_patch_search(c, 0, xyl.data(), m, 1, ref.data(), nObjRecoverRadius, nObjRecoverExcl, nPatchMinVar, nObjRecoverMinZnccQ10, nObjRecoverPeakRatioQ10,
+                                                                   dxy.data(), sums.data(), second.data(), status.data(), stats, 0); }, "orb_patch_search") != VIDO_OK) throw std::runtime_error(vido_last_error(c));
+        std::vector<int> found; std::vector<float> fxy;
+        for (int k = 0; k < m; k++) {
+            const int i = which[k];
+            F->mvObjRecoverStatus[i] = status[k];
+            memcpy(&F->mvObjRecoverDXY[2 * (size_t)i], &dxy[2 * (size_t)k], 2 * sizeof(int32_t)); memcpy(&F->mvObjRecoverSums[3 * (size_t)i], &sums[3 * (size_t)k], 3 * sizeof(int32_t));
+            memcpy(&F->mvObjRecoverSecond[2 * (size_t)i], &second[2 * (size_t)k], 2 * sizeof(int32_t));
+            if (status[k] != 0) continue;
+            found.push_back(i); fxy.push_back((float)(xyl[3 * (size_t)k] + dxy[2 * (size_t)k])); fxy.push_back((float)(xyl[3 * (size_t)k + 1] + dxy[2 * (size_t)k + 1]));
+        }
+        const int nf = (int)found.size();
+        if (nf > 0) {
+            std::vector<float> fd(nf, -1.f); std::vector<int32_t> fl(nf, -1);
+            check(vido_gather_object_depth_label(c, slot_cur_, fxy.data(), nf, mThDepthObj, fd.data(), fl.data()), "gather_object(recover)");
+            for (int k = 0; k < nf; k++) {
+                const int i = found[k];
+                F->mvObjRecoverGather[2 * (size_t)i] = fd[k]; F->mvObjRecoverGather[2 * (size_t)i + 1] = (float)fl[k];
+                if (fl[k] != L->vSemObjLabel[i] || fl[k] <= 0 || !(fd[k] > 0.f)) continue;
+                const cv::Point2f pt(fxy[2 * (size_t)k], fxy[2 * (size_t)k + 1]);
+                F->mvObjKeys[i].pt = pt; F->mvObjDepth[i] = fd[k]; F->vSemObjLabel[i] = fl[k];
+                L->mvObjCorres[i].pt = pt; L->mvObjFlowNext[i] = cv::Point2f(pt.x - L->mvObjKeys[i].pt.x, pt.y - L->mvObjKeys[i].pt.y);
+                nObjVerifyRejected--; nObjRecovered++;
+            }
+        }
+    }
+    F->mvObjRecoverAfter.resize(6 * (size_t)n);
+    const bool flows = (int)L->mvObjFlowNext.size() == n;
+    for (int i = 0; i < n; i++) {
+        float* o = &F->mvObjRecoverAfter[6 * (size_t)i];
+        o[0] = F->mvObjKeys[i].pt.x; o[1] = F->mvObjKeys[i].pt.y; o[2] = F->mvObjDepth[i]; o[3] = (float)F->vSemObjLabel[i]; o[4] = flows ? L->mvObjFlowNext[i].x : 0.f; o[5] = flows ? L->mvObjFlowNext[i].y : 0.f;
     }
 }
 
@@ -1753,6 +1822,38 @@ int vido_system_get_object_verify_points(const vido_system* s, int32_t* xyl, int
     if (status) memcpy(status, F->mvObjVerifyStatus.data(), sizeof(int32_t) * n);
     if (prev_xy) memcpy(prev_xy, F->mvObjVerifyPrevXY.data(), sizeof(float) * 2 * n);
     if (ref_patch) memcpy(ref_patch, F->mvObjVerifyRef.data(), 64 * (size_t)n);
+    return VIDO_OK;
+}
+
+int vido_system_get_object_recover_stats(const vido_system* s, int* n_tried, int* n_recovered)
+{
+    if (!s || !s->inited) return VIDO_E_INVALID;
+    if (n_tried) *n_tried = 0;
+    if (n_recovered) *n_recovered = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) T->GetObjectRecoverStats(n_tried, n_recovered);
+    return VIDO_OK;
+}
+
+int vido_system_get_object_recover_points(const vido_system* s, int32_t* status, int32_t* dxy, int32_t* sums, int32_t* second, float* gather, float* after, int cap, int* n_out)
+{
+    if (!s || !s->inited || !n_out) return VIDO_E_INVALID;
+    *n_out = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (!T || !T->mpCurrentFrame || !T->bVerifyObjectRecover) return VIDO_OK;
+    const VIDO_SLAM::Frame* F = T->mpCurrentFrame;
+    const int n = F->mvObjVerifyRef.empty() ? 0 : (int)F->mvObjRecoverStatus.size();      // (no reference patches: the frame verified nothing)
+    *n_out = n;
+    if (n > cap) return VIDO_E_CAPACITY;
+    if (n == 0) return VIDO_OK;
+    if ((int)F->mvObjRecoverDXY.size() != 2 * n || (int)F->mvObjRecoverSums.size() != 3 * n || (int)F->mvObjRecoverSecond.size() != 2 * n || (int)F->mvObjRecoverGather.size() != 2 * n ||
+        (int)F->mvObjRecoverAfter.size() != 6 * n) return VIDO_E_INVALID;
+    if (status) memcpy(status, F->mvObjRecoverStatus.data(), sizeof(int32_t) * n);
+    if (dxy) memcpy(dxy, F->mvObjRecoverDXY.data(), sizeof(int32_t) * 2 * n);
+    if (sums) memcpy(sums, F->mvObjRecoverSums.data(), sizeof(int32_t) * 3 * n);
+    if (second) memcpy(second, F->mvObjRecoverSecond.data(), sizeof(int32_t) * 2 * n);
+    if (gather) memcpy(gather, F->mvObjRecoverGather.data(), sizeof(float) * 2 * n);
+    if (after) memcpy(after, F->mvObjRecoverAfter.data(), sizeof(float) * 6 * n);
     return VIDO_OK;
 }
 

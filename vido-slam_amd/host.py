@@ -66,6 +66,8 @@ def load_library():
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_patch_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_orb_patch_search.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -236,6 +238,27 @@ class Context:
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
         vp = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.vido_orb_patch_points(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(min_var), int(min_zncc_q10), vp(patch_ptr), vp(sums_ptr), vp(status_ptr), 1))
+
+    def orb_patch_search(self, frame, xyl, ref_patch, radius, excl=2, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, peak_ratio_q10=0):
+        """The offset within `radius` at which the 8 x 8 patch of pyramid slab `frame` correlates best with ref_patch (n,64) u8 (vido_orb_patch_search; the statement is
+        tests/refimpl/patch_search_np.py): xyl (n,3) i32 = x, y in level coordinates, level.  Returns (dxy (n,2) i32, sums (n,3) i32 = cov, var_ref, var_cur of the best,
+        second (n,2) i32 = cov, var_cur of the best outside +-excl of it, status (n,) i32: 0 found, 1 not found, 2 no texture in the reference, 3 ambiguous
+        (peak_ratio_q10 > 0), -1 invalid; stats (5,) i32 = the counts of 0, 1, 2, 3, -1)."""
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3); n = len(xyl)
+        ref_patch = np.ascontiguousarray(ref_patch, np.uint8).reshape(-1, 64)
+        if len(ref_patch) != n:
+            raise VidoError(-1, "orb_patch_search: %d reference patches for %d points" % (len(ref_patch), n))
+        dxy = np.empty((n, 2), np.int32); sums = np.empty((n, 3), np.int32); second = np.empty((n, 2), np.int32); status = np.empty(n, np.int32); stats = np.empty(5, np.int32)
+        self._check(self.lib.vido_orb_patch_search(self.h, frame, _ptr(xyl), n, int(blurred), _ptr(ref_patch), int(radius), int(excl), int(min_var), int(min_zncc_q10), int(peak_ratio_q10),
+                                                   _ptr(dxy), _ptr(sums), _ptr(second), _ptr(status), _ptr(stats), 0))
+        return dxy, sums, second, status, stats
+
+    def orb_patch_search_device(self, frame, xyl_ptr, n, ref_ptr, radius, excl=2, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, peak_ratio_q10=0,
+                                dxy_ptr=None, sums_ptr=None, second_ptr=None, status_ptr=None, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_orb_patch_search(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(radius), int(excl), int(min_var), int(min_zncc_q10), int(peak_ratio_q10),
+                                                   vp(dxy_ptr), vp(sums_ptr), vp(second_ptr), vp(status_ptr), vp(stats_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

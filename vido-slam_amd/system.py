@@ -51,6 +51,8 @@ def _bind(lib):
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.vido_system_get_object_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vido_system_get_object_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.vido_system_get_object_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_get_object_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
 
@@ -207,6 +209,26 @@ class System:
         if rc != VIDO_OK:
             raise VidoError(rc, "vido_system_get_object_verify_points")
         return dict(xyl=xyl[:n], sums=sums[:n], status=status[:n], prev_xy=pxy[:n], ref_patch=ref[:n])
+
+    def object_recover_stats(self):
+        """(n_tried, n_recovered) of the last frame's search for the object points the patch verification rejected (Verify.ObjectRecover: 1; both 0 otherwise)."""
+        a, b = C.c_int(), C.c_int()
+        self.lib.vido_system_get_object_recover_stats(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def object_recover_points(self):
+        """Debug read of the last frame's Verify.ObjectRecover step (vido_system_get_object_recover_points), index-aligned with object_verify_points(): dict of status (n,)
+        i32 of vido_orb_patch_search (-2: not searched), dxy (n,2), sums (n,3), second (n,2) i32 as the call returned them, gather (n,2) f32 = depth, label at the re-found
+        pixel (-1, -1 where status != 0), after (n,6) f32 = x, y, depth, label, last frame's flow x, y as the step left them."""
+        n = C.c_int()
+        self.lib.vido_system_get_object_recover_points(self.h, None, None, None, None, None, None, 0, C.byref(n))
+        n = n.value; m = max(n, 1)
+        status = np.empty(m, np.int32); dxy = np.empty((m, 2), np.int32); sums = np.empty((m, 3), np.int32); second = np.empty((m, 2), np.int32)
+        gather = np.empty((m, 2), np.float32); after = np.empty((m, 6), np.float32)
+        rc = self.lib.vido_system_get_object_recover_points(self.h, status.ctypes.data, dxy.ctypes.data, sums.ctypes.data, second.ctypes.data, gather.ctypes.data, after.ctypes.data, m, C.byref(C.c_int()))
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_get_object_recover_points")
+        return dict(status=status[:n], dxy=dxy[:n], sums=sums[:n], second=second[:n], gather=gather[:n], after=after[:n])
 
     def SaveResultsIJRR2020(self, filename=""):
         rc = self.lib.vido_system_save_results(self.h, os.fsencode(filename))
