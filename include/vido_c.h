@@ -152,6 +152,30 @@ int vido_orb_patch_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, i
 int vido_orb_patch_search(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int radius, int excl, int min_var, int min_zncc_q10,
                           int peak_ratio_q10, int32_t* dxy_out, int32_t* sums_out, int32_t* second_out, int32_t* status_out, int32_t* stats_out, int on_device);
 
+/* Sub-pixel alignment of a caller-given 8 x 8 reference patch to pyramid slab `frame` around CALLER-GIVEN points: translation-only inverse-compositional Gauss-Newton with a
+ * bias term, to 1/256 px and entirely in integers (no reference call site; defined by tests/refimpl/patch_refine_np.py, exact to the bit).  xyl [n*3], blurred and
+ * T = ref_patch[64 i ..] (required; T[r][c] belongs to level pixel (x - 4 + c, y - 4 + r)) as for vido_orb_patch_search.  Only the 36 interior pixels r, c in 1..6 are
+ * compared (N = 36); the border ring serves the template's gradients.  1 <= iters <= 8, 0 <= max_shift_q8 <= 512 (1/256 px), min_eig >= 0; VIDO_E_INVALID otherwise.
+ * In the order the rules apply, per point:
+ *   status -1   level outside [0, n_levels), or not (x - 3 - C >= 0 and x + 3 + C <= w - 1 and the same in y), C = (max_shift_q8 + 255) >> 8: every output of the point is
+ *               0 and nothing is read for it.  Otherwise the footprint is inside the level for every admissible offset
+ *   gradients   gx = T[r][c+1] - T[r][c-1], gy = T[r+1][c] - T[r-1][c]
+ *   Hessian     Hxx = N sum gx^2 - (sum gx)^2, Hyy = N sum gy^2 - (sum gy)^2, Hxy = N sum gx gy - sum gx sum gy, det = Hxx Hyy - Hxy^2, tr = Hxx + Hyy
+ *   status  2   det <= 0 or tr < 2 min_eig or det - min_eig tr + min_eig^2 < 0 (smaller eigenvalue of H below min_eig: no texture, or an edge only): outputs 0
+ *   evaluation  at offset p = (px, py): X = (x - 4 + c) 256 + px, ix = X >> 8, fx = X & 255 (Y likewise),
+ *               I = (256 - fx)(256 - fy) L[iy][ix] + fx (256 - fy) L[iy][ix+1] + (256 - fx) fy L[iy+1][ix] + fx fy L[iy+1][ix+1], e = (I - 65536 T[r][c] + 128) >> 8,
+ *               cost = N sum e^2 - (sum e)^2, bx = N sum gx e - sum gx sum e, by likewise
+ *   step        numx = Hyy bx - Hxy by, numy = Hxx by - Hxy bx, d = rdiv(-2 num, det) per axis, clamped to +-256; rdiv rounds to the nearest, halves away from zero
+ *   loop        p = (0, 0); at most iters times: step; d = (0, 0) stops; p += d; |px| or |py| > max_shift_q8: status 3, q8 = 0, cost = cost0, cost0; else the cost is
+ *               evaluated at the new p
+ *   status  0   q8_out[2 i ..] = the iterate of the smallest cost (the earliest on ties), cost_out[2 i ..] = cost at (0, 0), cost at q8
+ *   iters_out[i] = the number of steps taken (the one that left the window included)
+ * stats_out[0..3] count the statuses 0, 2, 3, -1 of this call.  Every intermediate fits int64 (|2 num| < 2^62.7).  Any output may be NULL; every element of a given output
+ * is written.  n == 0 is a successful no-op that zeroes stats_out.  on_device != 0: every pointer is a device pointer (4-byte aligned, cost_out 8-byte) and the call only
+ * enqueues on the ctx stream; otherwise it returns when the results are in the caller's arrays.  Results depend neither on n nor on the order of the points. */
+int vido_orb_patch_refine(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int iters, int max_shift_q8, int min_eig, int32_t* q8_out,
+                          int64_t* cost_out, int32_t* iters_out, int32_t* status_out, int32_t* stats_out, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device
@@ -820,6 +844,13 @@ int         vido_system_get_object_recover_stats(const vido_system* sys, int* n_
  * vido_system_get_object_verify_points a caller can recompute the call.  *n_out = n (0 with the key off or on a frame that verified nothing); VIDO_E_CAPACITY if cap is
  * smaller. */
 int         vido_system_get_object_recover_points(const vido_system* sys, int32_t* status, int32_t* dxy, int32_t* sums, int32_t* second, float* gather, float* after, int cap, int* n_out);
+/* Verify.ObjectRecoverSubpixel (default 0; needs Verify.ObjectRecover: 1): of the last tracked frame, n_tried = the object points the search re-found and
+ * vido_orb_patch_refine was given, n_refined = those it aligned (status 0), which moved to a sub-pixel position before the gather.  Both 0 with the key off. */
+int         vido_system_get_object_refine_stats(const vido_system* sys, int* n_tried, int* n_refined);
+/* Debug read of the same step, index-aligned with vido_system_get_object_recover_points (any array may be NULL): status [n] of vido_orb_patch_refine (-2: the point was
+ * not sent), q8 [n*2] and cost [n*2] as the call returned them (0 where not sent).  The call's centre is xyl + dxy of the two sibling read-backs at level 0, its reference
+ * their ref_patch, so a caller can recompute it.  *n_out = n (0 with the key off or on a frame that verified nothing); VIDO_E_CAPACITY if cap is smaller. */
+int         vido_system_get_object_refine_points(const vido_system* sys, int32_t* q8, int64_t* cost, int32_t* status, int cap, int* n_out);
 int         vido_system_save_results(vido_system* sys, const char* prefix);
 /* the vido_ctx the system's tracker runs on (NULL before the first frame): lets a caller share the device / query timings */
 vido_ctx*   vido_system_context(vido_system* sys);

@@ -118,6 +118,10 @@ public:
        returned them (0 where not searched); Gather = (depth, label) the slot holds at the re-found pixel (-1, -1 where status != 0); After per point (x, y, depth, label,
        last frame's flow x, y) as the step left them: for an accepted point the re-found pixel, its depth and label and pixel - last position, else unchanged. */
     std::vector<int32_t> mvObjRecoverStatus, mvObjRecoverDXY, mvObjRecoverSums, mvObjRecoverSecond; std::vector<float> mvObjRecoverGather, mvObjRecoverAfter;
+    /* extension (Verify.ObjectRecoverSubpixel: 1; without the key none of these vectors exists): index-aligned with mvObjRecover*.  Status of vido_orb_patch_refine for
+       the points the search found (0 refined, 2 no texture or an edge only, 3 left the window, -1 invalid) and -2 for a point that was not sent; Q8 (x, y in 1/256 px)
+       and Cost (at the re-found pixel, at Q8) as the call returned them (0 where not sent). */
+    std::vector<int32_t> mvObjRefineStatus, mvObjRefineQ8; std::vector<int64_t> mvObjRefineCost;
     Frame *mpPrevFrame = nullptr, *mpNextFrame = nullptr;
 };
 
@@ -230,6 +234,13 @@ public:
     bool bVerifyObjectRecover = false; int nObjRecoverRadius = 8, nObjRecoverExcl = 2, nObjRecoverMinZnccQ10 = 976, nObjRecoverPeakRatioQ10 = 0, nObjRecoverTried = 0, nObjRecovered = 0;
     void GetRecoverStats(int* n_tried, int* n_recovered) const { if (n_tried) *n_tried = nRecoverTried; if (n_recovered) *n_recovered = nRecovered; }
     bool bVerifyRecover = false; float fRecoverRadius = 32.f; int nRecoverLevelTol = 1, nRecoverMaxHamming = 50, nRecoverRatioNum = 0, nRecoverTried = 0, nRecovered = 0;
+    /* extension (Verify.ObjectRecoverSubpixel: 1, needs Verify.ObjectRecover: 1 and is off without it): between the search and the gather of RecoverRejectedObjects the
+       found points are aligned to 1/256 px (vido_orb_patch_refine, ONE call: blurred level 0, the same reference patch, centre = the re-found pixel).  A refined point
+       goes to re-found pixel + q8 / 256 + (last position - lrintf(last position)): the patch's displacement applied to the point's own sub-pixel last position; any
+       other status keeps the whole pixel.  Keys Verify.ObjectRecoverSubpixelIters (1 .. 8), Verify.ObjectRecoverSubpixelMaxShift (px, in [0, 2]; kept in 1/256 px) and
+       Verify.ObjectRecoverSubpixelMinEig (>= 0, the op's own unit): defaults from profiles/r19/patch_refine_cpu.txt. */
+    void GetObjectRefineStats(int* n_tried, int* n_refined) const { if (n_tried) *n_tried = nObjRefineTried; if (n_refined) *n_refined = nObjRefined; }
+    bool bVerifyObjectRecoverSubpixel = false; int nObjRefineIters = 6, nObjRefineMaxShiftQ8 = 384, nObjRefineMinEig = 0, nObjRefineTried = 0, nObjRefined = 0;
     std::vector<float> mvRecoverTrainXY, mvRecoverTrainDepth; std::vector<int> mvRecoverTrainLevel; std::vector<unsigned char> mvRecoverTrainDesc;
     /* extension (Mask.PropagateMissing: 1): a GrabImageRGBD call with an EMPTY mask, or a GrabImageRGBDDevice call with a null mask pointer, takes the frame's mask from
        the previous frame: its mask warped through its flow, the nearer (pre-scaled) depth winning a collision (vido_frame_propagate_mask), before any list is built.

@@ -49,6 +49,7 @@ struct vido_ctx {
     struct HamWinState* hamwin = nullptr;    // hamwin.hip: chunk partials, owner plane and staging of vido_hamming_match_window
     struct PatchPtsState* patchpts = nullptr; // patchpts.hip: staging of vido_orb_patch_points' host form
     struct PatchSearchState* patchsearch = nullptr; // patchsearch.hip: staging of vido_orb_patch_search's host form
+    struct PatchRefineState* patchrefine = nullptr; // patchrefine.hip: staging of vido_orb_patch_refine's host form
     struct PoseState* pose = nullptr;
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
@@ -88,7 +89,7 @@ int orb_collect(vido_ctx* ctx, int nf, int copy);
 int orb_mirror_async(vido_ctx* ctx, int nf);
 struct OrbView { const vido_keypoint* d_kpf; const int* d_nkp; int row_cap; const vido_keypoint* h_kpf; const uint8_t* h_descf; const int* h_frame_beg; };
 OrbView orb_view(vido_ctx* ctx);
-int orb_frame_planes(vido_ctx* ctx, int frame, const uint8_t** pyr, const uint8_t** blur, PyrDev* P);      // (orb.hip) for patchpts.hip, patchsearch.hip: 0 = frame outside the batch
+int orb_frame_planes(vido_ctx* ctx, int frame, const uint8_t** pyr, const uint8_t** blur, PyrDev* P);      // (orb.hip) for patchpts.hip, patchsearch.hip, patchrefine.hip: 0 = frame outside the batch
 void track_state_destroy(vido_ctx* ctx);
 int track_slot_maps(vido_ctx* ctx, int slot, float** depth, float** flow, int32_t** mask, int* W, int* H);      // (track.hip) for maskprop.hip, maskcc.hip
 void maskprop_state_destroy(vido_ctx* ctx);
@@ -98,6 +99,7 @@ void ham_state_destroy(vido_ctx* ctx);
 void hamwin_state_destroy(vido_ctx* ctx);
 void patchpts_state_destroy(vido_ctx* ctx);
 void patchsearch_state_destroy(vido_ctx* ctx);
+void patchrefine_state_destroy(vido_ctx* ctx);
 void pose_state_destroy(vido_ctx* ctx);
 void ba_state_destroy(vido_ctx* ctx);
 // device-resident inputs of the local-window solve (bawin.hip assembles them, ba.hip solves): observations sorted by camera, landmark-major slot tables, points (in / out)

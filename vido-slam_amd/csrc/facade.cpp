@@ -901,6 +901,13 @@ Tracking::Tracking(System* pSys, Map* pMap, const std::string& path, const int s
             throw std::runtime_error("Tracking: Verify.ObjectRecoverRadius must be in [0, 16], Verify.ObjectRecoverExcl in [1, 16], Verify.ObjectRecoverMinZncc and Verify.ObjectRecoverPeakRatio in [0, 1]");
         nObjRecoverRadius = (int)lrint(r); nObjRecoverExcl = (int)lrint(e); nObjRecoverMinZnccQ10 = (int)lrint(1024.0 * z); nObjRecoverPeakRatioQ10 = (int)lrint(1024.0 * pr);
     }
+    bVerifyObjectRecoverSubpixel = bVerifyObjectRecover && num(kv, "Verify.ObjectRecoverSubpixel", 0) != 0;      // (off without Verify.ObjectRecover; defaults: profiles/r19/patch_refine_cpu.txt)
+    if (bVerifyObjectRecoverSubpixel) {
+        const double it = num(kv, "Verify.ObjectRecoverSubpixelIters", 6), ms = num(kv, "Verify.ObjectRecoverSubpixelMaxShift", 1.5), me = num(kv, "Verify.ObjectRecoverSubpixelMinEig", 0);
+        if (!(it >= 1.0) || !(it <= 8.0) || !(ms >= 0.0) || !(ms <= 2.0) || !(me >= 0.0) || !(me <= 2147483647.0))
+            throw std::runtime_error("Tracking: Verify.ObjectRecoverSubpixelIters must be in [1, 8], Verify.ObjectRecoverSubpixelMaxShift in [0, 2] px, Verify.ObjectRecoverSubpixelMinEig in [0, 2^31)");
+        nObjRefineIters = (int)lrint(it); nObjRefineMaxShiftQ8 = (int)lrint(256.0 * ms); nObjRefineMinEig = (int)lrint(me);
+    }
     if (bVerifyRecover && (!(fRecoverRadius >= 0.f) || !(fRecoverRadius < 1e9f) || nRecoverRatioNum < 0 || nRecoverRatioNum > 1024))
         throw std::runtime_error("Tracking: Verify.RecoverRadius must be finite and >= 0, Verify.RecoverRatio in [0, 1]");
     bPropagateMissingMask = num(kv, "Mask.PropagateMissing", 0) != 0;
@@ -1057,7 +1064,7 @@ cv::Mat Tracking::GrabCommon(const double& timestamp, const int& nImage, void* t
         if (no) check(vido_gather_object_depth_label(c, slot_cur_, oxy.data(), no, mThDepthObj, F->mvObjDepth.data(), F->vSemObjLabel.data()), "gather_object");
         nObjVerifyChecked = nObjVerifyRejected = nObjVerifyNoTexture = 0;
         if (bVerifyObjectPatch) VerifyObjectPatches();
-        nObjRecoverTried = nObjRecovered = 0;
+        nObjRecoverTried = nObjRecovered = 0; nObjRefineTried = nObjRefined = 0;
         if (bVerifyObjectRecover) RecoverRejectedObjects();
         TemperalMatch.assign(F->N_s, -1);
         nVerifyChecked = nVerifyRejected = 0; nRecoverTried = nRecovered = 0;
@@ -1133,6 +1140,7 @@ void Tracking::RecoverRejectedObjects()
     Frame *F = mpCurrentFrame, *L = mpLastFrame; const int n = (int)F->mvObjKeys.size();
     F->mvObjRecoverStatus.assign(n, -2); F->mvObjRecoverDXY.assign(2 * (size_t)n, 0); F->mvObjRecoverSums.assign(3 * (size_t)n, 0); F->mvObjRecoverSecond.assign(2 * (size_t)n, 0);
     F->mvObjRecoverGather.assign(2 * (size_t)n, -1.f);
+    if (bVerifyObjectRecoverSubpixel) { F->mvObjRefineStatus.assign(n, -2); F->mvObjRefineQ8.assign(2 * (size_t)n, 0); F->mvObjRefineCost.assign(2 * (size_t)n, 0); }
     std::vector<int> which;
     if (n > 0 && F->mvObjVerifyRef.size() == 64 * (size_t)n && (int)F->mvObjVerifyStatus.size() == n && (int)L->mvObjKeys.size() == n && (int)L->mvObjCorres.size() == n &&
         (int)L->mvObjFlowNext.size() == n && (int)L->vSemObjLabel.size() == n)
@@ -1158,6 +1166,28 @@ void Tracking::RecoverRejectedObjects()
             found.push_back(i); fxy.push_back((float)(xyl[3 * (size_t)k] + dxy[2 * (size_t)k])); fxy.push_back((float)(xyl[3 * (size_t)k + 1] + dxy[2 * (size_t)k + 1]));
         }
         const int nf = (int)found.size();
+        // Verify.ObjectRecoverSubpixel: the found points, centred on the re-found pixel, are aligned to 1/256 px against the same reference patch (ONE call).  The patch was
+        // cut at lrintf of the last position, so its displacement q8 / 256 carries the point's own fraction along: p' = re-found pixel + q8 / 256 + (last - lrintf(last)),
+        // formed in double and rounded once.  A point that is not refined (no texture, an edge only, left the window, too close to the border) keeps the whole pixel.
+        if (bVerifyObjectRecoverSubpixel && nf > 0) {
+            std::vector<int32_t> rxyl(3 * (size_t)nf), rq8(2 * (size_t)nf), rst(nf); std::vector<int64_t> rcost(2 * (size_t)nf); std::vector<uint8_t> rref(64 * (size_t)nf); int32_t rstats[4];
+            for (int k = 0; k < nf; k++) {
+                rxyl[3 * (size_t)k] = (int32_t)fxy[2 * (size_t)k]; rxyl[3 * (size_t)k + 1] = (int32_t)fxy[2 * (size_t)k + 1]; rxyl[3 * (size_t)k + 2] = 0;
+                memcpy(&rref[64 * (size_t)k], &F->mvObjVerifyRef[64 * (size_t)found[k]], 64);
+            }
+            if (timed_call([&]() -> int { return vido_orb_patch_refine(c, 0, rxyl.data(), nf, 1, rref.data(), nObjRefineIters, nObjRefineMaxShiftQ8, nObjRefineMinEig, rq8.data(), rcost.data(), nullptr,
+                                                                       rst.data(), rstats, 0); }, "orb_patch_refine") != VIDO_OK) throw std::runtime_error(vido_last_error(c));
+            nObjRefineTried = nf;
+            for (int k = 0; k < nf; k++) {
+                const int i = found[k];
+                F->mvObjRefineStatus[i] = rst[k]; memcpy(&F->mvObjRefineQ8[2 * (size_t)i], &rq8[2 * (size_t)k], 2 * sizeof(int32_t)); memcpy(&F->mvObjRefineCost[2 * (size_t)i], &rcost[2 * (size_t)k], 2 * sizeof(int64_t));
+                if (rst[k] != 0) continue;
+                const cv::Point2f lp = L->mvObjKeys[i].pt;
+                fxy[2 * (size_t)k] = (float)((double)rxyl[3 * (size_t)k] + (double)rq8[2 * (size_t)k] / 256.0 + ((double)lp.x - (double)lrintf(lp.x)));
+                fxy[2 * (size_t)k + 1] = (float)((double)rxyl[3 * (size_t)k + 1] + (double)rq8[2 * (size_t)k + 1] / 256.0 + ((double)lp.y - (double)lrintf(lp.y)));
+                nObjRefined++;
+            }
+        }
         if (nf > 0) {
             std::vector<float> fd(nf, -1.f); std::vector<int32_t> fl(nf, -1);
             check(vido_gather_object_depth_label(c, slot_cur_, fxy.data(), nf, mThDepthObj, fd.data(), fl.data()), "gather_object(recover)");
@@ -1854,6 +1884,34 @@ int vido_system_get_object_recover_points(const vido_system* s, int32_t* status,
     if (second) memcpy(second, F->mvObjRecoverSecond.data(), sizeof(int32_t) * 2 * n);
     if (gather) memcpy(gather, F->mvObjRecoverGather.data(), sizeof(float) * 2 * n);
     if (after) memcpy(after, F->mvObjRecoverAfter.data(), sizeof(float) * 6 * n);
+    return VIDO_OK;
+}
+
+int vido_system_get_object_refine_stats(const vido_system* s, int* n_tried, int* n_refined)
+{
+    if (!s || !s->inited) return VIDO_E_INVALID;
+    if (n_tried) *n_tried = 0;
+    if (n_refined) *n_refined = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (T) T->GetObjectRefineStats(n_tried, n_refined);
+    return VIDO_OK;
+}
+
+int vido_system_get_object_refine_points(const vido_system* s, int32_t* q8, int64_t* cost, int32_t* status, int cap, int* n_out)
+{
+    if (!s || !s->inited || !n_out) return VIDO_E_INVALID;
+    *n_out = 0;
+    VIDO_SLAM::Tracking* T = const_cast<vido_system*>(s)->sys.GetTracker();
+    if (!T || !T->mpCurrentFrame || !T->bVerifyObjectRecoverSubpixel) return VIDO_OK;
+    const VIDO_SLAM::Frame* F = T->mpCurrentFrame;
+    const int n = F->mvObjVerifyRef.empty() ? 0 : (int)F->mvObjRefineStatus.size();      // (no reference patches: the frame verified nothing)
+    *n_out = n;
+    if (n > cap) return VIDO_E_CAPACITY;
+    if (n == 0) return VIDO_OK;
+    if ((int)F->mvObjRefineQ8.size() != 2 * n || (int)F->mvObjRefineCost.size() != 2 * n) return VIDO_E_INVALID;
+    if (q8) memcpy(q8, F->mvObjRefineQ8.data(), sizeof(int32_t) * 2 * n);
+    if (cost) memcpy(cost, F->mvObjRefineCost.data(), sizeof(int64_t) * 2 * n);
+    if (status) memcpy(status, F->mvObjRefineStatus.data(), sizeof(int32_t) * n);
     return VIDO_OK;
 }
 

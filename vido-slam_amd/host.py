@@ -68,6 +68,8 @@ def load_library():
     lib.vido_orb_patch_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_patch_search.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_orb_patch_refine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -259,6 +261,28 @@ class Context:
         vp = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.vido_orb_patch_search(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(radius), int(excl), int(min_var), int(min_zncc_q10), int(peak_ratio_q10),
                                                    vp(dxy_ptr), vp(sums_ptr), vp(second_ptr), vp(status_ptr), vp(stats_ptr), 1))
+
+    def orb_patch_refine(self, frame, xyl, ref_patch, iters=6, max_shift_q8=384, min_eig=0, blurred=1):
+        """Sub-pixel alignment of ref_patch (n,64) u8 to pyramid slab `frame` around xyl (n,3) i32 = x, y in level coordinates, level (vido_orb_patch_refine; the statement
+        is tests/refimpl/patch_refine_np.py): integer inverse-compositional Gauss-Newton, translation + bias, over the 36 interior pixels.  Returns (q8 (n,2) i32 = the
+        offset in 1/256 px, cost (n,2) i64 = cost at (0, 0), cost at q8, iters (n,) i32 = steps taken, status (n,) i32: 0 refined, 2 no texture or an edge only
+        (smaller eigenvalue below min_eig), 3 an iterate left +-max_shift_q8, -1 invalid; stats (4,) i32 = the counts of 0, 2, 3, -1).  Every intermediate fits int64:
+        |e| <= 65 280, |g| <= 255, |b| < 2^34.4, H < 2^26.4, det < 2^53, |2 num| < 2^62.7, cost < 2^42.4."""
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3); n = len(xyl)
+        ref_patch = np.ascontiguousarray(ref_patch, np.uint8).reshape(-1, 64)
+        if len(ref_patch) != n:
+            raise VidoError(-1, "orb_patch_refine: %d reference patches for %d points" % (len(ref_patch), n))
+        q8 = np.empty((n, 2), np.int32); cost = np.empty((n, 2), np.int64); it = np.empty(n, np.int32); status = np.empty(n, np.int32); stats = np.empty(4, np.int32)
+        self._check(self.lib.vido_orb_patch_refine(self.h, frame, _ptr(xyl), n, int(blurred), _ptr(ref_patch), int(iters), int(max_shift_q8), int(min_eig),
+                                                   _ptr(q8), _ptr(cost), _ptr(it), _ptr(status), _ptr(stats), 0))
+        return q8, cost, it, status, stats
+
+    def orb_patch_refine_device(self, frame, xyl_ptr, n, ref_ptr, iters=6, max_shift_q8=384, min_eig=0, blurred=1, q8_ptr=None, cost_ptr=None, iters_ptr=None, status_ptr=None,
+                                stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_orb_patch_refine(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(iters), int(max_shift_q8), int(min_eig),
+                                                   vp(q8_ptr), vp(cost_ptr), vp(iters_ptr), vp(status_ptr), vp(stats_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

@@ -53,6 +53,8 @@ def _bind(lib):
     lib.vido_system_get_object_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.vido_system_get_object_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vido_system_get_object_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.vido_system_get_object_refine_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vido_system_get_object_refine_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib._vido_system_bound = True
     return lib
 
@@ -229,6 +231,24 @@ class System:
         if rc != VIDO_OK:
             raise VidoError(rc, "vido_system_get_object_recover_points")
         return dict(status=status[:n], dxy=dxy[:n], sums=sums[:n], second=second[:n], gather=gather[:n], after=after[:n])
+
+    def object_refine_stats(self):
+        """(n_tried, n_refined) of the last frame's sub-pixel alignment of the re-found object points (Verify.ObjectRecoverSubpixel: 1; both 0 otherwise)."""
+        a, b = C.c_int(), C.c_int()
+        self.lib.vido_system_get_object_refine_stats(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def object_refine_points(self):
+        """Debug read of the last frame's Verify.ObjectRecoverSubpixel step (vido_system_get_object_refine_points), index-aligned with object_recover_points(): dict of
+        status (n,) i32 of vido_orb_patch_refine (-2: not sent), q8 (n,2) i32 and cost (n,2) i64 as the call returned them."""
+        n = C.c_int()
+        self.lib.vido_system_get_object_refine_points(self.h, None, None, None, 0, C.byref(n))
+        n = n.value; m = max(n, 1)
+        q8 = np.empty((m, 2), np.int32); cost = np.empty((m, 2), np.int64); status = np.empty(m, np.int32)
+        rc = self.lib.vido_system_get_object_refine_points(self.h, q8.ctypes.data, cost.ctypes.data, status.ctypes.data, m, C.byref(C.c_int()))
+        if rc != VIDO_OK:
+            raise VidoError(rc, "vido_system_get_object_refine_points")
+        return dict(status=status[:n], q8=q8[:n], cost=cost[:n])
 
     def SaveResultsIJRR2020(self, filename=""):
         rc = self.lib.vido_system_save_results(self.h, os.fsencode(filename))
