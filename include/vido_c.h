@@ -176,6 +176,34 @@ int vido_orb_patch_search(vido_ctx* ctx, int frame, const int32_t* xyl, int n, i
 int vido_orb_patch_refine(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int iters, int max_shift_q8, int min_eig, int32_t* q8_out,
                           int64_t* cost_out, int32_t* iters_out, int32_t* status_out, int32_t* stats_out, int on_device);
 
+/* Dense optical flow of the Dense Inverse Search kind from img0 to img1, two u8 images of one size, to 1/256 px and entirely in integers (no reference call site; defined by
+ * tests/refimpl/dis_flow_np.py, exact to the bit).  16 <= width, height <= 4095; channels 1, 3 or 4 (interleaved; rgb_order as in vido_orb_extract_color), stride in bytes
+ * >= width * channels; 0 <= coarsest <= 6 with min(width, height) >> coarsest >= 8; 1 <= iters <= 16; 0 <= max_shift_q8 <= 2048 (1/256 px); min_eig >= 0; VIDO_E_INVALID
+ * otherwise, and when all three outputs are NULL.  Needs no extractor state and not the context's configured frame size.  In the order the rules apply:
+ *   grey        1 channel: the bytes; else (1868 B + 9617 G + 4899 R + 8192) >> 14
+ *   pyramid     levels 0 .. coarsest of both images, w[l+1] = w[l] >> 1, h likewise, G[l+1][y][x] = (sum of the 2 x 2 block + 2) >> 2
+ *   flow        U[l][y][x] = (ux, uy) in 1/256 px of level l, from level coarsest down to 0; the initial field is 0 at the coarsest level and
+ *               2 U[l+1][min(y >> 1, h[l+1] - 1)][min(x >> 1, w[l+1] - 1)] below
+ *   patches     8 x 8, origins 0, 4, 8, ... while o + 8 <= n along an axis of length n, plus n - 8 when that is not among them; u0 = the initial field at (x0 + 4, y0 + 4)
+ *   template    N = 64; T = the patch of image 0, gx = G0[y][min(x+1, w-1)] - G0[y][max(x-1, 0)], gy likewise; Hxx = N sum gx^2 - (sum gx)^2, Hyy, Hxy likewise,
+ *               det = Hxx Hyy - Hxy^2, tr = Hxx + Hyy; flat (keeps u0) when det <= 0 or tr < 2 min_eig or det - min_eig tr + min_eig^2 < 0
+ *   sample      S(X, Y) of image 1 at 1/256 px: X clamped to [0, (w-1) 256], ix = X >> 8, fx = X & 255, right neighbour min(ix+1, w-1), y likewise; bilinear, weights sum 65536
+ *   evaluation  at u: e = (S((x0+c) 256 + ux, (y0+r) 256 + uy) - 65536 T[r][c] + 2048) >> 12 (1/16 grey), cost = N sum e^2 - (sum e)^2, bx = N sum gx e - sum gx sum e, by likewise
+ *   step        d = rdiv(-32 (Hyy bx - Hxy by), det), rdiv(-32 (Hxx by - Hxy bx), det), each clamped to +-256; rdiv rounds to the nearest, halves away from zero
+ *   loop        u = u0; at most iters times: step; d = (0, 0) stops; u += d; max(|ux - u0x|, |uy - u0y|) > max_shift_q8: rejected (keeps u0); else the cost is evaluated at
+ *               the new u.  The iterate of the smallest cost wins, the earliest on ties
+ *   densify     pixel (x, y) of level l over every patch p that holds it: d = |S(x 256 + u_p.x, y 256 + u_p.y) - 65536 G0[y][x]| >> 16, wgt = 65536 / max(1, d) (integer),
+ *               U = rdiv(sum wgt u_p.x, sum wgt), rdiv(sum wgt u_p.y, sum wgt)
+ * q8_out [h*w*2] = U[0]; flow_out [h*w*2] = q8 / 256 in pixels (dx, dy; exact); stats [4], summed over the levels: patches that kept an iterate, flat patches, rejected
+ * patches, steps taken.  Every intermediate fits int64 (H < 2^28, |b| < 2^32, |2 num| < 2^62, cost < 2^36; the step's division is taken in two parts).  Any output may be
+ * NULL, not all.  on_device != 0: every pointer is a device pointer (outputs 4-byte aligned) and the call only enqueues on the ctx stream (vido_set_stream's when one is
+ * set): no host synchronisation, so a call can sit inside a stream capture — except the first call of a size, which grows the context's scratch (the two pyramids, the
+ * fields of the levels above 0, one level's patch flows).  Otherwise the images and outputs are the caller's host arrays, staged through pinned buffers that grow on demand,
+ * and the call returns when the results are there.  A result depends on nothing but the two images and the parameters. */
+int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int channels, int rgb_order, int stride, int width, int height,
+                  int coarsest, int iters, int max_shift_q8, int min_eig,
+                  float* flow_out /* [h*w*2], NULL ok */, int32_t* q8_out /* [h*w*2], NULL ok */, int32_t* stats /* [4], NULL ok */, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device

@@ -50,6 +50,7 @@ struct vido_ctx {
     struct PatchPtsState* patchpts = nullptr; // patchpts.hip: staging of vido_orb_patch_points' host form
     struct PatchSearchState* patchsearch = nullptr; // patchsearch.hip: staging of vido_orb_patch_search's host form
     struct PatchRefineState* patchrefine = nullptr; // patchrefine.hip: staging of vido_orb_patch_refine's host form
+    struct DisFlowState* disflow = nullptr;  // disflow.hip: pyramids, per-level fields and staging of vido_dis_flow
     struct PoseState* pose = nullptr;
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
@@ -100,6 +101,7 @@ void hamwin_state_destroy(vido_ctx* ctx);
 void patchpts_state_destroy(vido_ctx* ctx);
 void patchsearch_state_destroy(vido_ctx* ctx);
 void patchrefine_state_destroy(vido_ctx* ctx);
+void disflow_state_destroy(vido_ctx* ctx);
 void pose_state_destroy(vido_ctx* ctx);
 void ba_state_destroy(vido_ctx* ctx);
 // device-resident inputs of the local-window solve (bawin.hip assembles them, ba.hip solves): observations sorted by camera, landmark-major slot tables, points (in / out)

@@ -70,6 +70,7 @@ def load_library():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_orb_patch_refine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_dis_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -283,6 +284,31 @@ class Context:
         vp = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.vido_orb_patch_refine(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(iters), int(max_shift_q8), int(min_eig),
                                                    vp(q8_ptr), vp(cost_ptr), vp(iters_ptr), vp(status_ptr), vp(stats_ptr), 1))
+
+    def dis_flow(self, img0, img1, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0):
+        """Dense optical flow from img0 to img1 (vido_dis_flow; the statement is tests/refimpl/dis_flow_np.py): u8 H x W or H x W x 3|4 host arrays of one shape (a row
+        stride above the width is taken from the array's strides).  Integer inverse-compositional alignment of every 8 x 8 patch on a factor-2 pyramid of coarsest + 1
+        levels, densified by photometric weights.  Returns (flow (H,W,2) f32 in pixels, q8 (H,W,2) i32 = the same in 1/256 px, stats (4,) i32 = patches that kept an
+        iterate, flat, rejected, steps taken, over all levels)."""
+        img0, img1 = np.asarray(img0), np.asarray(img1)
+        if img0.dtype != np.uint8 or img1.dtype != np.uint8 or img0.shape != img1.shape or img0.ndim not in (2, 3):
+            raise VidoError(-1, "dis_flow: two u8 images of one shape, H x W or H x W x C, expected")
+        cn = 1 if img0.ndim == 2 else img0.shape[2]
+        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
+        if not rows(img0) or not rows(img1) or img0.strides[0] != img1.strides[0]:
+            img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
+        h, w = img0.shape[:2]
+        flow = np.empty((h, w, 2), np.float32); q8 = np.empty((h, w, 2), np.int32); stats = np.empty(4, np.int32)
+        self._check(self.lib.vido_dis_flow(self.h, C.c_void_p(img0.ctypes.data), C.c_void_p(img1.ctypes.data), cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+                                           int(max_shift_q8), int(min_eig), _ptr(flow), _ptr(q8), _ptr(stats), 0))
+        return flow, q8, stats
+
+    def dis_flow_device(self, img0_ptr, img1_ptr, channels, stride, width, height, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, flow_ptr=None, q8_ptr=None,
+                        stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the context's scratch); any output pointer may be None, not all."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_dis_flow(self.h, vp(img0_ptr), vp(img1_ptr), int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
+                                           int(max_shift_q8), int(min_eig), vp(flow_ptr), vp(q8_ptr), vp(stats_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

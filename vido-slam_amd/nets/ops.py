@@ -720,6 +720,44 @@ class HipOps:
                                                          H, W, C.c_void_p(out.data_ptr()), C.c_void_p(stats.data_ptr()) if stats is not None else None))
         return out
 
+    def dis_flow(self, prev, cur, out=None, q8=None, stats=None, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0):
+        """vido_dis_flow on device tensors: prev, cur uint8 [H,W] or [H,W,3|4] of one shape -> the dense flow from prev into cur, float32 [H,W,2] (dx, dy) in pixels
+        (`out`, or a new tensor).  q8: an int32 [H,W,2] tensor that receives the same field in 1/256 px, or None; stats: an int32 tensor of >= 4 elements that receives
+        (patches that kept an iterate, flat, rejected, steps), or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/dis_flow_np.py.  Enqueued on
+        torch's current stream, nothing is waited for; the first call of a size grows the context's scratch, so it comes before a graph capture.  CPU tensors, other
+        dtypes or shapes and non-contiguous tensors raise."""
+        from ..host import VidoError
+        def bad(why):
+            raise VidoError(-1, "dis_flow: " + why)
+        for name, t, dt in (("prev", prev, torch.uint8), ("cur", cur, torch.uint8), ("out", out, torch.float32), ("q8", q8, torch.int32), ("stats", stats, torch.int32)):
+            if t is None and name not in ("prev", "cur"):
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != prev.device:
+                bad("%s is on another device than prev" % name)
+        if prev.dim() not in (2, 3) or (prev.dim() == 3 and prev.shape[2] not in (3, 4)):
+            bad("prev must be [H, W] or [H, W, 3|4], got %s" % (tuple(prev.shape),))
+        if tuple(cur.shape) != tuple(prev.shape):
+            bad("cur must have prev's shape %s, got %s" % (tuple(prev.shape), tuple(cur.shape)))
+        H, W = int(prev.shape[0]), int(prev.shape[1]); cn = 1 if prev.dim() == 2 else int(prev.shape[2])
+        if out is None:
+            out = torch.empty((H, W, 2), device=prev.device, dtype=torch.float32)
+        for name, t in (("out", out), ("q8", q8)):
+            if t is not None and tuple(t.shape) != (H, W, 2):
+                bad("%s must be [%d, %d, 2], got %s" % (name, H, W, tuple(t.shape)))
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_dis_flow(self.ctx.h, C.c_void_p(prev.data_ptr()), C.c_void_p(cur.data_ptr()), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters),
+                                                   int(max_shift_q8), int(min_eig), C.c_void_p(out.data_ptr()), C.c_void_p(q8.data_ptr()) if q8 is not None else None,
+                                                   C.c_void_p(stats.data_ptr()) if stats is not None else None, 1))
+        return out
+
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
         """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
         (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),

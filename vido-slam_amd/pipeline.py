@@ -219,15 +219,21 @@ class NetNodes:
     the dynamic head would rank the detections anew after the ids were given, so it is skipped and only counted in det_overflows.  Not with skip_detector (infer() raises
     ValueError: a frame without a detector image would leave the carried image and the id state behind the sequence).  Not with on_range="recompute", for
     the reason that applies to detect_every > 1: every later mask descends from the flows already used.  With stable_ids = False nothing of this exists: the launches,
-    the id bases and the outputs are those of before."""
+    the id bases and the outputs are those of before.
+
+    flow_source = "dis" (default "net": LiteFlowNet, and nothing below applies): the flow is HipOps.dis_flow of the two BGR frames (csrc/disflow.hip, INTEGRATION.md §39;
+    dis_params: a dict of coarsest / iters / max_shift_q8 / min_eig, the op's defaults otherwise) on the flow context and the flow stream, captured into g_flow like
+    LiteFlowNet.  LiteFlowNet is not constructed (flow_net is None).  The op is all-integer: the flow half of the range words stays 0 and recompute() leaves the flow alone.
+    detect_every, stable_ids and EndToEnd take the tensor as they take LiteFlowNet's."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
-                 detect_every=1, stable_ids=False, stable_hold=0):
+                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
+        self.flow_source, self.dis_params = self._check_flow_source(flow_source, dis_params)
         self._check_stable_ids(stable_ids, stable_hold, label_mode, on_range)
         self.stable_ids = bool(stable_ids); self.stable_hold = int(stable_hold); self._ids = None
         self.detect_every = int(detect_every)
@@ -253,9 +259,9 @@ class NetNodes:
         self.ctx2 = _Context(device=ctx.cfg.device, width=ctx.cfg.width, height=ctx.cfg.height, max_batch=1)
         self.ops = ops = _nets.HipOps(ctx)                # Mask R-CNN (ROI-Align, NMS, box decode, paste) + MonoDepth2 epilogues
         self.ops_flow = _nets.HipOps(self.ctx2)           # LiteFlowNet (cost volume, epilogues)
-        self.flow_net = _nets.fill_deterministic(_nets.LiteFlowNet(self.ops_flow.correlation, epilogue=self.ops_flow.bias_act_, warp=self.ops_flow.backwarp,
-                                                                       fused=None if _os.environ.get("VIDO_LFN_NO_FUSED") else self.ops_flow,
-                                                                       pair_batch=not _os.environ.get("VIDO_LFN_NO_PAIR_BATCH")), seed).eval().to(dev)
+        self.flow_net = None if self.flow_source == "dis" else _nets.fill_deterministic(
+            _nets.LiteFlowNet(self.ops_flow.correlation, epilogue=self.ops_flow.bias_act_, warp=self.ops_flow.backwarp, fused=None if _os.environ.get("VIDO_LFN_NO_FUSED") else self.ops_flow,
+                              pair_batch=not _os.environ.get("VIDO_LFN_NO_PAIR_BATCH")), seed).eval().to(dev)
         self.depth_net = _nets.fill_deterministic(_nets.MonoDepth2(), seed + 1).eval().to(dev)
         self.mask_net = _nets.fill_maskrcnn(_nets.MaskRCNN(ops), seed + 2).eval().to(dev)
         if label_mode == "instance" and self.mask_net.config.detections_per_img > self.ID_BASES[1]:
@@ -297,7 +303,10 @@ class NetNodes:
         self.last_counts = None
         self.det_overflows = 0                                        # frames whose detection count exceeded the static head's slots (redone through the dynamic head)
         ex = torch.zeros((height, width, 3), dtype=torch.uint8, device=dev)
-        self._flow_fn = lambda a, b: _nets.analyse_flow(self.flow_net, a, b)
+        if self.flow_source == "dis":                                 # the op on the flow context (its first call of the size, below, grows the context's scratch: before any capture)
+            self._flow_fn = lambda a, b: self.ops_flow.dis_flow(a, b, **self.dis_params)
+        else:
+            self._flow_fn = lambda a, b: _nets.analyse_flow(self.flow_net, a, b)
         self._depth_fn = lambda a: _nets.analyse_depth(self.depth_net, a, feed=self.depth_feed, ops=ops).to(torch.float32)
         self._trunk_fn = lambda a: self.mask_net.trunk(_nets.maskrcnn.image_to_feed(a, dev, self.mask_feed, ops=ops))
         # the whole detector with static shapes (nets/maskrcnn.py: heads_static / analyse_image_static): trunk + device-side RPN selection + box head + fixed-slot
@@ -421,6 +430,17 @@ class NetNodes:
             self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
 
+    FLOW_SOURCES = ("net", "dis")
+    DIS_PARAMS = ("coarsest", "iters", "max_shift_q8", "min_eig")
+
+    @classmethod
+    def _check_flow_source(cls, flow_source, dis_params):
+        if flow_source not in cls.FLOW_SOURCES:
+            raise ValueError("flow_source: one of %s, not %r" % (cls.FLOW_SOURCES, flow_source))
+        if dis_params is not None and (flow_source != "dis" or not isinstance(dis_params, dict) or any(k not in cls.DIS_PARAMS for k in dis_params)):
+            raise ValueError("dis_params: with flow_source='dis', a dict with keys among %s, not %r" % (cls.DIS_PARAMS, dis_params))
+        return flow_source, dict(dis_params or {})
+
     @staticmethod
     def _check_detect_every(detect_every, on_range):
         import numbers as _numbers
@@ -483,7 +503,7 @@ class NetNodes:
         n_det are None after the dynamic head (no static detector).  The caller serialises it with infer() (the nodes' host-side state has one user at a time).
         id_base (label_mode="instance"): the id base infer() gave THAT frame (its self.id_base then); None: the last frame's."""
         out = {"flow": None, "detector": None}
-        if flow:
+        if flow and self.flow_source == "net":                        # (the integer flow op launches nothing whose range can be left: nothing to recompute)
             with _nets.range_safe(self.flow_net):
                 out["flow"] = self._flow_fn(prev_bgr, cur_bgr).contiguous()
             self.range_recomputes["flow"] += 1
