@@ -3324,6 +3324,12 @@ static int ba_run(vido_ctx* ctx, vido_ba_problem* prob, vido_ba_dynamic* dynp, v
     // (previous solve's trials + 2) trial slots on the stream in one go and waits ONCE; a solve that needs more gets four more slots at a time.  No host round trip per trial:
     // inside the pipeline each one cost a stream drain behind the networks' workgroups.
     const bool local_static = lds_path && !allreduce && nd == 0 && n6 % 6 == 0 && n6 >= 12 && n_pose <= 64 && D.n_odo <= 64 && n_long == 0 && p.max_iters >= 1 && n_ptl > 0 && no > 0;
+    if (getenv("VIDO_BA_VERBOSE")) {      // what is launched below, by name (the selections at the Schur launch and the reduced solve, restated)
+        const char* schur = !n_ptl ? "none" : (lds_path ? "schur0" : (use_mfma_schur ? "mfma" : "schur2"));
+        const char* solver = lds_path ? ((n6 % 6 == 0 && n6 >= 12) ? "small6" : "small") : (Bc.m ? (Bc.m == 66 ? "bcr66" : "bcr96") :
+                             (D.bw < 0 ? "dense" : (band6_lds ? "band6" : (band6s_lds ? (band6s_nb == 8 ? "band6s8" : "band6s4") : "band"))));
+        fprintf(stderr, "[ba] path: schur %s schur_long %d | solver %s | driver %s\n", schur, n_long, solver, local_static ? "resident" : "host");
+    }
     if (local_static) {
         if (!BS->d_ticket) { HIP_TRY(ctx, hipMalloc((void**)&BS->d_ticket, sizeof(int))); HIP_TRY(ctx, hipMemset(BS->d_ticket, 0, sizeof(int))); }
         const int parts_grid = std::min(128, std::max(1, (n_ptl + 3) / 4));       // partial reduced systems: every one is summed by the fold; tracker alone: 32 / 64 / 128 / 256 partials -> 2.49 / 2.13 / 1.95 / 1.95 ms per solve
