@@ -204,6 +204,38 @@ int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int c
                   int coarsest, int iters, int max_shift_q8, int min_eig,
                   float* flow_out /* [h*w*2], NULL ok */, int32_t* q8_out /* [h*w*2], NULL ok */, int32_t* stats /* [4], NULL ok */, int on_device);
 
+/* Forward-backward check of two dense flow fields, entirely in integers (no reference call site; defined by tests/refimpl/flow_consistency_np.py, exact to the bit).
+ * fwd_q8, bwd_q8 [H*W*2] (dx, dy) in 1/256 px: the flow of image 0 -> 1 on image 0's grid and of image 1 -> 0 on image 1's grid, the layout of vido_dis_flow's q8.
+ * 1 <= H, W <= 4095; 0 <= alpha_q10 <= 1024 (alpha = alpha_q10 / 1024); 0 <= beta_q16 <= 2^30 (beta = beta_q16 / 65536 px^2); VIDO_E_INVALID otherwise, for a NULL
+ * field and when all three outputs are NULL.  Needs no other state of the context.  For pixel (x, y) with f = fwd[y][x], in the order the rules apply:
+ *   status 3    not a flow: |f.x| or |f.y| >= 2^19
+ *   status 2    leaves the image: tx = 256 x + f.x, ty = 256 y + f.y; tx < 0, tx > 256 (W - 1), ty < 0 or ty > 256 (H - 1)
+ *   taps        x0 = tx >> 8, ax = tx & 255, x1 = min(x0 + 1, W - 1), y likewise; bwd[y0][x0], bwd[y0][x1], bwd[y1][x0], bwd[y1][x1], all four also where a weight is 0;
+ *               status 3 when a component of one of them has |.| >= 2^19
+ *   b           s = (256-ax)(256-ay) B[y0][x0] + ax (256-ay) B[y0][x1] + (256-ax) ay B[y1][x0] + ax ay B[y1][x1] per component, b = (s + 32768) >> 16 (arithmetic shift)
+ *   r           r = f + b
+ *   status 1    inconsistent: 1024 |r|^2 > alpha_q10 (|f|^2 + |b|^2) + 1024 beta_q16 (squares summed over both components); else status 0
+ * status_out [H*W] = the status; flow_marked_out [H*W*2] = f / 256 in pixels (exact) where the status is 0, elsewhere the quiet NaN with bits 0x7FC00000 on both
+ * components — the front end drops such a vector by failing comparisons, and vido_mask_propagate defines a NaN source as not voting; stats_out [4] = the count of each
+ * status (zeroed by the call).  Bounds: |f|, |tap| < 2^19, |s| < 2^35, |b| < 2^19, |r| < 2^20; 1024 |r|^2 < 2^51, alpha_q10 (|f|^2 + |b|^2) < 2^50, 1024 beta_q16 <= 2^40:
+ * every term stays below 2^52.  Any output may be NULL, not all.  on_device != 0: every pointer is a device pointer (the fields and flow_marked_out 8-byte aligned,
+ * stats_out 4-byte) and the call only enqueues on the ctx stream (vido_set_stream's when one is set): a memset of the counters and one launch, no host synchronisation,
+ * so it can sit inside a stream capture.  Otherwise the arrays are the caller's host arrays, staged through pinned buffers that grow on demand, and the call returns when
+ * the results are there.  A result depends on nothing but the two fields and the two parameters. */
+int vido_flow_consistency(vido_ctx* ctx, const int32_t* fwd_q8, const int32_t* bwd_q8, int H, int W, int alpha_q10, int beta_q16,
+                          uint8_t* status_out /* [H*W], NULL ok */, float* flow_marked_out /* [H*W*2], NULL ok */, int32_t* stats_out /* [4], NULL ok */, int on_device);
+
+/* vido_dis_flow in both directions from one ingest and one pyramid build, and vido_flow_consistency of the two fields.  Arguments and their limits as in those two calls.
+ * All bit for bit: fwd_q8_out = vido_dis_flow(img0, img1)'s q8, bwd_q8_out = vido_dis_flow(img1, img0)'s q8, stats_out[0..3] and [4..7] = those two calls' stats,
+ * and flow_out (the MARKED flow), status_out and stats_out[8..11] = vido_flow_consistency(fwd, bwd, alpha_q10, beta_q16)'s outputs.  Any output may be NULL, not all.
+ * At every level both directions run in one k_dis_patch and one k_dis_densify launch (the direction is a grid dimension), so the call has vido_dis_flow's launches plus
+ * the check's.  on_device != 0: device pointers (flow_out and the q8 outputs 8-byte aligned, stats_out 4-byte), the call only enqueues on the ctx stream — except the
+ * first call of a size, which grows the scratch it shares with vido_dis_flow (the second direction's per-level fields and patch flows, and both level-0 fields). */
+int vido_dis_flow_pair(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int channels, int rgb_order, int stride, int width, int height,
+                       int coarsest, int iters, int max_shift_q8, int min_eig, int alpha_q10, int beta_q16,
+                       float* flow_out /* [h*w*2] marked, NULL ok */, int32_t* fwd_q8_out /* [h*w*2], NULL ok */, int32_t* bwd_q8_out /* [h*w*2], NULL ok */,
+                       uint8_t* status_out /* [h*w], NULL ok */, int32_t* stats_out /* [12]: forward 4, backward 4, check 4; NULL ok */, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device

@@ -4,6 +4,8 @@
 // Launches of one call, all on one stream, no host synchronisation in the device form: a 16-byte memset of the counters, k_dis_ingest (grey + level 0 of both images),
 // k_dis_down per level above 0 (both images), and per level from the coarsest down k_dis_patch then k_dis_densify — separate launches because a level's densification needs
 // every patch of the level and no workgroup may wait for another.  Results depend on no execution order: integer sums only, the counters included.
+// vido_dis_flow_pair: both directions (image 0 -> 1 and 1 -> 0) from one ingest and one pyramid build — the pyramids are symmetric in the two images — with the direction as a
+// grid dimension of k_dis_patch (blockIdx.y) and k_dis_densify (blockIdx.z), so the same number of launches as one direction, and flowcheck.hip's k_flow_check behind them.
 #include "common.hpp"
 
 constexpr int DF_MAX_LEVELS = 7;                                   // coarsest in 0..6
@@ -13,31 +15,34 @@ constexpr int DF_WIN = 9 + 2 * DF_MAX_C;                           // rows and c
 constexpr int DF_STRIDE = 28;                                      // bytes per staged row
 
 struct DisFlowState {
-    // scratch of one (w, h, coarsest): the two pyramids (tight rows, image 1 at +pyr_bytes), the dense fields of the levels above 0 and the patch flows of one level
+    // scratch of one (w, h, coarsest): the two pyramids (tight rows, image 1 at +pyr_bytes), the dense fields of the levels above 0 and the patch flows of one level;
+    // the pair call: the last two per direction, and both level-0 fields (the check reads them whether or not the caller asks for them)
     uint8_t* d_scratch = nullptr; size_t scratch_cap = 0;
-    int32_t* d_stats = nullptr;                                    // the counters of a call without a caller's stats buffer, and of the host form
-    // host form: device + pinned staging [img0 | img1 | flow | q8 | stats]
+    int32_t* d_stats = nullptr;                                    // the counters (12 words) of a call without a caller's stats buffer
+    // host form: device + pinned staging [img0 | img1 | flow | q8 | stats], the pair call [img0 | img1 | flow | fwd | bwd | stats | status]
     uint8_t *d_io = nullptr, *h_io = nullptr; size_t io_cap = 0;
 };
 
 struct DisGeom {
     int L, w[DF_MAX_LEVELS], h[DF_MAX_LEVELS], nx[DF_MAX_LEVELS], ny[DF_MAX_LEVELS];
-    size_t pyr_off[DF_MAX_LEVELS], pyr_bytes, u_off[DF_MAX_LEVELS], up_off, total;
+    size_t pyr_off[DF_MAX_LEVELS], pyr_bytes, u_off[2][DF_MAX_LEVELS], up_off[2], q8_off[2], total;      // [direction]
 };
 
 static int df_origins(int n) { return ((n - 8) >> 2) + 1 + (((n - 8) & 3) != 0); }
 
-static DisGeom df_geom(int w, int h, int L)
+// ndir = 1: vido_dis_flow's layout; 2: the pair call's — the same groups in the same order, each once per direction, then both level-0 fields.  Every offset is a multiple of 8
+static DisGeom df_geom(int w, int h, int L, int ndir)
 {
-    DisGeom G; G.L = L; size_t o = 0;
+    DisGeom G{}; G.L = L; size_t o = 0;
     for (int l = 0; l <= L; l++) {
         G.w[l] = w >> l; G.h[l] = h >> l; G.nx[l] = df_origins(G.w[l]); G.ny[l] = df_origins(G.h[l]);
         G.pyr_off[l] = o; o += ((size_t)G.w[l] * G.h[l] + 15) & ~(size_t)15;
     }
     G.pyr_bytes = o; o *= 2;
-    G.u_off[0] = 0;                                                 // (level 0's field is the caller's q8)
-    for (int l = 1; l <= L; l++) { G.u_off[l] = o; o += (size_t)G.w[l] * G.h[l] * 8; }
-    G.up_off = o; o += (size_t)G.nx[0] * G.ny[0] * 8;
+    for (int d = 0; d < ndir; d++)                                  // (level 0's field is the caller's q8, or q8_off)
+        for (int l = 1; l <= L; l++) { G.u_off[d][l] = o; o += (size_t)G.w[l] * G.h[l] * 8; }
+    for (int d = 0; d < ndir; d++) { G.up_off[d] = o; o += (size_t)G.nx[0] * G.ny[0] * 8; }
+    if (ndir == 2) for (int d = 0; d < 2; d++) { G.q8_off[d] = o; o += (size_t)w * h * 8; }
     G.total = o;
     return G;
 }
@@ -116,12 +121,18 @@ __device__ __forceinline__ void df_eval(const uint8_t* win, int X0, int Y0, int 
 // One wave per patch, four patches per workgroup, lane = pixel.  The wave stages rows and columns (u0 >> 8) - C .. (u0 >> 8) + 8 + C around the patch of image 1 into its own
 // LDS slice with the definition's clamping applied (a clamped coordinate reads the border pixel twice, which is the clamped sample), keeps its pixel's T, gx, gy in registers,
 // the sums are wave reductions that leave the total in every lane, and lane 0 alone divides; the step it finds is broadcast, so the loop is wave-uniform.  up[p] = the
-// patch's flow.  The four counters take one atomic add per counter and workgroup; no workgroup waits for another.
-__global__ __launch_bounds__(256) void k_dis_patch(const uint8_t* __restrict__ G0, const uint8_t* __restrict__ G1, int w, int h, const int* __restrict__ Uc /* null at the coarsest level */,
-                                                   int w1, int h1, int nx, int ny, int iters, int max_shift, long long min_eig, int* __restrict__ up, int* __restrict__ stats)
+// patch's flow.  The four counters take one atomic add per counter and workgroup; no workgroup waits for another.  blockIdx.y = the direction: 0 aligns Ga's patches to Gb
+// with (Uc0, up0, stats), 1 Gb's patches to Ga with (Uc1, up1, stats + 4); the choice is wave-uniform, scalar registers only.  A one-direction launch has gridDim.y = 1.
+__global__ __launch_bounds__(256) void k_dis_patch(const uint8_t* __restrict__ Ga, const uint8_t* __restrict__ Gb, int w, int h, const int* __restrict__ Uc0 /* null at the coarsest level */,
+                                                   const int* __restrict__ Uc1, int w1, int h1, int nx, int ny, int iters, int max_shift, long long min_eig, int* __restrict__ up0,
+                                                   int* __restrict__ up1, int* __restrict__ stats)
 {
     __shared__ uint8_t s_win[4][DF_WIN * DF_STRIDE];
     __shared__ int s_status[4], s_steps[4];
+    const int dir = blockIdx.y;
+    const uint8_t* __restrict__ G0 = dir ? Gb : Ga; const uint8_t* __restrict__ G1 = dir ? Ga : Gb;
+    const int* __restrict__ Uc = dir ? Uc1 : Uc0; int* __restrict__ up = dir ? up1 : up0;
+    stats += 4 * dir;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, p = blockIdx.x * 4 + wv;
     int status = 99, steps = 0;                                            // a wave past the last patch counts nowhere
     if (p < nx * ny) {                                                     // (wave-uniform, like every branch below that is not marked per lane)
@@ -185,12 +196,16 @@ __device__ __forceinline__ int df_sample(const uint8_t* __restrict__ G, int w, i
 
 // One thread per pixel: the photometric-weighted mean of the flows of the 1..9 patches that hold it.  Along an axis the candidates are the regular origins 4 (x >> 2) - 4 and
 // 4 (x >> 2) where they exist, and the edge-aligned origin n - 8 (index nreg, when n - 8 is no multiple of 4) from x = n - 8 on.  U (null at level 0 without a q8 output)
-// takes the Q8 field, flow (level 0 only) the same in pixels.
-__global__ __launch_bounds__(256) void k_dis_densify(const uint8_t* __restrict__ G0, const uint8_t* __restrict__ G1, int w, int h, const int* __restrict__ up, int nx, int ny,
-                                                     int* __restrict__ U, float* __restrict__ flow)
+// takes the Q8 field, flow (level 0 only, direction 0 only) the same in pixels.  blockIdx.z = the direction, as in k_dis_patch: 1 densifies up1 into U1 with the images swapped.
+__global__ __launch_bounds__(256) void k_dis_densify(const uint8_t* __restrict__ Ga, const uint8_t* __restrict__ Gb, int w, int h, const int* __restrict__ up0, const int* __restrict__ up1,
+                                                     int nx, int ny, int* __restrict__ U0, int* __restrict__ U1, float* __restrict__ flow)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
+    const int dir = blockIdx.z;
+    const uint8_t* __restrict__ G0 = dir ? Gb : Ga; const uint8_t* __restrict__ G1 = dir ? Ga : Gb;
+    const int* __restrict__ up = dir ? up1 : up0; int* __restrict__ U = dir ? U1 : U0;
+    if (dir) flow = nullptr;
     const int nrx = ((w - 8) >> 2) + 1, nry = ((h - 8) >> 2) + 1;
     int cx[3], cy[3];
     cx[0] = (x >> 2) - 1; cx[1] = x >> 2; cx[2] = (nx > nrx && x >= w - 8) ? nrx : -1;
@@ -230,28 +245,28 @@ void disflow_state_destroy(vido_ctx* ctx)
     delete S; ctx->disflow = nullptr;
 }
 
-extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int channels, int rgb_order, int stride, int width, int height, int coarsest, int iters,
-                             int max_shift_q8, int min_eig, float* flow_out, int32_t* q8_out, int32_t* stats, int on_device)
+// the argument rules vido_dis_flow and vido_dis_flow_pair share; 0 = fine
+static int df_check_args(vido_ctx* ctx, const char* who, const uint8_t* img0, const uint8_t* img1, int channels, int stride, int width, int height, int coarsest, int iters, int max_shift_q8, int min_eig)
 {
-    if (!ctx) return VIDO_E_INVALID;
-    if (!img0 || !img1) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: null image");
-    if (width < 16 || height < 16 || width > 4095 || height > 4095) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: size %d x %d outside 16 .. 4095", width, height);
-    if (channels != 1 && channels != 3 && channels != 4) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: channels must be 1, 3 or 4 (got %d)", channels);
-    if (stride < width * channels) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: stride %d below width * channels = %d", stride, width * channels);
+    if (!img0 || !img1) return vido_set_error(ctx, VIDO_E_INVALID, "%s: null image", who);
+    if (width < 16 || height < 16 || width > 4095 || height > 4095) return vido_set_error(ctx, VIDO_E_INVALID, "%s: size %d x %d outside 16 .. 4095", who, width, height);
+    if (channels != 1 && channels != 3 && channels != 4) return vido_set_error(ctx, VIDO_E_INVALID, "%s: channels must be 1, 3 or 4 (got %d)", who, channels);
+    if (stride < width * channels) return vido_set_error(ctx, VIDO_E_INVALID, "%s: stride %d below width * channels = %d", who, stride, width * channels);
     if (coarsest < 0 || coarsest >= DF_MAX_LEVELS || (std::min(width, height) >> coarsest) < 8)
-        return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: coarsest %d outside 0 .. %d, or min(w, h) >> coarsest below 8", coarsest, DF_MAX_LEVELS - 1);
-    if (iters < 1 || iters > DF_MAX_ITERS) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: iters %d outside 1 .. %d", iters, DF_MAX_ITERS);
-    if (max_shift_q8 < 0 || max_shift_q8 > DF_MAX_SHIFT_Q8) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: max_shift_q8 %d outside 0 .. %d", max_shift_q8, DF_MAX_SHIFT_Q8);
-    if (min_eig < 0) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: min_eig %d is negative", min_eig);
-    if (!flow_out && !q8_out && !stats) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: no output asked for");
-    if (on_device && ((((uintptr_t)flow_out | (uintptr_t)q8_out | (uintptr_t)stats) & 3) != 0)) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: device outputs must be 4-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return vido_set_error(ctx, VIDO_E_INVALID, "%s: coarsest %d outside 0 .. %d, or min(w, h) >> coarsest below 8", who, coarsest, DF_MAX_LEVELS - 1);
+    if (iters < 1 || iters > DF_MAX_ITERS) return vido_set_error(ctx, VIDO_E_INVALID, "%s: iters %d outside 1 .. %d", who, iters, DF_MAX_ITERS);
+    if (max_shift_q8 < 0 || max_shift_q8 > DF_MAX_SHIFT_Q8) return vido_set_error(ctx, VIDO_E_INVALID, "%s: max_shift_q8 %d outside 0 .. %d", who, max_shift_q8, DF_MAX_SHIFT_Q8);
+    if (min_eig < 0) return vido_set_error(ctx, VIDO_E_INVALID, "%s: min_eig %d is negative", who, min_eig);
+    return VIDO_OK;
+}
+
+// the state, the counters and a scratch of G.total bytes; the first call of a size waits for earlier calls, which may still read the old scratch
+static int df_prepare(vido_ctx* ctx, hipStream_t st, const DisGeom& G)
+{
     if (!ctx->disflow) ctx->disflow = new DisFlowState();
     DisFlowState* S = ctx->disflow;
-    hipStream_t st = on_device && ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    const DisGeom G = df_geom(width, height, coarsest);
-    if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 16));
-    if (G.total > S->scratch_cap) {                                        // the first call of a size: earlier calls may still read the old scratch
+    if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 48));
+    if (G.total > S->scratch_cap) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
         if (st != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (S->d_scratch) { HIP_TRY(ctx, hipFree(S->d_scratch)); S->d_scratch = nullptr; }
@@ -259,25 +274,31 @@ extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* 
         HIP_TRY(ctx, hipMalloc((void**)&S->d_scratch, G.total));
         S->scratch_cap = G.total;
     }
-    const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
-    const size_t o_img1 = (img_bytes + 15) & ~(size_t)15, o_flow = 2 * o_img1, o_q8 = o_flow + px * 8, o_stats = o_q8 + px * 8, io_total = o_stats + 16;
-    const uint8_t *d_img0 = img0, *d_img1 = img1; float* d_flow = flow_out; int32_t *d_q8 = q8_out, *d_stats = stats ? stats : S->d_stats;
-    if (!on_device) {
-        if (io_total > S->io_cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
-            if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
-            S->io_cap = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
-            S->io_cap = io_total;
-        }
-        memcpy(S->h_io, img0, img_bytes); memcpy(S->h_io + o_img1, img1, img_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_img1 + img_bytes, hipMemcpyHostToDevice, st));
-        d_img0 = S->d_io; d_img1 = S->d_io + o_img1;
-        d_flow = flow_out ? (float*)(S->d_io + o_flow) : nullptr; d_q8 = q8_out ? (int32_t*)(S->d_io + o_q8) : nullptr; d_stats = (int32_t*)(S->d_io + o_stats);
+    return VIDO_OK;
+}
+
+// the host form's staging of io_total bytes
+static int df_staging(vido_ctx* ctx, hipStream_t st, size_t io_total)
+{
+    DisFlowState* S = ctx->disflow;
+    if (io_total > S->io_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
+        if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
+        S->io_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
+        S->io_cap = io_total;
     }
+    return VIDO_OK;
+}
+
+// The launches of one call on device pointers: the counters' memset (16 bytes per direction), ingest, the pyramid, and per level k_dis_patch and k_dis_densify over ndir
+// directions.  q8[d] = direction d's level-0 field (null: not kept; the pair call always gives both), flow = direction 0's in pixels or null.
+static hipError_t df_enqueue(DisFlowState* S, hipStream_t st, const DisGeom& G, int ndir, const uint8_t* d_img0, const uint8_t* d_img1, int channels, int rgb_order, int stride, int width, int height,
+                       int coarsest, int iters, int max_shift_q8, int min_eig, float* d_flow, int32_t* const q8[2], int32_t* d_stats)
+{
     uint8_t* pyr = S->d_scratch;
-    HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 16, st));
+    if (hipError_t e = hipMemsetAsync(d_stats, 0, 16 * ndir, st)) return e;
     const dim3 blk(256);
     auto grid = [](int w, int h, int z) { return dim3((w + 63) / 64, (h + 3) / 4, z); };
     if (channels == 1)      hipLaunchKernelGGL(k_dis_ingest<1>, grid(width, height, 2), blk, 0, st, d_img0, d_img1, stride, width, height, rgb_order != 0, pyr, G.pyr_bytes);
@@ -285,15 +306,45 @@ extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* 
     else                    hipLaunchKernelGGL(k_dis_ingest<4>, grid(width, height, 2), blk, 0, st, d_img0, d_img1, stride, width, height, rgb_order != 0, pyr, G.pyr_bytes);
     for (int l = 1; l <= coarsest; l++)
         hipLaunchKernelGGL(k_dis_down, grid(G.w[l], G.h[l], 2), blk, 0, st, pyr, G.pyr_bytes, G.pyr_off[l - 1], G.w[l - 1], G.pyr_off[l], G.w[l], G.h[l]);
-    int* up = (int*)(S->d_scratch + G.up_off);
+    int* up[2] = {(int*)(S->d_scratch + G.up_off[0]), ndir == 2 ? (int*)(S->d_scratch + G.up_off[1]) : nullptr};
     for (int l = coarsest; l >= 0; l--) {
         const uint8_t *g0 = pyr + G.pyr_off[l], *g1 = pyr + G.pyr_bytes + G.pyr_off[l];
-        const int* Uc = l < coarsest ? (const int*)(S->d_scratch + G.u_off[l + 1]) : nullptr;
+        const int *Uc[2] = {nullptr, nullptr}; int* U[2] = {nullptr, nullptr};
+        for (int d = 0; d < ndir; d++) {
+            if (l < coarsest) Uc[d] = (const int*)(S->d_scratch + G.u_off[d][l + 1]);
+            U[d] = l > 0 ? (int*)(S->d_scratch + G.u_off[d][l]) : q8[d];
+        }
         const int w1 = l < coarsest ? G.w[l + 1] : 0, h1 = l < coarsest ? G.h[l + 1] : 0, np = G.nx[l] * G.ny[l];
-        hipLaunchKernelGGL(k_dis_patch, dim3((np + 3) / 4), blk, 0, st, g0, g1, G.w[l], G.h[l], Uc, w1, h1, G.nx[l], G.ny[l], iters, max_shift_q8, (long long)min_eig, up, d_stats);
-        int* U = l > 0 ? (int*)(S->d_scratch + G.u_off[l]) : d_q8;
-        hipLaunchKernelGGL(k_dis_densify, grid(G.w[l], G.h[l], 1), blk, 0, st, g0, g1, G.w[l], G.h[l], (const int*)up, G.nx[l], G.ny[l], U, l == 0 ? d_flow : nullptr);
+        hipLaunchKernelGGL(k_dis_patch, dim3((np + 3) / 4, ndir), blk, 0, st, g0, g1, G.w[l], G.h[l], Uc[0], Uc[1], w1, h1, G.nx[l], G.ny[l], iters, max_shift_q8, (long long)min_eig, up[0], up[1], d_stats);
+        hipLaunchKernelGGL(k_dis_densify, grid(G.w[l], G.h[l], ndir), blk, 0, st, g0, g1, G.w[l], G.h[l], (const int*)up[0], (const int*)up[1], G.nx[l], G.ny[l], U[0], U[1], l == 0 ? d_flow : nullptr);
     }
+    return hipSuccess;
+}
+
+extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int channels, int rgb_order, int stride, int width, int height, int coarsest, int iters,
+                             int max_shift_q8, int min_eig, float* flow_out, int32_t* q8_out, int32_t* stats, int on_device)
+{
+    if (!ctx) return VIDO_E_INVALID;
+    if (int rc = df_check_args(ctx, "dis_flow", img0, img1, channels, stride, width, height, coarsest, iters, max_shift_q8, min_eig)) return rc;
+    if (!flow_out && !q8_out && !stats) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: no output asked for");
+    if (on_device && ((((uintptr_t)flow_out | (uintptr_t)q8_out | (uintptr_t)stats) & 3) != 0)) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow: device outputs must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = on_device && ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
+    const DisGeom G = df_geom(width, height, coarsest, 1);
+    if (int rc = df_prepare(ctx, st, G)) return rc;
+    DisFlowState* S = ctx->disflow;
+    const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
+    const size_t o_img1 = (img_bytes + 15) & ~(size_t)15, o_flow = 2 * o_img1, o_q8 = o_flow + px * 8, o_stats = o_q8 + px * 8, io_total = o_stats + 16;
+    const uint8_t *d_img0 = img0, *d_img1 = img1; float* d_flow = flow_out; int32_t *d_q8 = q8_out, *d_stats = stats ? stats : S->d_stats;
+    if (!on_device) {
+        if (int rc = df_staging(ctx, st, io_total)) return rc;
+        memcpy(S->h_io, img0, img_bytes); memcpy(S->h_io + o_img1, img1, img_bytes);
+        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_img1 + img_bytes, hipMemcpyHostToDevice, st));
+        d_img0 = S->d_io; d_img1 = S->d_io + o_img1;
+        d_flow = flow_out ? (float*)(S->d_io + o_flow) : nullptr; d_q8 = q8_out ? (int32_t*)(S->d_io + o_q8) : nullptr; d_stats = (int32_t*)(S->d_io + o_stats);
+    }
+    int32_t* const q8[2] = {d_q8, nullptr};
+    HIP_TRY(ctx, df_enqueue(S, st, G, 1, d_img0, d_img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, d_flow, q8, d_stats));
     HIP_TRY(ctx, hipGetLastError());
     if (!on_device) {
         if (flow_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_flow, S->d_io + o_flow, px * 8, hipMemcpyDeviceToHost, st));
@@ -303,6 +354,46 @@ extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* 
         if (flow_out) memcpy(flow_out, S->h_io + o_flow, px * 8);
         if (q8_out) memcpy(q8_out, S->h_io + o_q8, px * 8);
         if (stats) memcpy(stats, S->h_io + o_stats, 16);
+    }
+    return VIDO_OK;
+}
+
+extern "C" int vido_dis_flow_pair(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int channels, int rgb_order, int stride, int width, int height, int coarsest, int iters,
+                                  int max_shift_q8, int min_eig, int alpha_q10, int beta_q16, float* flow_out, int32_t* fwd_q8_out, int32_t* bwd_q8_out, uint8_t* status_out,
+                                  int32_t* stats_out, int on_device)
+{
+    if (!ctx) return VIDO_E_INVALID;
+    if (int rc = df_check_args(ctx, "dis_flow_pair", img0, img1, channels, stride, width, height, coarsest, iters, max_shift_q8, min_eig)) return rc;
+    if (int rc = flowcheck_params(ctx, "dis_flow_pair", alpha_q10, beta_q16)) return rc;
+    if (!flow_out && !fwd_q8_out && !bwd_q8_out && !status_out && !stats_out) return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow_pair: no output asked for");
+    if (on_device && ((((uintptr_t)flow_out | (uintptr_t)fwd_q8_out | (uintptr_t)bwd_q8_out) & 7) != 0 || ((uintptr_t)stats_out & 3) != 0))
+        return vido_set_error(ctx, VIDO_E_INVALID, "dis_flow_pair: device flow and q8 outputs must be 8-byte aligned, stats 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = on_device && ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
+    const DisGeom G = df_geom(width, height, coarsest, 2);
+    if (int rc = df_prepare(ctx, st, G)) return rc;
+    DisFlowState* S = ctx->disflow;
+    const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
+    const size_t o_img1 = (img_bytes + 15) & ~(size_t)15, o_flow = 2 * o_img1, o_fwd = o_flow + px * 8, o_bwd = o_fwd + px * 8, o_stats = o_bwd + px * 8, o_status = o_stats + 48, io_total = o_status + px;
+    const uint8_t *d_img0 = img0, *d_img1 = img1; float* d_flow = flow_out; uint8_t* d_status = status_out;
+    int32_t* q8[2] = {fwd_q8_out ? fwd_q8_out : (int32_t*)(S->d_scratch + G.q8_off[0]), bwd_q8_out ? bwd_q8_out : (int32_t*)(S->d_scratch + G.q8_off[1])};
+    int32_t* d_stats = stats_out ? stats_out : S->d_stats;
+    if (!on_device) {
+        if (int rc = df_staging(ctx, st, io_total)) return rc;
+        memcpy(S->h_io, img0, img_bytes); memcpy(S->h_io + o_img1, img1, img_bytes);
+        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_img1 + img_bytes, hipMemcpyHostToDevice, st));
+        d_img0 = S->d_io; d_img1 = S->d_io + o_img1;
+        d_flow = flow_out ? (float*)(S->d_io + o_flow) : nullptr; d_status = status_out ? S->d_io + o_status : nullptr;
+        q8[0] = (int32_t*)(S->d_io + o_fwd); q8[1] = (int32_t*)(S->d_io + o_bwd); d_stats = (int32_t*)(S->d_io + o_stats);
+    }
+    HIP_TRY(ctx, df_enqueue(S, st, G, 2, d_img0, d_img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, nullptr, q8, d_stats));
+    HIP_TRY(ctx, flowcheck_enqueue(st, q8[0], q8[1], height, width, alpha_q10, beta_q16, d_status, d_flow, d_stats + 8));
+    HIP_TRY(ctx, hipGetLastError());
+    if (!on_device) {
+        const struct { void* dst; size_t off, n; } back[5] = {{flow_out, o_flow, px * 8}, {fwd_q8_out, o_fwd, px * 8}, {bwd_q8_out, o_bwd, px * 8}, {stats_out, o_stats, 48}, {status_out, o_status, px}};
+        for (const auto& b : back) if (b.dst) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + b.off, S->d_io + b.off, b.n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (const auto& b : back) if (b.dst) memcpy(b.dst, S->h_io + b.off, b.n);
     }
     return VIDO_OK;
 }

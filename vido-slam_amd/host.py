@@ -71,6 +71,8 @@ def load_library():
     lib.vido_orb_patch_refine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.vido_dis_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_flow_consistency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.vido_dis_flow_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p] * 5 + [C.c_int]
     lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -80,6 +82,10 @@ def load_library():
     _lib = lib
     return lib
 
+
+# defaults of vido_flow_consistency: alpha = 10 / 1024 ~ 0.01, beta = 32768 / 65536 = 0.5 px^2 (tools/measure_flow_consistency.py, profiles/r21/flow_consistency_cpu.txt)
+FLOW_ALPHA_Q10 = 10
+FLOW_BETA_Q16 = 32768
 
 # defaults of vido_orb_patch_points' verdict = the tracker's Verify.PatchMinStd 6 / Verify.PatchMinZncc 920 / 1024 (profiles/r16/patch_verify.txt)
 PATCH_MIN_VAR = 64 * 64 * 6 * 6
@@ -309,6 +315,48 @@ class Context:
         vp = lambda p: C.c_void_p(p) if p else None
         self._check(self.lib.vido_dis_flow(self.h, vp(img0_ptr), vp(img1_ptr), int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
                                            int(max_shift_q8), int(min_eig), vp(flow_ptr), vp(q8_ptr), vp(stats_ptr), 1))
+
+    def flow_consistency(self, fwd_q8, bwd_q8, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16):
+        """Forward-backward check of two flow fields (vido_flow_consistency; the statement is tests/refimpl/flow_consistency_np.py): fwd_q8, bwd_q8 (H,W,2) i32 host arrays in
+        1/256 px, image 0 -> 1 and image 1 -> 0 (dis_flow's q8).  A pixel is inconsistent when 1024 |f + b|^2 > alpha_q10 (|f|^2 + |b|^2) + 1024 beta_q16, b the backward
+        flow sampled at the pixel's target.  Returns (status (H,W) u8: 0 consistent, 1 inconsistent, 2 the target leaves the image, 3 not a flow; flow_marked (H,W,2) f32 =
+        fwd / 256 where the status is 0, NaN elsewhere; stats (4,) i32 = the count of each status)."""
+        fwd_q8, bwd_q8 = np.ascontiguousarray(fwd_q8), np.ascontiguousarray(bwd_q8)
+        if fwd_q8.dtype != np.int32 or bwd_q8.dtype != np.int32 or fwd_q8.ndim != 3 or fwd_q8.shape[2] != 2 or fwd_q8.shape != bwd_q8.shape:
+            raise VidoError(-1, "flow_consistency: two i32 fields of one shape H x W x 2 expected")
+        h, w = fwd_q8.shape[:2]
+        status = np.empty((h, w), np.uint8); marked = np.empty((h, w, 2), np.float32); stats = np.empty(4, np.int32)
+        self._check(self.lib.vido_flow_consistency(self.h, _ptr(fwd_q8), _ptr(bwd_q8), h, w, int(alpha_q10), int(beta_q16), _ptr(status), _ptr(marked), _ptr(stats), 0))
+        return status, marked, stats
+
+    def flow_consistency_device(self, fwd_ptr, bwd_ptr, height, width, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16, status_ptr=None, marked_ptr=None, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream; any output pointer may be None, not all."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_flow_consistency(self.h, vp(fwd_ptr), vp(bwd_ptr), int(height), int(width), int(alpha_q10), int(beta_q16), vp(status_ptr), vp(marked_ptr), vp(stats_ptr), 1))
+
+    def dis_flow_pair(self, img0, img1, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16):
+        """dis_flow in both directions from one pyramid build, and flow_consistency of the two fields (vido_dis_flow_pair): images and flow parameters as for dis_flow, the
+        check's as for flow_consistency.  Returns (flow_marked (H,W,2) f32, fwd_q8 (H,W,2) i32 = dis_flow(img0, img1)'s q8, bwd_q8 = dis_flow(img1, img0)'s q8, status
+        (H,W) u8, stats (12,) i32 = the forward call's four counters, the backward call's, the check's), each bit-equal to the separate calls."""
+        img0, img1 = np.asarray(img0), np.asarray(img1)
+        if img0.dtype != np.uint8 or img1.dtype != np.uint8 or img0.shape != img1.shape or img0.ndim not in (2, 3):
+            raise VidoError(-1, "dis_flow_pair: two u8 images of one shape, H x W or H x W x C, expected")
+        cn = 1 if img0.ndim == 2 else img0.shape[2]
+        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
+        if not rows(img0) or not rows(img1) or img0.strides[0] != img1.strides[0]:
+            img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
+        h, w = img0.shape[:2]
+        flow = np.empty((h, w, 2), np.float32); fwd = np.empty((h, w, 2), np.int32); bwd = np.empty((h, w, 2), np.int32); status = np.empty((h, w), np.uint8); stats = np.empty(12, np.int32)
+        self._check(self.lib.vido_dis_flow_pair(self.h, C.c_void_p(img0.ctypes.data), C.c_void_p(img1.ctypes.data), cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+                                                int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), _ptr(flow), _ptr(fwd), _ptr(bwd), _ptr(status), _ptr(stats), 0))
+        return flow, fwd, bwd, status, stats
+
+    def dis_flow_pair_device(self, img0_ptr, img1_ptr, channels, stride, width, height, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, alpha_q10=FLOW_ALPHA_Q10,
+                             beta_q16=FLOW_BETA_Q16, flow_ptr=None, fwd_ptr=None, bwd_ptr=None, status_ptr=None, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the context's scratch); any output pointer may be None, not all."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self.lib.vido_dis_flow_pair(self.h, vp(img0_ptr), vp(img1_ptr), int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
+                                                int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), vp(flow_ptr), vp(fwd_ptr), vp(bwd_ptr), vp(status_ptr), vp(stats_ptr), 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

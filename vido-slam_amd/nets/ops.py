@@ -758,6 +758,88 @@ class HipOps:
                                                    C.c_void_p(stats.data_ptr()) if stats is not None else None, 1))
         return out
 
+    def flow_consistency(self, fwd_q8, bwd_q8, status=None, out=None, stats=None, alpha_q10=None, beta_q16=None):
+        """vido_flow_consistency on device tensors: fwd_q8, bwd_q8 int32 [H,W,2] in 1/256 px (dis_flow's q8 of the pair in either order) -> the marked flow, float32 [H,W,2]
+        (`out`, or a new tensor): fwd / 256 where the backward flow at the target brings the pixel back (1024 |f + b|^2 <= alpha_q10 (|f|^2 + |b|^2) + 1024 beta_q16), NaN
+        elsewhere.  status: a uint8 [H,W] tensor that receives 0 consistent / 1 inconsistent / 2 leaves the image / 3 not a flow, or None; stats: an int32 tensor of >= 4
+        elements that receives the four counts, or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/flow_consistency_np.py.  Enqueued on torch's
+        current stream, nothing is waited for.  CPU tensors, other dtypes or shapes and non-contiguous tensors raise."""
+        from ..host import VidoError, FLOW_ALPHA_Q10, FLOW_BETA_Q16
+        def bad(why):
+            raise VidoError(-1, "flow_consistency: " + why)
+        for name, t, dt in (("fwd_q8", fwd_q8, torch.int32), ("bwd_q8", bwd_q8, torch.int32), ("status", status, torch.uint8), ("out", out, torch.float32), ("stats", stats, torch.int32)):
+            if t is None and name not in ("fwd_q8", "bwd_q8"):
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != fwd_q8.device:
+                bad("%s is on another device than fwd_q8" % name)
+        if fwd_q8.dim() != 3 or fwd_q8.shape[2] != 2:
+            bad("fwd_q8 must be [H, W, 2], got %s" % (tuple(fwd_q8.shape),))
+        if tuple(bwd_q8.shape) != tuple(fwd_q8.shape):
+            bad("bwd_q8 must have fwd_q8's shape %s, got %s" % (tuple(fwd_q8.shape), tuple(bwd_q8.shape)))
+        H, W = int(fwd_q8.shape[0]), int(fwd_q8.shape[1])
+        if out is None:
+            out = torch.empty((H, W, 2), device=fwd_q8.device, dtype=torch.float32)
+        elif tuple(out.shape) != (H, W, 2):
+            bad("out must be [%d, %d, 2], got %s" % (H, W, tuple(out.shape)))
+        if status is not None and tuple(status.shape) != (H, W):
+            bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        self._adopt_stream()
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.ctx._check(self.ctx.lib.vido_flow_consistency(self.ctx.h, vp(fwd_q8), vp(bwd_q8), H, W, int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10),
+                                                           int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), vp(status), vp(out), vp(stats), 1))
+        return out
+
+    def dis_flow_pair(self, prev, cur, out=None, fwd_q8=None, bwd_q8=None, status=None, stats=None, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0,
+                      alpha_q10=None, beta_q16=None):
+        """vido_dis_flow_pair on device tensors: prev, cur as for dis_flow -> the MARKED flow from prev into cur, float32 [H,W,2] (`out`, or a new tensor): dis_flow(prev, cur)
+        where flow_consistency of it and dis_flow(cur, prev) gives status 0, NaN elsewhere; both directions come from one pyramid build.  fwd_q8 / bwd_q8: int32 [H,W,2]
+        tensors that receive the two fields in 1/256 px, or None; status: uint8 [H,W] or None; stats: int32 of >= 12 elements (the forward call's four counters, the
+        backward call's, the check's) or None.  Enqueued on torch's current stream, nothing is waited for; the first call of a size grows the context's scratch, so it comes
+        before a graph capture.  The argument checks are dis_flow's."""
+        from ..host import VidoError, FLOW_ALPHA_Q10, FLOW_BETA_Q16
+        def bad(why):
+            raise VidoError(-1, "dis_flow_pair: " + why)
+        for name, t, dt in (("prev", prev, torch.uint8), ("cur", cur, torch.uint8), ("out", out, torch.float32), ("fwd_q8", fwd_q8, torch.int32), ("bwd_q8", bwd_q8, torch.int32),
+                            ("status", status, torch.uint8), ("stats", stats, torch.int32)):
+            if t is None and name not in ("prev", "cur"):
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != prev.device:
+                bad("%s is on another device than prev" % name)
+        if prev.dim() not in (2, 3) or (prev.dim() == 3 and prev.shape[2] not in (3, 4)):
+            bad("prev must be [H, W] or [H, W, 3|4], got %s" % (tuple(prev.shape),))
+        if tuple(cur.shape) != tuple(prev.shape):
+            bad("cur must have prev's shape %s, got %s" % (tuple(prev.shape), tuple(cur.shape)))
+        H, W = int(prev.shape[0]), int(prev.shape[1]); cn = 1 if prev.dim() == 2 else int(prev.shape[2])
+        if out is None:
+            out = torch.empty((H, W, 2), device=prev.device, dtype=torch.float32)
+        for name, t in (("out", out), ("fwd_q8", fwd_q8), ("bwd_q8", bwd_q8)):
+            if t is not None and tuple(t.shape) != (H, W, 2):
+                bad("%s must be [%d, %d, 2], got %s" % (name, H, W, tuple(t.shape)))
+        if status is not None and tuple(status.shape) != (H, W):
+            bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
+        if stats is not None and stats.numel() < 12:
+            bad("stats needs 12 elements")
+        self._adopt_stream()
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.ctx._check(self.ctx.lib.vido_dis_flow_pair(self.ctx.h, vp(prev), vp(cur), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
+                                                        int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10), int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16),
+                                                        vp(out), vp(fwd_q8), vp(bwd_q8), vp(status), vp(stats), 1))
+        return out
+
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
         """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
         (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),

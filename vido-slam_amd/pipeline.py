@@ -224,16 +224,25 @@ class NetNodes:
     flow_source = "dis" (default "net": LiteFlowNet, and nothing below applies): the flow is HipOps.dis_flow of the two BGR frames (csrc/disflow.hip, INTEGRATION.md §39;
     dis_params: a dict of coarsest / iters / max_shift_q8 / min_eig, the op's defaults otherwise) on the flow context and the flow stream, captured into g_flow like
     LiteFlowNet.  LiteFlowNet is not constructed (flow_net is None).  The op is all-integer: the flow half of the range words stays 0 and recompute() leaves the flow alone.
-    detect_every, stable_ids and EndToEnd take the tensor as they take LiteFlowNet's."""
+    detect_every, stable_ids and EndToEnd take the tensor as they take LiteFlowNet's.
+
+    dis_consistency (with flow_source = "dis" only; default None: off, and the flow function is exactly the one above): True, or a dict that may hold alpha_q10 and beta_q16
+    (the op's defaults otherwise: 10 and 32768, i.e. alpha 0.01 and beta 0.5 px^2) — the flow is HipOps.dis_flow_pair's MARKED flow: both directions
+    from one pyramid build, and every vector whose backward flow does not bring it back, or whose target leaves the image, is NaN.  The front end drops a NaN vector by
+    failing comparisons, and vido_mask_propagate defines a NaN source as not voting — which is what an occluded pixel should do: it has no counterpart in the next frame,
+    so it carries no label there.  flow_status: the uint8 HxW status image of the last frame (0 consistent, 1 inconsistent, 2 leaves the image, 3 not a flow), valid in
+    stream order with the flow; None when off.  Anything else raises ValueError before anything is built, and so does dis_consistency with flow_source = "net"."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
-                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None):
+                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
         self.flow_source, self.dis_params = self._check_flow_source(flow_source, dis_params)
+        self.dis_consistency = self._check_dis_consistency(dis_consistency, flow_source)
+        self.flow_status = None
         self._check_stable_ids(stable_ids, stable_hold, label_mode, on_range)
         self.stable_ids = bool(stable_ids); self.stable_hold = int(stable_hold); self._ids = None
         self.detect_every = int(detect_every)
@@ -303,7 +312,10 @@ class NetNodes:
         self.last_counts = None
         self.det_overflows = 0                                        # frames whose detection count exceeded the static head's slots (redone through the dynamic head)
         ex = torch.zeros((height, width, 3), dtype=torch.uint8, device=dev)
-        if self.flow_source == "dis":                                 # the op on the flow context (its first call of the size, below, grows the context's scratch: before any capture)
+        if self.dis_consistency is not None:                          # both directions and the check; the status image is the nodes' own buffer, written by eager calls and replays alike
+            self.flow_status = torch.zeros((height, width), dtype=torch.uint8, device=dev)
+            self._flow_fn = lambda a, b: self.ops_flow.dis_flow_pair(a, b, status=self.flow_status, **self.dis_params, **self.dis_consistency)
+        elif self.flow_source == "dis":                               # the op on the flow context (its first call of the size, below, grows the context's scratch: before any capture)
             self._flow_fn = lambda a, b: self.ops_flow.dis_flow(a, b, **self.dis_params)
         else:
             self._flow_fn = lambda a, b: _nets.analyse_flow(self.flow_net, a, b)
@@ -440,6 +452,23 @@ class NetNodes:
         if dis_params is not None and (flow_source != "dis" or not isinstance(dis_params, dict) or any(k not in cls.DIS_PARAMS for k in dis_params)):
             raise ValueError("dis_params: with flow_source='dis', a dict with keys among %s, not %r" % (cls.DIS_PARAMS, dis_params))
         return flow_source, dict(dis_params or {})
+
+    DIS_CONSISTENCY = ("alpha_q10", "beta_q16")
+
+    @classmethod
+    def _check_dis_consistency(cls, dis_consistency, flow_source):
+        """None (off) or the check's parameters as a dict (empty: the op's defaults)"""
+        import numbers as _numbers
+        if dis_consistency is None:
+            return None
+        ok = dis_consistency is True or (isinstance(dis_consistency, dict) and all(
+            k in cls.DIS_CONSISTENCY and isinstance(v, _numbers.Integral) and not isinstance(v, bool) for k, v in dis_consistency.items()))
+        if flow_source != "dis" or not ok:
+            raise ValueError("dis_consistency: with flow_source='dis', None, True or a dict with integer values under keys among %s, not %r" % (cls.DIS_CONSISTENCY, dis_consistency))
+        cons = {} if dis_consistency is True else {k: int(v) for k, v in dis_consistency.items()}
+        if not 0 <= cons.get("alpha_q10", 0) <= 1024 or not 0 <= cons.get("beta_q16", 0) <= 1 << 30:
+            raise ValueError("dis_consistency: alpha_q10 in 0..1024 and beta_q16 in 0..2^30 expected, not %r" % (dis_consistency,))
+        return cons
 
     @staticmethod
     def _check_detect_every(detect_every, on_range):
