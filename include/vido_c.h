@@ -568,6 +568,8 @@ int vido_conv1x1_layout(int cin, int cout, int hw);
  * Also selected by VIDO_CONV1X1_ARITH = f16x2 | bf16x3 | f32 in the environment.  Returns the previous setting; process-wide — set it before weights are packed (a packed
  * weight carries its layout, a mismatch is refused by the caller's shape check). */
 int vido_conv1x1_set_arith(int arith);
+/* the current setting (0 / 1 / 2) */
+int vido_conv1x1_get_arith(void);
 /* non-zero when a split-fp16 launch on this context (1x1, 3x3, fully connected, 2x2 transposed) met an activation outside fp16's range, an infinity or a NaN since the last
  * reset; read after the stream has been waited for.  reset != 0: read and clear in one atomic exchange. */
 int vido_conv1x1_range_flag(vido_ctx* ctx, int reset);
@@ -661,6 +663,13 @@ int vido_wino3x3_bias_act_form(vido_ctx* ctx, const float* x, const float* u_pac
 int vido_gconv3x3_supported(int H, int W, int cpg_in, int cpg_out);
 int64_t vido_gconv3x3_packed_size(int groups, int cpg_in, int cpg_out);
 int vido_gconv3x3_bias_act(vido_ctx* ctx, const float* x, const float* in_bias, const float* w_packed, const float* bias, float* y, int groups, int cpg_in, int cpg_out, int H, int W, float slope);
+/* The same convolution (no in_bias) with 32 -> 32 or 64 -> 64 channels per group in the split-fp16 arithmetic of vido_conv3x3_h_bias_act (csrc/gconvh.hip): `conv2` of the
+ * ResNeXt bottlenecks of layer3 / layer4.  w_packed (16-byte aligned): two fp16 planes of the output channels scaled by powers of two, plane p of element (co, ci, dy, dx) of
+ * group g at [g][(co % cpg) / 32][ci / 16][3 dy + dx][p][32 ((ci % 16) / 8) + co % 32][ci % 8], then [groups * cpg] floats: the inverse scales
+ * (vido_slam_amd/nets/ops.py::pack_gconv3x3_h).  Activations must be finite and below 65504 in magnitude (vido_conv1x1_range_flag otherwise).
+ * vido_gconv3x3_h_supported: 1 when the kernel takes the shape (cpg_in == cpg_out in {32, 64}, W <= 93 / 45). */
+int vido_gconv3x3_h_supported(int H, int W, int cpg_in, int cpg_out);
+int vido_gconv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int groups, int cpg_in, int cpg_out, int H, int W, float slope);
 /* ... with stride 2 (padding 1): the strided `conv2` of the first bottleneck of a ResNeXt stage (resnet.py:300-372 with STRIDE_IN_1X1 = False).  y [groups * cpg_out][(H + 1) / 2][W / 2];
  * W a multiple of 4, 8 / 16 / a multiple of 32 output channels per group (same w_packed), x 16-byte aligned, no in_bias.  vido_gconv3x3_s2_supported: 1 when the shape has a kernel. */
 int vido_gconv3x3_s2_supported(int H, int W, int cpg_in, int cpg_out);

@@ -589,6 +589,7 @@ static std::atomic<int>& c1_arith()          // 0 = split-fp16 (two planes, thre
 }
 
 int vido_conv1x1_set_arith(int arith) { return c1_arith().exchange(arith == 1 ? 1 : arith == 2 ? 2 : 0); }
+int vido_conv1x1_get_arith(void) { return c1_arith().load(std::memory_order_relaxed); }
 
 /* The range flag of the split-fp16 kernels (1x1, 3x3, fully connected, 2x2 transposed): non-zero when a launch since the last reset met an activation with |x| >= 65504, an
  * infinity or a NaN — its outputs are then not valid.

@@ -16,6 +16,7 @@ _CONV3X3_H_MIN_WGS = 0 if os.environ.get("VIDO_CONV3X3_H") == "0" else int(os.en
 # the dense 3x3 layers: LiteFlowNet on the library's vector-ALU Winograd throughout gives 82 frames/s.
 # Round 6 (detector in split fp16, profiles/r6/convdirect_set_ab.txt): 125.0 frames/s with "novalu" against 124.3 / 124.5 with "all" (the chain without the detector: 191.4 against 193.8).
 _CONVDIRECT_SET = os.environ.get("VIDO_CONVDIRECT_SET", "novalu")
+_GCONV_H = os.environ.get("VIDO_GCONV_H", "1") != "0"      # split-fp16 grouped 3x3 (csrc/gconvh.hip) for 32 / 64 channels per group; 0: the fp32 kernel of csrc/gconv.hip everywhere
 
 
 def correlation_torch_reference(first, second, stride):
@@ -37,7 +38,7 @@ class HipOps:
 
     @property
     def range_safe_active(self):
-        """True inside range_safe(): conv1x1_conv / conv1x1_bias_act callers, the direct 3x3, fc_h_linear and deconv2x2_conv take their fp32 routes."""
+        """True inside range_safe(): conv1x1_conv / conv1x1_bias_act callers, the direct 3x3, the grouped 3x3 (gconv3x3_conv), fc_h_linear and deconv2x2_conv take their fp32 routes."""
         return self._range_safe > 0
 
     @staticmethod
@@ -212,6 +213,33 @@ class HipOps:
                                                             C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
                                                             int(groups), cpg_in, cpg_out, H, W, C.c_float(slope)))
         return out
+
+    def gconv3x3_h_supported(self, H, W, cpg_in, cpg_out):
+        return bool(self.ctx.lib.vido_gconv3x3_h_supported(int(H), int(W), int(cpg_in), int(cpg_out)))
+
+    def gconv3x3_h_bias_act(self, x, w_packed, bias, groups, slope=0.0):
+        """leaky_relu(conv2d(x, w, None, 1, 1, 1, groups) + bias, slope) for one image as one split-fp16 launch (csrc/gconvh.hip: 32 -> 32 or 64 -> 64 channels per group);
+        w_packed = pack_gconv3x3_h(w, groups).  Activations must be finite and below 65504 in magnitude (conv1x1_range_flag otherwise)."""
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == 1
+        _, Cin, H, W = x.shape
+        cpg = Cin // groups
+        assert bias.numel() == Cin and w_packed.dtype == torch.int16 and w_packed.numel() == 2 * Cin * (cpg * 9 + 1), "gconv3x3_h: weight not packed by pack_gconv3x3_h for this layer"
+        out = torch.empty((1, Cin, H, W), device=x.device, dtype=torch.float32)
+        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * Cin * cpg * 9 * H * W
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_gconv3x3_h_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                              int(groups), cpg, cpg, H, W, C.c_float(slope)))
+        return out
+
+    def gconv3x3_conv(self, x, w_packed, w_packed_h, bias, groups, slope=0.0, in_bias=None):
+        """The grouped 3x3 convolution of a ResNeXt bottleneck: the split-fp16 kernel (gconv3x3_h_bias_act, w_packed_h = pack_gconv3x3_h(w, groups) or None) when the operand needs
+        no input bias, the kernel takes the shape, the arithmetic setting is not f32 (conv1x1_set_arith(1) / VIDO_CONV1X1_ARITH=f32), no range_safe scope holds this object and
+        VIDO_GCONV_H is not 0; in every other case gconv3x3_bias_act (fp32 matrix instruction, w_packed = pack_gconv3x3(w, groups))."""
+        cpg = x.shape[1] // groups
+        if (_GCONV_H and w_packed_h is not None and in_bias is None and not self._range_safe and int(self.ctx.lib.vido_conv1x1_get_arith()) != 1
+                and bias.numel() == x.shape[1] and self.gconv3x3_h_supported(x.shape[2], x.shape[3], cpg, cpg)):
+            return self.gconv3x3_h_bias_act(x, w_packed_h, bias, groups, slope)
+        return self.gconv3x3_bias_act(x, w_packed, bias, groups, slope, in_bias=in_bias)
 
     def gconv3x3_s2_supported(self, H, W, cpg_in, cpg_out):
         return bool(self.ctx.lib.vido_gconv3x3_s2_supported(int(H), int(W), int(cpg_in), int(cpg_out)))
@@ -980,7 +1008,8 @@ def _ops_of(obj, out):
 def range_safe(*targets):
     """Scope in which every split-fp16 entry point of the HipOps objects behind `targets` (HipOps objects or modules) declines, so that their callers take the fp32 routes they
     already have: the 1x1 convolutions (conv1x1_conv, the fused bottleneck's conv1 / conv3 / shortcut, the FPN laterals) the library convolution, the direct 3x3 (wino3x3_conv)
-    the fp32 Winograd kernel, fc_h_linear F.linear, deconv2x2_conv F.conv_transpose2d.  The fp32 matrix kernels (gconv, convdirect, convsmall, correlation, Winograd) stay.
+    the fp32 Winograd kernel, the grouped 3x3 of 32 / 64 channels per group (gconv3x3_conv) the fp32 grouped kernel, fc_h_linear F.linear, deconv2x2_conv F.conv_transpose2d.
+    The fp32 matrix kernels (gconv, convdirect, convsmall, correlation, Winograd) stay.
     Results then have fp32's range: any finite activation is legal.  Only EAGER calls see the scope (a captured graph replays what it captured).  Nothing process-wide is read or
     changed, and no cached packed weight is replaced or freed (a captured graph reads them): a layer that normally runs on the direct 3x3 gains a Winograd pack on first use."""
     ops = list(_ops_of_all(targets))
@@ -1164,6 +1193,20 @@ def pack_gconv3x3(w, groups):
         return w9.reshape(groups, cpg_out // 32, 32, cpg_in // 8, 8, 9).permute(0, 1, 3, 5, 4, 2).contiguous()
     pad = w9.new_zeros((groups, 16, cpg_in // 8, 8, 9)); pad[:, :cpg_out] = w9
     return pad.permute(0, 2, 4, 3, 1).contiguous()
+
+
+def pack_gconv3x3_h(w, groups):
+    """Grouped convolution weight [groups * cpg, cpg, 3, 3] (cpg = 32 or 64 channels per group, in and out) -> the operand order of csrc/gconvh.hip: two fp16 planes of the output
+    channels scaled by powers of two (split_f16x2 over a channel's cpg x 9 weights), plane p of element (co, ci, dy, dx) of group g at
+    [g][(co % cpg) / 32][ci / 16][3 dy + dx][p][32 * ((ci % 16) / 8) + co % 32][ci % 8], followed by the [groups * cpg] inverse scales (flat int16 tensor).  None when the kernel
+    does not take the shape."""
+    cout, cpg = int(w.shape[0]), int(w.shape[1])
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or groups < 1 or cout != groups * cpg or cpg not in (32, 64):
+        return None
+    h, l, inv = split_f16x2(w.detach().reshape(cout, cpg * 9))
+    planes = torch.stack([h, l], 0).view(torch.int16).reshape(2, groups, cpg // 32, 32, cpg // 16, 2, 8, 9)      # [plane][g][cob][co32][step][k half][k8][tap]
+    planes = planes.permute(1, 2, 4, 7, 0, 5, 3, 6).contiguous().reshape(-1)                                   # [g][cob][step][tap][plane][k half][co32][k8]
+    return torch.cat([planes, inv.contiguous().view(torch.int16).reshape(-1)])
 
 
 def pack_conv_direct(w):
