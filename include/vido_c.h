@@ -670,6 +670,14 @@ int vido_gconv3x3_bias_act(vido_ctx* ctx, const float* x, const float* in_bias, 
  * vido_gconv3x3_h_supported: 1 when the kernel takes the shape (cpg_in == cpg_out in {32, 64}, W <= 93 / 45). */
 int vido_gconv3x3_h_supported(int H, int W, int cpg_in, int cpg_out);
 int vido_gconv3x3_h_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int groups, int cpg_in, int cpg_out, int H, int W, float slope);
+/* ... and with 8 -> 8 or 16 -> 16 channels per group on v_mfma_f32_16x16x32_f16 (csrc/gconvhs.hip): `conv2` of the ResNeXt bottlenecks of layer1 / layer2, any W.  w_packed
+ * (16-byte aligned): plane p of element (co, ci, dy, dx) of group g at [g][instruction i][p][16 b + co % cpg][ci % 8], where block b of instruction i is tap 3 dy + dx = 4 i + b
+ * (8 per group, 3 instructions, rows 8 .. 15 zero) or tap 2 i + (b >> 1) of input channels 8 (b & 1) .. + 7 (16 per group, 5 instructions), taps >= 9 zero; then [groups * cpg]
+ * floats: the inverse scales (vido_slam_amd/nets/ops.py::pack_gconv3x3_hs).  vido_gconv3x3_hs_supported: 1 when the kernel takes the shape (cpg_in == cpg_out in {8, 16},
+ * W <= 957 / 445).  vido_debug_ghs_plan: test hook, see csrc/gconvhs.hip. */
+int vido_gconv3x3_hs_supported(int H, int W, int cpg_in, int cpg_out);
+int vido_gconv3x3_hs_bias_act(vido_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* y, int groups, int cpg_in, int cpg_out, int H, int W, float slope);
+int vido_debug_ghs_plan(int groups, int H, int W, int cpg_in, int cpg_out, int* out, long long* loaded);
 /* ... with stride 2 (padding 1): the strided `conv2` of the first bottleneck of a ResNeXt stage (resnet.py:300-372 with STRIDE_IN_1X1 = False).  y [groups * cpg_out][(H + 1) / 2][W / 2];
  * W a multiple of 4, 8 / 16 / a multiple of 32 output channels per group (same w_packed), x 16-byte aligned, no in_bias.  vido_gconv3x3_s2_supported: 1 when the shape has a kernel. */
 int vido_gconv3x3_s2_supported(int H, int W, int cpg_in, int cpg_out);

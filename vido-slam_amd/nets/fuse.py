@@ -42,12 +42,14 @@ def fold_batchnorm(net, ops):
                 m._wd, m._bd = _fold(m.downsample[0], m.downsample[1], _eps(m.downsample[1])); n += 1
             m._ep = ops.bias_res_act_
             # the grouped 3x3 convolution + its bias + ReLU as one matrix-core kernel (csrc/gconv.hip) where it has a form for the layer
-            c2 = m.conv2; m._w2p = None; m._w2ph = None; m._ops = ops
+            c2 = m.conv2; m._w2p = None; m._w2ph = None; m._w2phs = None; m._ops = ops
             if c2.groups > 1 and tuple(c2.stride) == (1, 1) and tuple(c2.padding) == (1, 1) and tuple(c2.dilation) == (1, 1) and not os.environ.get("VIDO_NO_GCONV"):
-                from .ops import pack_gconv3x3, pack_gconv3x3_h
+                from .ops import pack_gconv3x3, pack_gconv3x3_h, pack_gconv3x3_hs
                 m._w2p = pack_gconv3x3(m._w2, c2.groups)
                 # 32 / 64 channels per group (layer3 / layer4): the split-fp16 form of csrc/gconvh.hip as well; ops.gconv3x3_conv picks per call (VIDO_GCONV_H=0: never)
                 m._w2ph = pack_gconv3x3_h(m._w2, c2.groups) if m._w2p is not None else None
+                # 8 / 16 channels per group (layer1 / layer2): that of csrc/gconvhs.hip (VIDO_GCONV_HS=0: never)
+                m._w2phs = pack_gconv3x3_hs(m._w2, c2.groups) if m._w2p is not None else None
             elif (c2.groups > 1 and tuple(c2.stride) == (2, 2) and tuple(c2.padding) == (1, 1) and tuple(c2.dilation) == (1, 1) and ((c2.out_channels // c2.groups) % 32 == 0 or (c2.out_channels // c2.groups) in (8, 16))
                   and not os.environ.get("VIDO_NO_GCONV") and not os.environ.get("VIDO_NO_GCONV_S2")):
                 from .ops import pack_gconv3x3

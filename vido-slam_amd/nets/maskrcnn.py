@@ -75,6 +75,7 @@ class _Bottleneck(nn.Module):              # resnet.py:277-372 (BottleneckWithFi
     _ep = None                             # nets/fuse.py::fold_batchnorm installs the folded tensors + the fused HIP epilogue
     _w2p = None                            # ... and conv2's weight in the operand order of csrc/gconv.hip where that kernel takes the layer
     _w2ph = None                           # ... and in the split-fp16 operand order of csrc/gconvh.hip (32 / 64 channels per group)
+    _w2phs = None                          # ... or of csrc/gconvhs.hip (8 / 16 channels per group)
     _w1p = _w3p = _wdp = None; _c1x1_min_tiles = 0      # ... and the 1x1 convolutions' in the operand order of csrc/conv1x1.hip (fuse.py decides which layers take it)
 
     def forward(self, x):
@@ -95,8 +96,8 @@ class _Bottleneck(nn.Module):              # resnet.py:277-372 (BottleneckWithFi
                     y = ep(F.conv2d(y if b1_done else ep(y, self._b1, None, 0.0), self._w2, None, c2.stride, c2.padding, c2.dilation, c2.groups), self._b2, None, 0.0)
             elif self._w2p is not None and y.shape[0] == 1 and self._ops.gconv3x3_supported(y.shape[2], y.shape[3], c2.in_channels // c2.groups, c2.out_channels // c2.groups):
                 # conv2's own bias + ReLU leave through its accumulators; after a library conv1 its bias + ReLU are applied where conv2 reads its operands
-                # (32 / 64 channels per group behind our own conv1: the split-fp16 kernel of csrc/gconvh.hip, see ops.gconv3x3_conv)
-                y = self._ops.gconv3x3_conv(y, self._w2p, self._w2ph, self._b2, c2.groups, 0.0, in_bias=None if b1_done else self._b1)
+                # (behind our own conv1: the split-fp16 kernels of csrc/gconvh.hip (32 / 64 channels per group) and csrc/gconvhs.hip (8 / 16), see ops.gconv3x3_conv)
+                y = self._ops.gconv3x3_conv(y, self._w2p, self._w2ph, self._b2, c2.groups, 0.0, in_bias=None if b1_done else self._b1, w_packed_hs=self._w2phs)
             else:
                 y = ep(F.conv2d(y if b1_done else ep(y, self._b1, None, 0.0), self._w2, None, c2.stride, c2.padding, c2.dilation, c2.groups), self._b2, None, 0.0)
             if self.downsample is None:

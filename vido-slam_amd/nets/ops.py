@@ -17,6 +17,7 @@ _CONV3X3_H_MIN_WGS = 0 if os.environ.get("VIDO_CONV3X3_H") == "0" else int(os.en
 # Round 6 (detector in split fp16, profiles/r6/convdirect_set_ab.txt): 125.0 frames/s with "novalu" against 124.3 / 124.5 with "all" (the chain without the detector: 191.4 against 193.8).
 _CONVDIRECT_SET = os.environ.get("VIDO_CONVDIRECT_SET", "novalu")
 _GCONV_H = os.environ.get("VIDO_GCONV_H", "1") != "0"      # split-fp16 grouped 3x3 (csrc/gconvh.hip) for 32 / 64 channels per group; 0: the fp32 kernel of csrc/gconv.hip everywhere
+_GCONV_HS = os.environ.get("VIDO_GCONV_HS", "1") != "0"    # ... and for 8 / 16 channels per group (csrc/gconvhs.hip); 0: only those layers back on the fp32 kernel (A/B runs)
 
 
 def correlation_torch_reference(first, second, stride):
@@ -231,14 +232,36 @@ class HipOps:
                                                               int(groups), cpg, cpg, H, W, C.c_float(slope)))
         return out
 
-    def gconv3x3_conv(self, x, w_packed, w_packed_h, bias, groups, slope=0.0, in_bias=None):
-        """The grouped 3x3 convolution of a ResNeXt bottleneck: the split-fp16 kernel (gconv3x3_h_bias_act, w_packed_h = pack_gconv3x3_h(w, groups) or None) when the operand needs
-        no input bias, the kernel takes the shape, the arithmetic setting is not f32 (conv1x1_set_arith(1) / VIDO_CONV1X1_ARITH=f32), no range_safe scope holds this object and
-        VIDO_GCONV_H is not 0; in every other case gconv3x3_bias_act (fp32 matrix instruction, w_packed = pack_gconv3x3(w, groups))."""
+    def gconv3x3_hs_supported(self, H, W, cpg_in, cpg_out):
+        return bool(self.ctx.lib.vido_gconv3x3_hs_supported(int(H), int(W), int(cpg_in), int(cpg_out)))
+
+    def gconv3x3_hs_bias_act(self, x, w_packed, bias, groups, slope=0.0):
+        """leaky_relu(conv2d(x, w, None, 1, 1, 1, groups) + bias, slope) for one image as one split-fp16 launch (csrc/gconvhs.hip: 8 -> 8 or 16 -> 16 channels per group, any W);
+        w_packed = pack_gconv3x3_hs(w, groups).  Activations must be finite and below 65504 in magnitude (conv1x1_range_flag otherwise)."""
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == 1
+        _, Cin, H, W = x.shape
+        cpg = Cin // groups
+        assert cpg in (8, 16) and bias.numel() == Cin and w_packed.dtype == torch.int16 and w_packed.numel() == int(groups) * (3 if cpg == 8 else 5) * 1024 + 2 * Cin, \
+            "gconv3x3_hs: weight not packed by pack_gconv3x3_hs for this layer"
+        out = torch.empty((1, Cin, H, W), device=x.device, dtype=torch.float32)
+        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * Cin * cpg * 9 * H * W
+        self._adopt_stream()
+        self.ctx._check(self.ctx.lib.vido_gconv3x3_hs_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                               int(groups), cpg, cpg, H, W, C.c_float(slope)))
+        return out
+
+    def gconv3x3_conv(self, x, w_packed, w_packed_h, bias, groups, slope=0.0, in_bias=None, w_packed_hs=None):
+        """The grouped 3x3 convolution of a ResNeXt bottleneck: a split-fp16 kernel — gconv3x3_h_bias_act (w_packed_h = pack_gconv3x3_h(w, groups) or None: 32 / 64 channels per
+        group) or gconv3x3_hs_bias_act (w_packed_hs = pack_gconv3x3_hs(w, groups) or None: 8 / 16 per group, unless VIDO_GCONV_HS is 0) — when the operand needs no input bias, the
+        kernel takes the shape, the arithmetic setting is not f32 (conv1x1_set_arith(1) / VIDO_CONV1X1_ARITH=f32), no range_safe scope holds this object and VIDO_GCONV_H is not 0;
+        in every other case gconv3x3_bias_act (fp32 matrix instruction, w_packed = pack_gconv3x3(w, groups))."""
         cpg = x.shape[1] // groups
-        if (_GCONV_H and w_packed_h is not None and in_bias is None and not self._range_safe and int(self.ctx.lib.vido_conv1x1_get_arith()) != 1
-                and bias.numel() == x.shape[1] and self.gconv3x3_h_supported(x.shape[2], x.shape[3], cpg, cpg)):
-            return self.gconv3x3_h_bias_act(x, w_packed_h, bias, groups, slope)
+        if (_GCONV_H and in_bias is None and not self._range_safe and bias.numel() == x.shape[1] and (w_packed_h is not None or (_GCONV_HS and w_packed_hs is not None))
+                and int(self.ctx.lib.vido_conv1x1_get_arith()) != 1):
+            if w_packed_h is not None and self.gconv3x3_h_supported(x.shape[2], x.shape[3], cpg, cpg):
+                return self.gconv3x3_h_bias_act(x, w_packed_h, bias, groups, slope)
+            if _GCONV_HS and w_packed_hs is not None and self.gconv3x3_hs_supported(x.shape[2], x.shape[3], cpg, cpg):
+                return self.gconv3x3_hs_bias_act(x, w_packed_hs, bias, groups, slope)
         return self.gconv3x3_bias_act(x, w_packed, bias, groups, slope, in_bias=in_bias)
 
     def gconv3x3_s2_supported(self, H, W, cpg_in, cpg_out):
@@ -1207,6 +1230,29 @@ def pack_gconv3x3_h(w, groups):
     planes = torch.stack([h, l], 0).view(torch.int16).reshape(2, groups, cpg // 32, 32, cpg // 16, 2, 8, 9)      # [plane][g][cob][co32][step][k half][k8][tap]
     planes = planes.permute(1, 2, 4, 7, 0, 5, 3, 6).contiguous().reshape(-1)                                   # [g][cob][step][tap][plane][k half][co32][k8]
     return torch.cat([planes, inv.contiguous().view(torch.int16).reshape(-1)])
+
+
+def pack_gconv3x3_hs(w, groups):
+    """Grouped convolution weight [groups * cpg, cpg, 3, 3] (cpg = 8 or 16 channels per group, in and out) -> the operand order of csrc/gconvhs.hip: two fp16 planes of the output
+    channels scaled by powers of two (split_f16x2 over a channel's cpg x 9 weights) as A operands of v_mfma_f32_16x16x32_f16, plane p of element (co, ci, dy, dx) of group g at
+    [g][i][p][16 * b + co % cpg][ci % 8]: block b (of 8 k) of instruction i is the slot of tap 3 dy + dx = 4 i + b at 8 per group (3 instructions; rows 8 .. 15 of every block are
+    zero) and of (tap 2 i + b // 2, input channels 8 (b % 2) .. + 7) at 16 per group (5 instructions); the slots of taps 9 .. 11 / tap 9 are zero.  Followed by the
+    [groups * cpg] inverse scales (flat int16 tensor of groups * (3 | 5) * 1024 + 2 * groups * cpg elements).  None when the kernel does not take the shape."""
+    if w.dim() != 4:
+        return None
+    cout, cpg = int(w.shape[0]), int(w.shape[1])
+    if tuple(w.shape[2:]) != (3, 3) or groups < 1 or cout != groups * cpg or cpg not in (8, 16):
+        return None
+    h, l, inv = split_f16x2(w.detach().reshape(cout, cpg * 9))
+    planes = torch.stack([h, l], 0).view(torch.int16).reshape(2, groups, cpg, cpg // 8, 8, 9)                  # [plane][g][co][channel group][k8][tap]
+    ni = 3 if cpg == 8 else 5
+    out = torch.zeros((groups, ni, 2, 4, 16, 8), dtype=torch.int16, device=planes.device)                       # [g][i][plane][b][row][k8]
+    for i in range(ni):
+        for b in range(4):
+            tap, cg = (4 * i + b, 0) if cpg == 8 else (2 * i + (b >> 1), b & 1)
+            if tap < 9:
+                out[:, i, :, b, :cpg, :] = planes[:, :, :, cg, :, tap].permute(1, 0, 2, 3)
+    return torch.cat([out.reshape(-1), inv.contiguous().view(torch.int16).reshape(-1)])
 
 
 def pack_conv_direct(w):
