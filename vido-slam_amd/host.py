@@ -11,10 +11,12 @@ raises VidoError.
 """
 import ctypes as C
 import os
+import re
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIDO_LIB_VARIANT") or os.path.join(_HERE, "libvido_slam_hip.so")      # (VIDO_LIB_VARIANT: an experiment build of the same sources, tools/r6/)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vido_c.h")                         # the path csrc/common.hpp includes: the one statement of every signature
 
 VIDO_OK = 0
 KP_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"), ("octave", "i4")])
@@ -33,52 +35,63 @@ class Config(C.Structure):
                 ("host_threads", C.c_int32)]
 
 
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "long long": C.c_longlong, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "vido_allreduce_fn": C.c_void_p}
+
+
+def _ctype(decl, fn, named):
+    """The ctypes type of one C declarator of `fn`: a parameter (`named`: its name, when it has one, comes last) or a return type.  Every pointer and array is c_void_p
+    (callers pass byref(...), ctypes arrays, ints or None), except `char*`, which is c_char_p; `void` is None."""
+    d = " ".join(re.sub(r"\bconst\b", " ", decl).split())
+    if "*" in d or "[" in d:
+        return C.c_char_p if re.fullmatch(r"char ?\*( ?\w+)?", d) else C.c_void_p
+    words = d.split()
+    for t in ([" ".join(words[:-1])] if named and len(words) > 1 else []) + [d]:
+        if t in _SCALARS:
+            return _SCALARS[t]
+    if d == "void" and not named:
+        return None
+    raise ValueError("%s: no ctypes type for `%s`" % (fn, decl.strip()))
+
+
+def parse_header(text):
+    """The text of include/vido_c.h -> {name: (restype, [argtypes])} for every `vido_*(` prototype in it.  Pure: nothing is loaded or bound.  A prototype that cannot be read
+    or a type outside the table raises ValueError with the function's name; nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    sigs = {}
+    for m in re.finditer(r"\b(vido_[a-z0-9_]+)\s*\(", text):
+        fn = m.group(1)
+        end = re.compile(r"([^()]*)\)\s*;").match(text, m.end())
+        ret = text[max(text.rfind(c, 0, m.start()) for c in ";{}") + 1:m.start()]
+        if end is None or not ret.strip() or fn in sigs:
+            raise ValueError("%s: not a prototype this parser reads (`type %s(type name, ...);`, declared once)" % (fn, fn))
+        params = end.group(1).split(",") if end.group(1).strip() not in ("", "void") else []
+        sigs[fn] = (_ctype(ret, fn, False), [_ctype(p, fn, True) for p in params])
+    return sigs
+
+
 _lib = None
 
 
 def load_library():
-    """dlopen the in-tree HIP library; raises if it has not been built (no fallback)."""
+    """dlopen the in-tree HIP library and give every function include/vido_c.h declares its restype / argtypes; raises if the library has not been built (no fallback)."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise VidoError(-2, "%s not built: run `python __graft_entry__.py` (build()) first; there is no CPU fallback" % LIB_PATH)
+    if not os.path.exists(HEADER_PATH):
+        raise VidoError(-2, "%s not found: the bindings take every signature from it; keep include/ beside the package directory" % HEADER_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.vido_last_error.restype = C.c_char_p
-    lib.vido_last_error.argtypes = [C.c_void_p]
-    lib.vido_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
-    lib.vido_destroy.argtypes = [C.c_void_p]
-    lib.vido_stream.restype = C.c_void_p
-    lib.vido_stream.argtypes = [C.c_void_p]
-    lib.vido_synchronize.argtypes = [C.c_void_p]
-    lib.vido_orb_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.vido_orb_extract_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.vido_orb_extract_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.vido_orb_level_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_orb_read_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.vido_orb_read_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-    lib.vido_orb_last_timing.argtypes = [C.c_void_p, C.c_void_p]
-    lib.vido_orb_geometry.argtypes = [C.c_void_p, C.c_void_p]
-    lib.vido_hamming_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_hamming_match_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_orb_describe_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_orb_patch_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_orb_patch_search.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_orb_patch_refine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_dis_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_flow_consistency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.vido_dis_flow_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p] * 5 + [C.c_int]
-    lib.vido_device_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.vido_mask_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.vido_frame_propagate_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.vido_mask_associate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.vido_mask_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.vido_frame_split_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    with open(HEADER_PATH) as f:
+        sigs = parse_header(f.read())
+    for name, (restype, argtypes) in sigs.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise VidoError(-2, "%s does not export %s, which %s declares: rebuild it (build())" % (LIB_PATH, name, HEADER_PATH)) from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -101,7 +114,8 @@ def default_config(**kw):
 
 
 def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    """the pointer argument for a numpy array (it keeps the array alive), None (NULL) for an absent one"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class Context:
@@ -163,7 +177,7 @@ class Context:
         h, w, cn = img.shape
         gray = np.empty((h, w), np.uint8)
         kps = np.zeros(self.max_kp, KP_DTYPE); desc = np.zeros((self.max_kp, 32), np.uint8); n = C.c_int()
-        self._check(self.lib.vido_orb_extract_color(self.h, _ptr(img), cn, int(bool(rgb_order)), 0, 1, C.c_size_t(0), w * cn, w, h, _ptr(gray),
+        self._check(self.lib.vido_orb_extract_color(self.h, _ptr(img), cn, int(bool(rgb_order)), 0, 1, 0, w * cn, w, h, _ptr(gray),
                                                     _ptr(kps), self.max_kp, C.byref(n), _ptr(desc)))
         return gray, kps[:n.value].copy(), desc[:n.value].copy()
 
@@ -186,8 +200,7 @@ class Context:
             cnt = np.zeros(n, np.int32)
             if reuse:
                 self._orb_out = getattr(self, "_orb_out", {}); self._orb_out[key] = (kps, desc, cnt)
-        self._check(self.lib.vido_orb_extract_batch(self.h, C.c_void_p(ptr), on_dev, n, fstride, rstride, w, h, _ptr(kps), self.max_kp,
-                                                    _ptr(cnt), _ptr(desc) if want_desc else None))
+        self._check(self.lib.vido_orb_extract_batch(self.h, ptr, on_dev, n, fstride, rstride, w, h, _ptr(kps), self.max_kp, _ptr(cnt), _ptr(desc)))
         return kps, desc, cnt
 
     def orb_level(self, frame, level, blurred=False):
@@ -219,14 +232,12 @@ class Context:
             if len(ref_desc) != n:
                 raise VidoError(-1, "orb_describe_points: %d reference descriptors for %d points" % (len(ref_desc), n))
         ang = np.empty(n, np.float32); desc = np.empty((n, 32), np.uint8); dist = np.empty(n, np.int32) if ref_desc is not None else None
-        self._check(self.lib.vido_orb_describe_points(self.h, frame, _ptr(xyl), n, _ptr(ref_desc) if ref_desc is not None else None, _ptr(ang), _ptr(desc),
-                                                      _ptr(dist) if dist is not None else None, 0))
+        self._check(self.lib.vido_orb_describe_points(self.h, frame, _ptr(xyl), n, _ptr(ref_desc), _ptr(ang), _ptr(desc), _ptr(dist), 0))
         return ang, desc, dist
 
     def orb_describe_points_device(self, frame, xyl_ptr, n, ref_ptr=None, angle_ptr=None, desc_ptr=None, dist_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_orb_describe_points(self.h, frame, vp(xyl_ptr), n, vp(ref_ptr), vp(angle_ptr), vp(desc_ptr), vp(dist_ptr), 1))
+        self._check(self.lib.vido_orb_describe_points(self.h, frame, xyl_ptr, n, ref_ptr, angle_ptr, desc_ptr, dist_ptr, 1))
 
     def orb_patch_points(self, frame, xyl, ref_patch=None, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10):
         """8 x 8 patches at given points of pyramid slab `frame` and their integer ZNCC verdict against ref_patch (vido_orb_patch_points): xyl (n,3) i32 = x, y in level
@@ -239,14 +250,12 @@ class Context:
                 raise VidoError(-1, "orb_patch_points: %d reference patches for %d points" % (len(ref_patch), n))
         patch = np.empty((n, 64), np.uint8)
         sums = np.empty((n, 3), np.int32) if ref_patch is not None else None; status = np.empty(n, np.int32) if ref_patch is not None else None
-        self._check(self.lib.vido_orb_patch_points(self.h, frame, _ptr(xyl), n, int(blurred), _ptr(ref_patch) if ref_patch is not None else None, int(min_var), int(min_zncc_q10),
-                                                   _ptr(patch), _ptr(sums) if sums is not None else None, _ptr(status) if status is not None else None, 0))
+        self._check(self.lib.vido_orb_patch_points(self.h, frame, _ptr(xyl), n, int(blurred), _ptr(ref_patch), int(min_var), int(min_zncc_q10), _ptr(patch), _ptr(sums), _ptr(status), 0))
         return patch, sums, status
 
     def orb_patch_points_device(self, frame, xyl_ptr, n, ref_ptr=None, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, patch_ptr=None, sums_ptr=None, status_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_orb_patch_points(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(min_var), int(min_zncc_q10), vp(patch_ptr), vp(sums_ptr), vp(status_ptr), 1))
+        self._check(self.lib.vido_orb_patch_points(self.h, frame, xyl_ptr, n, int(blurred), ref_ptr, int(min_var), int(min_zncc_q10), patch_ptr, sums_ptr, status_ptr, 1))
 
     def orb_patch_search(self, frame, xyl, ref_patch, radius, excl=2, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, peak_ratio_q10=0):
         """The offset within `radius` at which the 8 x 8 patch of pyramid slab `frame` correlates best with ref_patch (n,64) u8 (vido_orb_patch_search; the statement is
@@ -265,9 +274,8 @@ class Context:
     def orb_patch_search_device(self, frame, xyl_ptr, n, ref_ptr, radius, excl=2, blurred=1, min_var=PATCH_MIN_VAR, min_zncc_q10=PATCH_MIN_ZNCC_Q10, peak_ratio_q10=0,
                                 dxy_ptr=None, sums_ptr=None, second_ptr=None, status_ptr=None, stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_orb_patch_search(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(radius), int(excl), int(min_var), int(min_zncc_q10), int(peak_ratio_q10),
-                                                   vp(dxy_ptr), vp(sums_ptr), vp(second_ptr), vp(status_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_orb_patch_search(self.h, frame, xyl_ptr, n, int(blurred), ref_ptr, int(radius), int(excl), int(min_var), int(min_zncc_q10), int(peak_ratio_q10),
+                                                   dxy_ptr, sums_ptr, second_ptr, status_ptr, stats_ptr, 1))
 
     def orb_patch_refine(self, frame, xyl, ref_patch, iters=6, max_shift_q8=384, min_eig=0, blurred=1):
         """Sub-pixel alignment of ref_patch (n,64) u8 to pyramid slab `frame` around xyl (n,3) i32 = x, y in level coordinates, level (vido_orb_patch_refine; the statement
@@ -287,9 +295,8 @@ class Context:
     def orb_patch_refine_device(self, frame, xyl_ptr, n, ref_ptr, iters=6, max_shift_q8=384, min_eig=0, blurred=1, q8_ptr=None, cost_ptr=None, iters_ptr=None, status_ptr=None,
                                 stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_orb_patch_refine(self.h, frame, vp(xyl_ptr), n, int(blurred), vp(ref_ptr), int(iters), int(max_shift_q8), int(min_eig),
-                                                   vp(q8_ptr), vp(cost_ptr), vp(iters_ptr), vp(status_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_orb_patch_refine(self.h, frame, xyl_ptr, n, int(blurred), ref_ptr, int(iters), int(max_shift_q8), int(min_eig),
+                                                   q8_ptr, cost_ptr, iters_ptr, status_ptr, stats_ptr, 1))
 
     def dis_flow(self, img0, img1, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0):
         """Dense optical flow from img0 to img1 (vido_dis_flow; the statement is tests/refimpl/dis_flow_np.py): u8 H x W or H x W x 3|4 host arrays of one shape (a row
@@ -305,16 +312,15 @@ class Context:
             img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
         h, w = img0.shape[:2]
         flow = np.empty((h, w, 2), np.float32); q8 = np.empty((h, w, 2), np.int32); stats = np.empty(4, np.int32)
-        self._check(self.lib.vido_dis_flow(self.h, C.c_void_p(img0.ctypes.data), C.c_void_p(img1.ctypes.data), cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+        self._check(self.lib.vido_dis_flow(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
                                            int(max_shift_q8), int(min_eig), _ptr(flow), _ptr(q8), _ptr(stats), 0))
         return flow, q8, stats
 
     def dis_flow_device(self, img0_ptr, img1_ptr, channels, stride, width, height, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, flow_ptr=None, q8_ptr=None,
                         stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the context's scratch); any output pointer may be None, not all."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_dis_flow(self.h, vp(img0_ptr), vp(img1_ptr), int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
-                                           int(max_shift_q8), int(min_eig), vp(flow_ptr), vp(q8_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_dis_flow(self.h, img0_ptr, img1_ptr, int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
+                                           int(max_shift_q8), int(min_eig), flow_ptr, q8_ptr, stats_ptr, 1))
 
     def flow_consistency(self, fwd_q8, bwd_q8, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16):
         """Forward-backward check of two flow fields (vido_flow_consistency; the statement is tests/refimpl/flow_consistency_np.py): fwd_q8, bwd_q8 (H,W,2) i32 host arrays in
@@ -331,8 +337,7 @@ class Context:
 
     def flow_consistency_device(self, fwd_ptr, bwd_ptr, height, width, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16, status_ptr=None, marked_ptr=None, stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; any output pointer may be None, not all."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_flow_consistency(self.h, vp(fwd_ptr), vp(bwd_ptr), int(height), int(width), int(alpha_q10), int(beta_q16), vp(status_ptr), vp(marked_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_flow_consistency(self.h, fwd_ptr, bwd_ptr, int(height), int(width), int(alpha_q10), int(beta_q16), status_ptr, marked_ptr, stats_ptr, 1))
 
     def dis_flow_pair(self, img0, img1, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, alpha_q10=FLOW_ALPHA_Q10, beta_q16=FLOW_BETA_Q16):
         """dis_flow in both directions from one pyramid build, and flow_consistency of the two fields (vido_dis_flow_pair): images and flow parameters as for dis_flow, the
@@ -347,16 +352,15 @@ class Context:
             img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
         h, w = img0.shape[:2]
         flow = np.empty((h, w, 2), np.float32); fwd = np.empty((h, w, 2), np.int32); bwd = np.empty((h, w, 2), np.int32); status = np.empty((h, w), np.uint8); stats = np.empty(12, np.int32)
-        self._check(self.lib.vido_dis_flow_pair(self.h, C.c_void_p(img0.ctypes.data), C.c_void_p(img1.ctypes.data), cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+        self._check(self.lib.vido_dis_flow_pair(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
                                                 int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), _ptr(flow), _ptr(fwd), _ptr(bwd), _ptr(status), _ptr(stats), 0))
         return flow, fwd, bwd, status, stats
 
     def dis_flow_pair_device(self, img0_ptr, img1_ptr, channels, stride, width, height, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0, alpha_q10=FLOW_ALPHA_Q10,
                              beta_q16=FLOW_BETA_Q16, flow_ptr=None, fwd_ptr=None, bwd_ptr=None, status_ptr=None, stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the context's scratch); any output pointer may be None, not all."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._check(self.lib.vido_dis_flow_pair(self.h, vp(img0_ptr), vp(img1_ptr), int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
-                                                int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), vp(flow_ptr), vp(fwd_ptr), vp(bwd_ptr), vp(status_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_dis_flow_pair(self.h, img0_ptr, img1_ptr, int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
+                                                int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), flow_ptr, fwd_ptr, bwd_ptr, status_ptr, stats_ptr, 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)
@@ -398,11 +402,9 @@ class Context:
     def hamming_match_window_device(self, q_desc_ptr, q_xy_ptr, q_level_ptr, nq, t_desc_ptr, t_xy_ptr, t_level_ptr, nt, radius, level_tol, max_dist, ratio, unique,
                                     idx_ptr, dist_ptr, dist2_ptr, status_ptr, stats_ptr=None):
         """Device-pointer form: only enqueues on the context's stream; stats_ptr (5 x i32 on the device) may be None."""
-        vp = lambda p: C.c_void_p(p) if p else None
         num, den = self._ratio(ratio)
-        self._check(self.lib.vido_hamming_match_window(self.h, vp(q_desc_ptr), vp(q_xy_ptr), vp(q_level_ptr), int(nq), vp(t_desc_ptr), vp(t_xy_ptr), vp(t_level_ptr), int(nt),
-                                                       float(radius), int(level_tol), int(max_dist), num, den, int(bool(unique)), vp(idx_ptr), vp(dist_ptr), vp(dist2_ptr),
-                                                       vp(status_ptr), vp(stats_ptr), 1))
+        self._check(self.lib.vido_hamming_match_window(self.h, q_desc_ptr, q_xy_ptr, q_level_ptr, int(nq), t_desc_ptr, t_xy_ptr, t_level_ptr, int(nt),
+                                                       float(radius), int(level_tol), int(max_dist), num, den, int(bool(unique)), idx_ptr, dist_ptr, dist2_ptr, status_ptr, stats_ptr, 1))
 
     # ---- label-image propagation ---------------------------------------------------------------------
     def frame_propagate_mask(self, slot_last, slot_cur):
@@ -421,7 +423,7 @@ class Context:
         return int(st[0]), int(st[1]), int(st[2]), int(st[3])
 
     def hamming_match_device(self, a_ptr, na, b_ptr, nb, idx_ptr, dist_ptr):
-        self._check(self.lib.vido_hamming_match(self.h, C.c_void_p(a_ptr), na, C.c_void_p(b_ptr), nb, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), 1))
+        self._check(self.lib.vido_hamming_match(self.h, a_ptr, na, b_ptr, nb, idx_ptr, dist_ptr, 1))
 
 
 class TrackParams(C.Structure):
@@ -501,8 +503,7 @@ class FrameFeatures:
         else:
             dp, fp, mp, maps_dev = int(depth), int(flow), int(mask), (2 if alias else 1)     # 2: zero-copy, the slots refer to the caller's device buffers
         v = FrontendView()
-        ctx._check(ctx.lib.vido_frontend_batch(ctx.h, C.c_void_p(ptr), img_dev, n, C.c_size_t(fstride), rstride, w, h, C.c_void_p(dp), C.c_void_p(fp), C.c_void_p(mp),
-                                               maps_dev, slot0, C.byref(self.p), C.byref(v)))
+        ctx._check(ctx.lib.vido_frontend_batch(ctx.h, ptr, img_dev, n, fstride, rstride, w, h, dp, fp, mp, maps_dev, slot0, C.byref(self.p), C.byref(v)))
         cache = self.__dict__.setdefault("_views", {})          # the result buffers are ctx-owned and stable between calls: build each numpy view once
         def arr(p, shape, dtype):
             key = (p, shape, np.dtype(dtype).str)
@@ -530,7 +531,7 @@ class FrameFeatures:
     def gather_object_depth_label(self, slot, keys):
         keys = np.ascontiguousarray(keys, np.float32).reshape(-1, 2)
         d = np.empty(len(keys), np.float32); l = np.empty(len(keys), np.int32)
-        self.ctx._check(self.ctx.lib.vido_gather_object_depth_label(self.ctx.h, slot, _ptr(keys), len(keys), C.c_float(self.p.th_depth_obj), _ptr(d), _ptr(l)))
+        self.ctx._check(self.ctx.lib.vido_gather_object_depth_label(self.ctx.h, slot, _ptr(keys), len(keys), self.p.th_depth_obj, _ptr(d), _ptr(l)))
         return d, l
 
     def gather_point_samples(self, slot, xy):
@@ -697,7 +698,6 @@ def rccl_direct_init(ctx, rank=0, world=1):
     """Prepare `ctx` for the library's own RCCL all-reduce (vido_rccl_*, csrc/rccl.cpp): rank 0 draws the unique id, torch.distributed broadcasts its 128 bytes
     (any transport would do), every rank initialises its communicator.  Afterwards pass allreduce="rccl" to ba_optimize."""
     lib = ctx.lib
-    lib.vido_rccl_unique_id.argtypes = [C.c_void_p]; lib.vido_rccl_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     buf = (C.c_uint8 * 128)()
     if rank == 0:
         ctx._check(lib.vido_rccl_unique_id(buf))
@@ -787,8 +787,7 @@ def pnp_ransac(ctx, pts3d, pts2d, K, max_iters=500, reproj_err=0.4, confidence=0
     """cv::solvePnPRansac(..., SOLVEPNP_P3P) as called by Tracking::GetInitModelCam/Obj (Tracking.cc:1965, 2068)."""
     X = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3); x = np.ascontiguousarray(pts2d, np.float32).reshape(-1, 2)
     T = np.zeros(16); mask = np.zeros(max(len(X), 1), np.uint8); n = C.c_int32()
-    ctx._check(ctx.lib.vido_pnp_ransac(ctx.h, _ptr(X), _ptr(x), len(X), C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]),
-                                       max_iters, C.c_double(reproj_err), C.c_double(confidence), C.c_uint64(seed), _ptr(T), _ptr(mask), C.byref(n)))
+    ctx._check(ctx.lib.vido_pnp_ransac(ctx.h, _ptr(X), _ptr(x), len(X), K[0], K[1], K[2], K[3], max_iters, reproj_err, confidence, seed, _ptr(T), _ptr(mask), C.byref(n)))
     return T.reshape(4, 4), mask[:len(X)].astype(bool), n.value
 
 
@@ -811,14 +810,14 @@ class NetOps:
         f = np.ascontiguousarray(input, np.float32); r = np.ascontiguousarray(rois, np.float32).reshape(-1, 5)
         B, Cc, H, W = f.shape; ph, pw = output_size
         out = np.empty((len(r), Cc, ph, pw), np.float32)
-        self.ctx._check(self.ctx.lib.vido_roi_align(self.ctx.h, _ptr(f), B, Cc, H, W, _ptr(r), len(r), C.c_float(spatial_scale), ph, pw,
+        self.ctx._check(self.ctx.lib.vido_roi_align(self.ctx.h, _ptr(f), B, Cc, H, W, _ptr(r), len(r), spatial_scale, ph, pw,
                                                     sampling_ratio, _ptr(out), 0))
         return out
 
     def nms(self, boxes, scores, nms_thresh):
         b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4); s = np.ascontiguousarray(scores, np.float32)
         keep = np.empty(max(len(b), 1), np.int32); n = C.c_int32()
-        self.ctx._check(self.ctx.lib.vido_nms(self.ctx.h, _ptr(b), _ptr(s), len(b), C.c_float(nms_thresh), _ptr(keep), C.byref(n), 0))
+        self.ctx._check(self.ctx.lib.vido_nms(self.ctx.h, _ptr(b), _ptr(s), len(b), nms_thresh, _ptr(keep), C.byref(n), 0))
         return keep[:n.value].astype(np.int64)
 
     def box_decode(self, rel_codes, boxes, weights=(1.0, 1.0, 1.0, 1.0)):
@@ -904,7 +903,7 @@ def dyn_obj_tracking(sem_label, obj_label, obj_xy, obj_depth, flow3d, last_sem_l
     lml = np.ascontiguousarray(last_mod_label, np.int32); mid = C.c_int32(max_id); k = C.c_int32()
     off = np.zeros(n + 2, np.int32); ids = np.zeros(n + 1, np.int32); ml = np.zeros(n + 1, np.int32); sp = np.zeros(n + 1, np.int32)
     _rc(load_library().vido_dyn_obj_tracking(_ptr(sem), _ptr(lab), _ptr(xy), _ptr(dep), _ptr(f3), _ptr(lsem), n, _ptr(lsp), _ptr(lst), _ptr(lml), len(lsp), int(rows), int(cols),
-                                             C.c_float(sf_mg), C.c_float(sf_ds), C.c_float(th_depth_obj), int(f_id), C.byref(mid), _ptr(off), _ptr(ids), _ptr(ml), _ptr(sp), n + 1, C.byref(k)),
+                                             sf_mg, sf_ds, th_depth_obj, int(f_id), C.byref(mid), _ptr(off), _ptr(ids), _ptr(ml), _ptr(sp), n + 1, C.byref(k)),
         "dyn_obj_tracking")
     k = k.value
     return dict(obj_label=lab, objects=[ids[off[i]:off[i + 1]].copy() for i in range(k)], mod_label=ml[:k].copy(), sem_position=sp[:k].copy(), max_id=mid.value)

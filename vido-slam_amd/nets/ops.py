@@ -29,6 +29,21 @@ def correlation_torch_reference(first, second, stride):
     return torch.stack([(a * pad[:, :, p:p + H, o:o + W]).mean(1) for p in range(7) for o in range(7)], 1)
 
 
+def _p(t):
+    """the pointer argument for a tensor: its data_ptr(), None (NULL) for an absent one"""
+    return t.data_ptr() if t is not None else None
+
+
+def cached_pack(mod, slot, w, device, extra, pack):
+    """pack() kept on `mod` as the attribute `slot`: made on first use and again when the weight tensor `w` (its storage or its version: a checkpoint loaded later), the
+    device or one of the `extra` key parts differs from the call that made it."""
+    key = (w.data_ptr(), w._version, str(device)) + tuple(extra)
+    keys = mod.__dict__.setdefault("_pack_keys", {})
+    if keys.get(slot) != key:
+        setattr(mod, slot, pack()); keys[slot] = key
+    return getattr(mod, slot)
+
+
 class HipOps:
     """FunctionCorrelation / ROIAlign / nms / box decode on device tensors through libvido_slam_hip.so."""
 
@@ -36,6 +51,16 @@ class HipOps:
 
     def __init__(self, ctx):
         self.ctx = ctx
+
+    def _call(self, fn, *args):
+        """fn(ctx, *args) for a library function `fn` (self.ctx.lib.vido_x) enqueued on torch's current stream; a negative return raises VidoError"""
+        ctx = self.ctx
+        ctx._check(ctx.lib.vido_set_stream(ctx.h, torch.cuda.current_stream().cuda_stream, 1))      # (_adopt_stream, without its frame: every eager launch comes through here)
+        return ctx._check(fn(ctx.h, *args))
+
+    def _count_flops(self, flops):
+        """launches torch's FlopCounterMode does not see; bench.py resets and reads gconv_flops"""
+        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + flops
 
     @property
     def range_safe_active(self):
@@ -48,11 +73,11 @@ class HipOps:
         if n_live is None:
             return None
         assert n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1, "n_live: a one-element int32 device tensor"
-        return C.c_void_p(n_live.data_ptr())
+        return n_live.data_ptr()
 
     def _adopt_stream(self):
         st = torch.cuda.current_stream().cuda_stream
-        self.ctx._check(self.ctx.lib.vido_set_stream(self.ctx.h, C.c_void_p(st), 1))
+        self.ctx._check(self.ctx.lib.vido_set_stream(self.ctx.h, st, 1))
 
     def correlation(self, first, second, stride):
         if not first.is_cuda:
@@ -60,17 +85,14 @@ class HipOps:
         first = first.contiguous().float(); second = second.contiguous().float()
         B, Cc, H, W = first.shape
         out = torch.empty((B, 49, (H + stride - 1) // stride, (W + stride - 1) // stride), device=first.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_correlation(self.ctx.h, C.c_void_p(first.data_ptr()), C.c_void_p(second.data_ptr()), B, Cc, H, W, stride,
-                                                      C.c_void_p(out.data_ptr()), 1))
+        self._call(self.ctx.lib.vido_correlation, first.data_ptr(), second.data_ptr(), B, Cc, H, W, stride, out.data_ptr(), 1)
         return out
 
     def bias_act_(self, x, bias, slope):
         """in place: x = leaky_relu(x + bias[None, :, None, None], slope)"""
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
         N, Cc, H, W = x.shape
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), N, Cc, H, W, C.c_float(slope)))
+        self._call(self.ctx.lib.vido_bias_act, x.data_ptr(), bias.data_ptr(), N, Cc, H, W, slope)
         return x
 
     def deconv2x2_conv(self, conv, x, slope, n_live=None):
@@ -83,15 +105,11 @@ class HipOps:
         n, cin, H, W = (int(v) for v in x.shape); cout = int(w.shape[1])
         if not self.ctx.lib.vido_deconv2x2_supported(n, cin, cout, H, W):
             return None
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(conv, "_dc_key", None) != key:
-            conv._dc_w = pack_deconv2x2(w).to(x.device); conv._dc_key = key
+        wp = cached_pack(conv, "_dc_w", w, x.device, (), lambda: pack_deconv2x2(w).to(x.device))
         out = torch.empty((n, cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * n * cin * cout * 4 * H * W
-        self._adopt_stream()
-        b = conv.bias
-        self.ctx._check(self.ctx.lib.vido_deconv2x2_bias_act_n(self.ctx.h, C.c_void_p(x.contiguous().data_ptr()), C.c_void_p(conv._dc_w.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
-                                                               C.c_void_p(out.data_ptr()), n, cin, cout, H, W, C.c_float(slope), self._live_ptr(n_live)))
+        self._count_flops(2.0 * n * cin * cout * 4 * H * W)
+        x = x.contiguous()
+        self._call(self.ctx.lib.vido_deconv2x2_bias_act_n, x.data_ptr(), wp.data_ptr(), _p(conv.bias), out.data_ptr(), n, cin, cout, H, W, slope, self._live_ptr(n_live))
         return out
 
     def det_order(self, scores, labels, n_det, confidence, count32=False):
@@ -102,9 +120,7 @@ class HipOps:
         cap = int(scores.shape[0]); dev = scores.device
         order = torch.empty((cap,), device=dev, dtype=torch.int64); lab = torch.empty((cap,), device=dev, dtype=torch.int64); n_live = torch.empty((), device=dev, dtype=torch.int64)
         n32 = torch.empty((1,), device=dev, dtype=torch.int32) if count32 else None
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_det_order_n(self.ctx.h, C.c_void_p(scores.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_float(confidence), cap,
-                                                      C.c_void_p(order.data_ptr()), C.c_void_p(lab.data_ptr()), C.c_void_p(n_live.data_ptr()), C.c_void_p(n32.data_ptr()) if count32 else None))
+        self._call(self.ctx.lib.vido_det_order_n, scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), confidence, cap, order.data_ptr(), lab.data_ptr(), n_live.data_ptr(), _p(n32))
         return (order, lab, n_live, n32) if count32 else (order, lab, n_live)
 
     def roi_levels(self, boxes, k_min, k_max):
@@ -113,8 +129,7 @@ class HipOps:
         assert boxes.is_cuda and boxes.dtype == torch.float32
         boxes = boxes.contiguous(); n = int(boxes.shape[0])
         out = torch.empty((n,), device=boxes.device, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_roi_levels(self.ctx.h, C.c_void_p(boxes.data_ptr()), n, C.c_float(k_min), C.c_float(k_max), C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_roi_levels, boxes.data_ptr(), n, k_min, k_max, out.data_ptr())
         return out
 
     def mask_logit_select(self, feat, conv, labels, n_live=None):
@@ -126,9 +141,7 @@ class HipOps:
         if not w.is_contiguous():
             w = w.contiguous()
         out = torch.empty((n, 1, H, W), device=feat.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_logit_select_n(self.ctx.h, C.c_void_p(feat.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(conv.bias.data_ptr()) if conv.bias is not None else None,
-                                                            C.c_void_p(labels.data_ptr()), C.c_void_p(out.data_ptr()), int(n), int(c), int(H * W), classes, self._live_ptr(n_live)))
+        self._call(self.ctx.lib.vido_mask_logit_select_n, feat.data_ptr(), w.data_ptr(), _p(conv.bias), labels.data_ptr(), out.data_ptr(), int(n), int(c), int(H * W), classes, self._live_ptr(n_live))
         return out
 
     def bias_res_act_(self, x, bias, res, slope):
@@ -137,17 +150,14 @@ class HipOps:
         N, Cc, H, W = x.shape
         if res is not None:
             assert res.shape == x.shape and res.is_contiguous() and res.dtype == torch.float32
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_bias_res_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()),
-                                                       C.c_void_p(res.data_ptr()) if res is not None else None, N, Cc, H, W, C.c_float(slope)))
+        self._call(self.ctx.lib.vido_bias_res_act, x.data_ptr(), bias.data_ptr(), _p(res), N, Cc, H, W, slope)
         return x
 
     def bias_unary_(self, x, bias, kind):
         """in place: x = f(x + bias[None, :, None, None]); kind "elu" | "sigmoid" """
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
         N, Cc, H, W = x.shape
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_bias_unary(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()), N, Cc, H, W, 1 if kind == "elu" else 2))
+        self._call(self.ctx.lib.vido_bias_unary, x.data_ptr(), bias.data_ptr(), N, Cc, H, W, 1 if kind == "elu" else 2)
         return x
 
     def upcat_reflect(self, x, skip=None):
@@ -159,8 +169,7 @@ class HipOps:
             assert skip.is_contiguous() and skip.shape[0] == 1 and tuple(skip.shape[2:]) == (2 * h, 2 * w)
             C2 = skip.shape[1]
         out = torch.empty((1, C1 + C2, 2 * h + 2, 2 * w + 2), device=x.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_upcat_reflect(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(skip.data_ptr()) if skip is not None else None, C1, C2, h, w, C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_upcat_reflect, x.data_ptr(), _p(skip), C1, C2, h, w, out.data_ptr())
         return out
 
     def minmax_norm_u16(self, d):
@@ -168,16 +177,14 @@ class HipOps:
         d = d.contiguous()
         mm = torch.stack(torch.aminmax(d))
         out = torch.empty(d.shape, device=d.device, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_minmax_norm_u16(self.ctx.h, C.c_void_p(d.data_ptr()), C.c_void_p(mm.data_ptr()), C.c_int64(d.numel()), C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_minmax_norm_u16, d.data_ptr(), mm.data_ptr(), d.numel(), out.data_ptr())
         return out
 
     def area_feed(self, bgr, feed, div=1.0):
         """u8 HxWx3 BGR device tensor -> f32 [1,3,feed_h,feed_w] RGB, area-resized, / div (flip + permute + float + interpolate(area) + div in one pass)"""
         assert bgr.is_cuda and bgr.dtype == torch.uint8 and bgr.is_contiguous() and bgr.dim() == 3 and bgr.shape[2] == 3
         out = torch.empty((1, 3, int(feed[0]), int(feed[1])), device=bgr.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_area_feed(self.ctx.h, C.c_void_p(bgr.data_ptr()), bgr.shape[0], bgr.shape[1], C.c_void_p(out.data_ptr()), int(feed[0]), int(feed[1]), C.c_float(div)))
+        self._call(self.ctx.lib.vido_area_feed, bgr.data_ptr(), bgr.shape[0], bgr.shape[1], out.data_ptr(), int(feed[0]), int(feed[1]), div)
         return out
 
     def backwarp(self, x, flow):
@@ -185,8 +192,7 @@ class HipOps:
         assert x.is_cuda and x.dtype == torch.float32 and flow.dtype == torch.float32 and x.shape[0] == flow.shape[0] and x.shape[2:] == flow.shape[2:] and flow.shape[1] == 2
         x = x.contiguous(); flow = flow.contiguous()
         out = torch.empty_like(x)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_backwarp(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(flow.data_ptr()), x.shape[0], x.shape[1], x.shape[2], x.shape[3], C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_backwarp, x.data_ptr(), flow.data_ptr(), x.shape[0], x.shape[1], x.shape[2], x.shape[3], out.data_ptr())
         return out
 
     def deconv4s2_depthwise(self, x, weight, input_slope=1.0):
@@ -194,8 +200,7 @@ class HipOps:
         x = x.contiguous(); B, Cc, H, W = x.shape
         assert weight.shape == (Cc, 1, 4, 4) and weight.is_contiguous()
         out = torch.empty((B, Cc, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_deconv4s2_depthwise(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(weight.data_ptr()), B, Cc, H, W, C.c_float(input_slope), C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_deconv4s2_depthwise, x.data_ptr(), weight.data_ptr(), B, Cc, H, W, input_slope, out.data_ptr())
         return out
 
     def gconv3x3_supported(self, H, W, cpg_in, cpg_out):
@@ -208,11 +213,8 @@ class HipOps:
         _, Cin, H, W = x.shape
         cpg_in = Cin // groups; cpg_out = bias.numel() // groups
         out = torch.empty((1, bias.numel(), H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * bias.numel() * cpg_in * 9 * H * W      # (torch's FlopCounterMode does not see this launch; bench.py adds it)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_gconv3x3_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(in_bias.data_ptr()) if in_bias is not None else None,
-                                                            C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                            int(groups), cpg_in, cpg_out, H, W, C.c_float(slope)))
+        self._count_flops(2.0 * bias.numel() * cpg_in * 9 * H * W)
+        self._call(self.ctx.lib.vido_gconv3x3_bias_act, x.data_ptr(), _p(in_bias), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), int(groups), cpg_in, cpg_out, H, W, slope)
         return out
 
     def gconv3x3_h_supported(self, H, W, cpg_in, cpg_out):
@@ -226,10 +228,8 @@ class HipOps:
         cpg = Cin // groups
         assert bias.numel() == Cin and w_packed.dtype == torch.int16 and w_packed.numel() == 2 * Cin * (cpg * 9 + 1), "gconv3x3_h: weight not packed by pack_gconv3x3_h for this layer"
         out = torch.empty((1, Cin, H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * Cin * cpg * 9 * H * W
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_gconv3x3_h_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                              int(groups), cpg, cpg, H, W, C.c_float(slope)))
+        self._count_flops(2.0 * Cin * cpg * 9 * H * W)
+        self._call(self.ctx.lib.vido_gconv3x3_h_bias_act, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), int(groups), cpg, cpg, H, W, slope)
         return out
 
     def gconv3x3_hs_supported(self, H, W, cpg_in, cpg_out):
@@ -244,10 +244,8 @@ class HipOps:
         assert cpg in (8, 16) and bias.numel() == Cin and w_packed.dtype == torch.int16 and w_packed.numel() == int(groups) * (3 if cpg == 8 else 5) * 1024 + 2 * Cin, \
             "gconv3x3_hs: weight not packed by pack_gconv3x3_hs for this layer"
         out = torch.empty((1, Cin, H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * Cin * cpg * 9 * H * W
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_gconv3x3_hs_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                               int(groups), cpg, cpg, H, W, C.c_float(slope)))
+        self._count_flops(2.0 * Cin * cpg * 9 * H * W)
+        self._call(self.ctx.lib.vido_gconv3x3_hs_bias_act, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), int(groups), cpg, cpg, H, W, slope)
         return out
 
     def gconv3x3_conv(self, x, w_packed, w_packed_h, bias, groups, slope=0.0, in_bias=None, w_packed_hs=None):
@@ -273,10 +271,8 @@ class HipOps:
         _, Cin, H, W = x.shape
         cpg_in = Cin // groups; cpg_out = bias.numel() // groups
         out = torch.empty((1, bias.numel(), (H + 1) // 2, W // 2), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * bias.numel() * cpg_in * 9 * out.shape[2] * out.shape[3]
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_gconv3x3_s2_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                               int(groups), cpg_in, cpg_out, H, W, C.c_float(slope)))
+        self._count_flops(2.0 * bias.numel() * cpg_in * 9 * out.shape[2] * out.shape[3])
+        self._call(self.ctx.lib.vido_gconv3x3_s2_bias_act, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), int(groups), cpg_in, cpg_out, H, W, slope)
         return out
 
     def conv1x1_supported(self, cin, cout, hw):
@@ -291,8 +287,7 @@ class HipOps:
         """Enqueue on the current stream: dst |= this context's range flag, flag = 0 (vido_range_latch).  dst: an int32 tensor of one element or more (its first word), on the
         device or pinned on the host; zero it before the launches it is to cover.  In stream order dst then holds the trips of the split-fp16 launches enqueued before the latch."""
         assert dst.dtype == torch.int32 and dst.numel() >= 1 and dst.is_contiguous() and (dst.is_cuda or dst.is_pinned()), "range_latch: an int32 word on the device or pinned"
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_range_latch(self.ctx.h, C.c_void_p(dst.data_ptr())))
+        self._call(self.ctx.lib.vido_range_latch, dst.data_ptr())
         return dst
 
     def conv1x1_range_flag(self, reset=True):
@@ -317,18 +312,14 @@ class HipOps:
             "conv1x1: weight packed for another form (pack_conv1x1(w, layout))"      # (an unsupported shape is refused by the library call below)
         assert 0.0 <= slope <= 1.0 and (residual is None or residual_up2 is None)
         out = torch.empty((1, cout, H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * cout * cin * H * W      # (torch's FlopCounterMode does not see this launch; bench.py adds it)
-        self._adopt_stream()
-        pb = C.c_void_p(bias.data_ptr()) if bias is not None else None
+        self._count_flops(2.0 * cout * cin * H * W)
         if residual_up2 is not None:
             residual_up2 = residual_up2.contiguous(); assert tuple(residual_up2.shape) == (1, cout, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0
-            self.ctx._check(self.ctx.lib.vido_conv1x1_bias_up2_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), pb, C.c_void_p(residual_up2.data_ptr()),
-                                                                   C.c_void_p(out.data_ptr()), int(cin), int(cout), int(H), int(W), C.c_float(slope)))
+            self._call(self.ctx.lib.vido_conv1x1_bias_up2_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), residual_up2.data_ptr(), out.data_ptr(), int(cin), int(cout), int(H), int(W), slope)
             return out
         if residual is not None:
             residual = residual.contiguous(); assert residual.shape == out.shape
-        self.ctx._check(self.ctx.lib.vido_conv1x1_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), pb,
-                                                           C.c_void_p(residual.data_ptr()) if residual is not None else None, C.c_void_p(out.data_ptr()), int(cin), int(cout), int(H * W), C.c_float(slope)))
+        self._call(self.ctx.lib.vido_conv1x1_bias_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), _p(residual), out.data_ptr(), int(cin), int(cout), int(H * W), slope)
         return out
 
     def conv1x1_conv(self, conv, x, slope=1.0, residual=None, residual_up2=None):
@@ -341,10 +332,8 @@ class HipOps:
         if not conv1x1_fills_chip(w.shape[0], x.shape[2] * x.shape[3]):
             return None
         layout = self.conv1x1_layout(w.shape[1], w.shape[0], x.shape[2] * x.shape[3])
-        key = (w.data_ptr(), w._version, str(x.device), layout)
-        if getattr(conv, "_c1_key", None) != key:
-            conv._c1_w = pack_conv1x1(w, layout).to(x.device); conv._c1_key = key
-        return self.conv1x1_bias_act(x.contiguous(), conv._c1_w, conv.bias, residual, slope, residual_up2)
+        wp = cached_pack(conv, "_c1_w", w, x.device, (layout,), lambda: pack_conv1x1(w, layout).to(x.device))      # (the layout is a key part: one pack, of the form last met)
+        return self.conv1x1_bias_act(x.contiguous(), wp, conv.bias, residual, slope, residual_up2)
 
     def conv_kxk_c2(self, conv, x, residual=None):
         """conv(x) + residual for a k x k (3, 5, 7) stride-1 `same` convolution with TWO output channels on one image — the last layer of LiteFlowNet's flow heads — as one
@@ -359,10 +348,8 @@ class HipOps:
         out = torch.empty((1, 2, H, W), device=x.device, dtype=torch.float32)
         if residual is not None:
             residual = residual.contiguous(); assert residual.shape == out.shape
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * 2 * cin * k * k * H * W
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_conv_kxk_c2(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(wc.data_ptr()), C.c_void_p(conv.bias.data_ptr()) if conv.bias is not None else None,
-                                                      C.c_void_p(residual.data_ptr()) if residual is not None else None, C.c_void_p(out.data_ptr()), int(cin), k, int(H), int(W)))
+        self._count_flops(2.0 * 2 * cin * k * k * H * W)
+        self._call(self.ctx.lib.vido_conv_kxk_c2, x.data_ptr(), wc.data_ptr(), _p(conv.bias), _p(residual), out.data_ptr(), int(cin), k, int(H), int(W))
         return out
 
     def conv1x1_skinny(self, x, w_packed, bias, cout, slope=1.0, residual=None):
@@ -373,10 +360,8 @@ class HipOps:
         out = torch.empty((1, cout, H, W), device=x.device, dtype=torch.float32)
         if residual is not None:
             residual = residual.contiguous(); assert residual.shape == out.shape
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * cout * cin * H * W
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_conv1x1_skinny(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                                         C.c_void_p(residual.data_ptr()) if residual is not None else None, C.c_void_p(out.data_ptr()), cin, int(cout), C.c_longlong(H * W), C.c_float(slope)))
+        self._count_flops(2.0 * cout * cin * H * W)
+        self._call(self.ctx.lib.vido_conv1x1_skinny, x.data_ptr(), w_packed.data_ptr(), _p(bias), _p(residual), out.data_ptr(), cin, int(cout), H * W, slope)
         return out
 
     def conv1x1_skinny_conv(self, conv, x, slope=1.0):
@@ -386,10 +371,7 @@ class HipOps:
         if (tuple(w.shape[2:]) != (1, 1) or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (0, 0) or conv.groups != 1 or cin % 2 or cin > 256 or cout > 256
                 or not x.is_cuda or x.shape[0] != 1 or x.dtype != torch.float32):
             return None
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(conv, "_c1s_key", None) != key:
-            conv._c1s_w = pack_conv1x1_skinny(w).to(x.device); conv._c1s_key = key
-        return self.conv1x1_skinny(x, conv._c1s_w, conv.bias, cout, slope)
+        return self.conv1x1_skinny(x, cached_pack(conv, "_c1s_w", w, x.device, (), lambda: pack_conv1x1_skinny(w).to(x.device)), conv.bias, cout, slope)
 
     def stem7x7s2_pool(self, x, w_packed, bias):
         """max_pool2d(relu(conv2d(x, w, None, 2, 3) + bias), 3, 2, 1) for one image, 7x7, 3 -> 64 channels, as ONE launch whose convolution output stays on the chip
@@ -398,19 +380,16 @@ class HipOps:
         x = x.contiguous(); H, W = int(x.shape[2]), int(x.shape[3])
         Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         out = torch.empty((1, 64, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * 64 * 147 * Hc * Wc
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_stem7x7s2_pool(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()), H, W))
+        self._count_flops(2.0 * 64 * 147 * Hc * Wc)
+        self._call(self.ctx.lib.vido_stem7x7s2_pool, x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), H, W)
         return out
 
     def stem7x7s2_pool_conv(self, mod, w, bias, x):
         """The same for a folded stem weight `w` [64, 3, 7, 7] / `bias` [64]; None when they are not of that form.  Packed weight cached on `mod`, rebuilt when `w` changes."""
         if tuple(w.shape) != (64, 3, 7, 7) or bias is None or bias.numel() != 64 or not x.is_cuda or x.shape[0] != 1 or x.shape[1] != 3 or x.dtype != torch.float32 or w.dtype != torch.float32:
             return None
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(mod, "_stem_key", None) != key:
-            mod._stem_w = pack_stem7x7(w).to(x.device); mod._stem_b = bias.detach().to(x.device).contiguous(); mod._stem_key = key
-        return self.stem7x7s2_pool(x, mod._stem_w, mod._stem_b)
+        wp, bp = cached_pack(mod, "_stem_w", w, x.device, (), lambda: (pack_stem7x7(w).to(x.device), bias.detach().to(x.device).contiguous()))
+        return self.stem7x7s2_pool(x, wp, bp)
 
     def wino3x3_supported(self, cin, cout, H, W):
         return bool(self.ctx.lib.vido_wino3x3_supported(int(cin), int(cout), int(H), int(W)))
@@ -425,10 +404,8 @@ class HipOps:
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and u_packed.is_cuda
         N, cin, H, W = x.shape
         out = torch.empty((N, cout, H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * N * cout * cin * 9 * H * W      # direct-convolution count, as FlopCounterMode would give the library call
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_wino3x3_bias_act_form(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(u_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                                                C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope), int(form)))
+        self._count_flops(2.0 * N * cout * cin * 9 * H * W)                                                  # direct-convolution count, as FlopCounterMode would give the library call
+        self._call(self.ctx.lib.vido_wino3x3_bias_act_form, x.data_ptr(), u_packed.data_ptr(), _p(bias), out.data_ptr(), int(N), int(cin), int(cout), int(H), int(W), slope, int(form))
         return out
 
     def wino3x3_conv(self, conv, x, slope, weight=None, bias=None, n_live=None):
@@ -451,17 +428,13 @@ class HipOps:
         if (_CONV3X3_H_MIN_WGS > 0 and x.dtype == torch.float32 and not self._range_safe and self.ctx.lib.vido_conv3x3_h_supported(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3]))
                 and self.ctx.lib.vido_conv3x3_h_workgroups(int(x.shape[0]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3])) >= (1 if int(w.shape[0]) == 64 else _CONV3X3_H_MIN_WGS)):
             # (64-channel layers: the direct kernel wins at every size — 128 -> 64 on 30 x 40: 18 us against the K-split Winograd form's 26; profiles/r6/conv3x3_h_direct.txt)
-            key = (w.data_ptr(), w._version, str(x.device))
-            if getattr(conv, "_c3h_key", None) != key:
-                conv._c3h_w = pack_conv3x3_h(w).to(x.device); conv._c3h_key = key
-            return self.conv3x3_h_bias_act(x.contiguous(), conv._c3h_w, b, int(w.shape[0]), slope, n_live)
+            wp = cached_pack(conv, "_c3h_w", w, x.device, (), lambda: pack_conv3x3_h(w).to(x.device))
+            return self.conv3x3_h_bias_act(x.contiguous(), wp, b, int(w.shape[0]), slope, n_live)
         form = self.wino3x3_form(x.shape[0], w.shape[1], w.shape[0], x.shape[2], x.shape[3])
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(conv, "_wino_key", None) != key:
-            conv._wino_u = {}; conv._wino_key = key                          # per form: a layer shared by several map sizes (the RPN head over P2-P6) is launched in both
-        if form not in conv._wino_u:
-            conv._wino_u[form] = pack_wino3x3(w, form).to(x.device)
-        return self.wino3x3_bias_act(x.contiguous(), conv._wino_u[form], b, int(w.shape[0]), slope, form)
+        u = cached_pack(conv, "_wino_u", w, x.device, (), dict)                # per form: a layer shared by several map sizes (the RPN head over P2-P6) is launched in both
+        if form not in u:
+            u[form] = pack_wino3x3(w, form).to(x.device)
+        return self.wino3x3_bias_act(x.contiguous(), u[form], b, int(w.shape[0]), slope, form)
 
     def conv3x3_h_bias_act(self, x, w_packed, bias, cout, slope, n_live=None):
         """leaky_relu(conv2d(x, w, stride 1, padding 1) + bias, slope) as one direct split-fp16 launch (csrc/conv3x3h.hip); w_packed = pack_conv3x3_h(w).
@@ -470,10 +443,8 @@ class HipOps:
         N, cin, H, W = x.shape
         assert w_packed.dtype == torch.int16 and w_packed.numel() == 2 * cout * ((cin + 15) // 16 * 16 * 9 + 1), "conv3x3_h: weight not packed by pack_conv3x3_h for this layer"
         out = torch.empty((N, cout, H, W), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * N * cout * cin * 9 * H * W
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_conv3x3_h_bias_act_n(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                                               C.c_void_p(out.data_ptr()), int(N), int(cin), int(cout), int(H), int(W), C.c_float(slope), self._live_ptr(n_live)))
+        self._count_flops(2.0 * N * cout * cin * 9 * H * W)
+        self._call(self.ctx.lib.vido_conv3x3_h_bias_act_n, x.data_ptr(), w_packed.data_ptr(), _p(bias), out.data_ptr(), int(N), int(cin), int(cout), int(H), int(W), slope, self._live_ptr(n_live))
         return out
 
     def conv3x3_h_live_form(self, n, cout, h, w, live):
@@ -492,10 +463,8 @@ class HipOps:
             return None
         assert w_packed.dtype == torch.int16 and w_packed.numel() == 2 * outs * (k + 1), "fc_h: weight not packed (pack_conv1x1(w[:, :, None, None], 3))"
         part = torch.empty((S, rows, outs), device=x.device, dtype=torch.float32); y = torch.empty((rows, outs), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * rows * k * outs
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_fc_h(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(w_packed.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                               C.c_void_p(part.data_ptr()), C.c_void_p(y.data_ptr()), rows, k, int(outs), C.c_float(slope)))
+        self._count_flops(2.0 * rows * k * outs)
+        self._call(self.ctx.lib.vido_fc_h, x.data_ptr(), w_packed.data_ptr(), _p(bias), part.data_ptr(), y.data_ptr(), rows, k, int(outs), slope)
         return y
 
     def fc_h_linear(self, lin, x, slope=1.0):
@@ -504,10 +473,8 @@ class HipOps:
         w = lin.weight
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or os.environ.get("VIDO_NO_FC_H") or self._range_safe or int(self.ctx.lib.vido_fc_h_splitk(int(x.shape[0]), int(w.shape[1]), int(w.shape[0]))) <= 0:
             return None
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(lin, "_fch_key", None) != key:
-            lin._fch_w = pack_conv1x1(w.detach().reshape(int(w.shape[0]), int(w.shape[1]), 1, 1), 3).to(x.device); lin._fch_key = key
-        return self.fc_h(x.contiguous(), lin._fch_w, lin.bias, int(w.shape[0]), slope)
+        wp = cached_pack(lin, "_fch_w", w, x.device, (), lambda: pack_conv1x1(w.detach().reshape(int(w.shape[0]), int(w.shape[1]), 1, 1), 3).to(x.device))
+        return self.fc_h(x.contiguous(), wp, lin.bias, int(w.shape[0]), slope)
 
     def conv_direct_conv(self, conv, x, slope):
         """The convolution `conv` (nn.Conv2d: groups 1, dilation 1, zero padding, a k x k of csrc/convdirect.hip) + bias + activation as ONE direct implicit-GEMM launch on
@@ -524,16 +491,11 @@ class HipOps:
         Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
         if 4 * N * cout * Ho * Wo >= 1 << 30:
             return None
-        key = (w.data_ptr(), w._version, str(x.device))
-        if getattr(conv, "_cd_key", None) != key:
-            conv._cd_w = pack_conv_direct(w).to(x.device); conv._cd_key = key
+        wp = cached_pack(conv, "_cd_w", w, x.device, (), lambda: pack_conv_direct(w).to(x.device))
         x = x.contiguous()
         out = torch.empty((N, cout, Ho, Wo), device=x.device, dtype=torch.float32)
-        self.gconv_flops = getattr(self, "gconv_flops", 0.0) + 2.0 * N * cout * cin * kh * kw * Ho * Wo
-        self._adopt_stream()
-        b = conv.bias
-        self.ctx._check(self.ctx.lib.vido_conv_direct_bias_act(self.ctx.h, C.c_void_p(x.data_ptr()), C.c_void_p(conv._cd_w.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
-                                                               C.c_void_p(out.data_ptr()), int(N), int(cin), cout, int(H), int(W), kh, kw, sh, sw, ph, pw, C.c_float(slope)))
+        self._count_flops(2.0 * N * cout * cin * kh * kw * Ho * Wo)
+        self._call(self.ctx.lib.vido_conv_direct_bias_act, x.data_ptr(), wp.data_ptr(), _p(conv.bias), out.data_ptr(), int(N), int(cin), cout, int(H), int(W), kh, kw, sh, sw, ph, pw, slope)
         return out
 
     def lfn_reg_front(self, im1, im2, flow, scale, feat):
@@ -543,9 +505,7 @@ class HipOps:
         B, Cc, H, W = im1.shape
         out = torch.empty((B, 3 + feat.shape[1], H, W), device=im1.device, dtype=torch.float32)
         mean = flow.flatten(2).mean(2).contiguous()
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_lfn_reg_front(self.ctx.h, C.c_void_p(im1.data_ptr()), C.c_void_p(im2.data_ptr()), C.c_void_p(flow.data_ptr()), C.c_void_p(mean.data_ptr()),
-                                                        C.c_float(scale), B, Cc, H, W, C.c_void_p(out.data_ptr()), out.shape[1]))
+        self._call(self.ctx.lib.vido_lfn_reg_front, im1.data_ptr(), im2.data_ptr(), flow.data_ptr(), mean.data_ptr(), scale, B, Cc, H, W, out.data_ptr(), out.shape[1])
         out[:, 3:] = feat
         return out
 
@@ -555,9 +515,8 @@ class HipOps:
         B, nd, H, W = dist.shape
         assert nd == k * k
         out = torch.empty((B, 2, H, W), device=dist.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_lfn_reg_tail(self.ctx.h, C.c_void_p(dist.data_ptr()), C.c_void_p(flow.data_ptr()), C.c_void_p(scale_x.weight.data_ptr()), C.c_void_p(scale_x.bias.data_ptr()),
-                                                       C.c_void_p(scale_y.weight.data_ptr()), C.c_void_p(scale_y.bias.data_ptr()), B, int(k), H, W, C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_lfn_reg_tail, dist.data_ptr(), flow.data_ptr(), scale_x.weight.data_ptr(), scale_x.bias.data_ptr(), scale_y.weight.data_ptr(), scale_y.bias.data_ptr(),
+                   B, int(k), H, W, out.data_ptr())
         return out
 
     def roi_align(self, feat, rois, output_size, spatial_scale, sampling_ratio):
@@ -566,9 +525,7 @@ class HipOps:
         feat = feat.contiguous().float(); rois = rois.contiguous().float()
         B, Cc, H, W = feat.shape; ph, pw = output_size
         out = torch.empty((rois.shape[0], Cc, ph, pw), device=feat.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_roi_align(self.ctx.h, C.c_void_p(feat.data_ptr()), B, Cc, H, W, C.c_void_p(rois.data_ptr()), rois.shape[0],
-                                                    C.c_float(spatial_scale), ph, pw, sampling_ratio, C.c_void_p(out.data_ptr()), 1))
+        self._call(self.ctx.lib.vido_roi_align, feat.data_ptr(), B, Cc, H, W, rois.data_ptr(), rois.shape[0], spatial_scale, ph, pw, sampling_ratio, out.data_ptr(), 1)
         return out
 
     def box_decode(self, deltas, boxes, weights):
@@ -577,9 +534,7 @@ class HipOps:
         out = torch.empty_like(deltas)
         if n:
             w = (C.c_float * 4)(*[float(x) for x in weights])
-            self._adopt_stream()
-            self.ctx._check(self.ctx.lib.vido_box_decode(self.ctx.h, C.c_void_p(deltas.data_ptr()), C.c_void_p(boxes.data_ptr()), n, deltas.shape[1] // 4, w,
-                                                         C.c_void_p(out.data_ptr()), 1))
+            self._call(self.ctx.lib.vido_box_decode, deltas.data_ptr(), boxes.data_ptr(), n, deltas.shape[1] // 4, w, out.data_ptr(), 1)
         return out
 
     def nms_grouped(self, boxes, scores, groups, thresh):
@@ -604,9 +559,7 @@ class HipOps:
             return torch.sort(order[flat])[0]
         sb = boxes[order].contiguous().float(); sg = groups[order].to(torch.int32).contiguous()
         keep = torch.empty(n, device=boxes.device, dtype=torch.int32); cnt = torch.zeros(1, device=boxes.device, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_nms_grouped(self.ctx.h, C.c_void_p(sb.data_ptr()), None, C.c_void_p(sg.data_ptr()), n, C.c_float(thresh),
-                                                      C.c_void_p(keep.data_ptr()), C.c_void_p(cnt.data_ptr()), 1))
+        self._call(self.ctx.lib.vido_nms_grouped, sb.data_ptr(), None, sg.data_ptr(), n, thresh, keep.data_ptr(), cnt.data_ptr(), 1)
         m = int(cnt.item())
         return torch.sort(order[keep[:m].long()])[0]
 
@@ -619,8 +572,7 @@ class HipOps:
         order = torch.sort(scores, descending=True, stable=True)[1]
         sb = boxes[order].contiguous().float(); n = sb.shape[0]
         keep = torch.empty(max(n, 1), device=boxes.device, dtype=torch.int32); cnt = torch.zeros(1, device=boxes.device, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_nms(self.ctx.h, C.c_void_p(sb.data_ptr()), None, n, C.c_float(thresh), C.c_void_p(keep.data_ptr()), C.c_void_p(cnt.data_ptr()), 1))
+        self._call(self.ctx.lib.vido_nms, sb.data_ptr(), None, n, thresh, keep.data_ptr(), cnt.data_ptr(), 1)
         m = int(cnt.item())
         return torch.sort(order[keep[:m].long()])[0]
 
@@ -630,10 +582,7 @@ class HipOps:
         segment start, ascending, -1 padded; n_keep [n_seg]) — device tensors, no synchronisation."""
         boxes = boxes.contiguous().float(); n_seg = seg_n.shape[0]
         keep = torch.empty((n_seg, max_n), device=boxes.device, dtype=torch.int32); cnt = torch.empty(n_seg, device=boxes.device, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_nms_segments(self.ctx.h, C.c_void_p(boxes.data_ptr()), C.c_void_p(groups.data_ptr()) if groups is not None else None,
-                                                       C.c_void_p(seg_off.data_ptr()), C.c_void_p(seg_n.data_ptr()), n_seg, int(max_n), boxes.shape[0], C.c_float(thresh),
-                                                       C.c_void_p(keep.data_ptr()), C.c_void_p(cnt.data_ptr())))
+        self._call(self.ctx.lib.vido_nms_segments, boxes.data_ptr(), _p(groups), seg_off.data_ptr(), seg_n.data_ptr(), n_seg, int(max_n), boxes.shape[0], thresh, keep.data_ptr(), cnt.data_ptr())
         return keep, cnt
 
     def roi_align_fpn(self, feats, boxes, level, output_size, scales, sampling_ratio):
@@ -645,9 +594,7 @@ class HipOps:
         feats = [f.contiguous().float() for f in feats]; boxes = boxes.contiguous().float(); level = level.to(torch.int32).contiguous()
         fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats]); Hs = (C.c_int * 4)(*[f.shape[2] for f in feats]); Ws = (C.c_int * 4)(*[f.shape[3] for f in feats])
         sc = (C.c_float * 4)(*[float(x) for x in scales])
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_roi_align_fpn(self.ctx.h, fp, Hs, Ws, sc, Cc, C.c_void_p(boxes.data_ptr()), C.c_void_p(level.data_ptr()), n, ph, pw, sampling_ratio,
-                                                        C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_roi_align_fpn, fp, Hs, Ws, sc, Cc, boxes.data_ptr(), level.data_ptr(), n, ph, pw, sampling_ratio, out.data_ptr())
         return out
 
     # ---- detpost.hip: the detector's selection logic as ordered device kernels -----------------------------------------------------------------------------
@@ -661,17 +608,14 @@ class HipOps:
         key = ("anch", L, A)
         if getattr(self, "_anch_key", None) != key:                 # host copy of the cell anchors (module buffers): made once, outside any capture
             self._anch = (C.c_float * (L * A * 4))(*[float(v) for a in cell_anchors for v in a.detach().cpu().reshape(-1).tolist()]); self._anch_key = key
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_rpn_select(self.ctx.h, L, lp, dp, hs, ws, st, self._anch, A, int(K), int(image_wh[0]), int(image_wh[1]),
-                                                     C.c_void_p(boxes.data_ptr()), C.c_void_p(scores.data_ptr()), C.c_void_p(n.data_ptr())))
+        self._call(self.ctx.lib.vido_rpn_select, L, lp, dp, hs, ws, st, self._anch, A, int(K), int(image_wh[0]), int(image_wh[1]), boxes.data_ptr(), scores.data_ptr(), n.data_ptr())
         return boxes, scores, n
 
     def rpn_merge(self, boxes, scores, keep, cnt, K, post_nms_top_n, n_final):
         L = cnt.shape[0]; dev = boxes.device
         ob = torch.empty((n_final, 4), device=dev, dtype=torch.float32); osc = torch.empty((n_final,), device=dev, dtype=torch.float32); nv = torch.empty((1,), device=dev, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_rpn_merge(self.ctx.h, C.c_void_p(boxes.data_ptr()), C.c_void_p(scores.data_ptr()), C.c_void_p(keep.data_ptr()), C.c_void_p(cnt.data_ptr()),
-                                                    L, int(K), int(post_nms_top_n), int(n_final), C.c_void_p(ob.data_ptr()), C.c_void_p(osc.data_ptr()), C.c_void_p(nv.data_ptr())))
+        self._call(self.ctx.lib.vido_rpn_merge, boxes.data_ptr(), scores.data_ptr(), keep.data_ptr(), cnt.data_ptr(), L, int(K), int(post_nms_top_n), int(n_final),
+                   ob.data_ptr(), osc.data_ptr(), nv.data_ptr())
         return ob, osc, nv
 
     def det_class_sort(self, prob, deltas, proposals, objectness, thresh, weights, image_wh):
@@ -679,20 +623,16 @@ class HipOps:
         N, nc = prob.shape; dev = prob.device
         seg = torch.empty(((nc - 1) * N, 4), device=dev, dtype=torch.float32); order = torch.empty((nc - 1, N), device=dev, dtype=torch.int32); seg_n = torch.empty((nc - 1,), device=dev, dtype=torch.int32)
         wv = (C.c_float * 4)(*[float(x) for x in weights])
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_det_class_sort(self.ctx.h, C.c_void_p(prob.data_ptr()), C.c_void_p(deltas.data_ptr()), C.c_void_p(proposals.data_ptr()),
-                                                         C.c_void_p(objectness.data_ptr()) if objectness is not None else None, N, nc, C.c_float(thresh), wv, int(image_wh[0]), int(image_wh[1]),
-                                                         C.c_void_p(seg.data_ptr()), C.c_void_p(order.data_ptr()), C.c_void_p(seg_n.data_ptr())))
+        self._call(self.ctx.lib.vido_det_class_sort, prob.data_ptr(), deltas.data_ptr(), proposals.data_ptr(), _p(objectness), N, nc, thresh, wv, int(image_wh[0]), int(image_wh[1]),
+                   seg.data_ptr(), order.data_ptr(), seg_n.data_ptr())
         return seg, order, seg_n
 
     def det_select(self, prob, seg_boxes, order, keep, cnt, detections_per_img, cap):
         N, nc = prob.shape; dev = prob.device
         ob = torch.empty((cap, 4), device=dev, dtype=torch.float32); osc = torch.empty((cap,), device=dev, dtype=torch.float32); ol = torch.empty((cap,), device=dev, dtype=torch.int64)
         nd = torch.empty((1,), device=dev, dtype=torch.int32); scratch = torch.empty((nc + 3,), device=dev, dtype=torch.int32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_det_select(self.ctx.h, C.c_void_p(prob.data_ptr()), C.c_void_p(seg_boxes.data_ptr()), C.c_void_p(order.data_ptr()), C.c_void_p(keep.data_ptr()),
-                                                     C.c_void_p(cnt.data_ptr()), N, nc, int(detections_per_img), int(cap), C.c_void_p(scratch.data_ptr()),
-                                                     C.c_void_p(ob.data_ptr()), C.c_void_p(osc.data_ptr()), C.c_void_p(ol.data_ptr()), C.c_void_p(nd.data_ptr())))
+        self._call(self.ctx.lib.vido_det_select, prob.data_ptr(), seg_boxes.data_ptr(), order.data_ptr(), keep.data_ptr(), cnt.data_ptr(), N, nc, int(detections_per_img), int(cap),
+                   scratch.data_ptr(), ob.data_ptr(), osc.data_ptr(), ol.data_ptr(), nd.data_ptr())
         return ob, osc, ol, nd
 
     def to_nhwc(self, x):
@@ -700,8 +640,7 @@ class HipOps:
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
         x = x.contiguous(); B, Cc, H, W = x.shape
         out = torch.empty((B, H, W, Cc), device=x.device, dtype=torch.float32)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_nchw_to_nhwc(self.ctx.h, C.c_void_p(x.data_ptr()), B, Cc, H, W, C.c_void_p(out.data_ptr())))
+        self._call(self.ctx.lib.vido_nchw_to_nhwc, x.data_ptr(), B, Cc, H, W, out.data_ptr())
         return out
 
     def roi_align_fpn_nhwc(self, feats_nhwc, boxes, level, output_size, scales, sampling_ratio, n_live=None):
@@ -714,9 +653,7 @@ class HipOps:
         boxes = boxes.contiguous().float(); level = level.to(torch.int32).contiguous()
         fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats_nhwc]); Hs = (C.c_int * 4)(*[f.shape[1] for f in feats_nhwc]); Ws = (C.c_int * 4)(*[f.shape[2] for f in feats_nhwc])
         sc = (C.c_float * 4)(*[float(x) for x in scales])
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_roi_align_fpn_nhwc_n(self.ctx.h, fp, Hs, Ws, sc, Cc, C.c_void_p(boxes.data_ptr()), C.c_void_p(level.data_ptr()), n, ph, pw, sampling_ratio,
-                                                               C.c_void_p(out.data_ptr()), self._live_ptr(n_live)))
+        self._call(self.ctx.lib.vido_roi_align_fpn_nhwc_n, fp, Hs, Ws, sc, Cc, boxes.data_ptr(), level.data_ptr(), n, ph, pw, sampling_ratio, out.data_ptr(), self._live_ptr(n_live))
         return out
 
     def mask_label_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, n_live=None):
@@ -725,10 +662,8 @@ class HipOps:
         out = torch.empty((H, W), device=masks.device, dtype=torch.uint8)
         n = masks.shape[0]
         masks = masks.contiguous().float(); boxes = boxes.contiguous().float(); labels = labels.contiguous().to(torch.int64)
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_label_image_n(self.ctx.h, C.c_void_p(masks.data_ptr()) if n else None, C.c_void_p(boxes.data_ptr()) if n else None,
-                                                             C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
-                                                             C.c_void_p(out.data_ptr()), self._live_ptr(n_live)))
+        self._call(self.ctx.lib.vido_mask_label_image_n, masks.data_ptr() if n else None, boxes.data_ptr() if n else None, labels.data_ptr() if n else None, n, masks.shape[-1] if n else 28,
+                   padding, thresh, H, W, out.data_ptr(), self._live_ptr(n_live))
         return out
 
     def mask_propagate(self, mask, flow, depth=None, out=None, stats=None):
@@ -766,9 +701,7 @@ class HipOps:
             bad("out aliases mask")
         if stats is not None and stats.numel() < 3:
             bad("stats needs 3 elements")
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_propagate(self.ctx.h, C.c_void_p(mask.data_ptr()), C.c_void_p(flow.data_ptr()), C.c_void_p(depth.data_ptr()) if depth is not None else None,
-                                                         H, W, C.c_void_p(out.data_ptr()), C.c_void_p(stats.data_ptr()) if stats is not None else None))
+        self._call(self.ctx.lib.vido_mask_propagate, mask.data_ptr(), flow.data_ptr(), _p(depth), H, W, out.data_ptr(), _p(stats))
         return out
 
     def dis_flow(self, prev, cur, out=None, q8=None, stats=None, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0):
@@ -803,10 +736,8 @@ class HipOps:
                 bad("%s must be [%d, %d, 2], got %s" % (name, H, W, tuple(t.shape)))
         if stats is not None and stats.numel() < 4:
             bad("stats needs 4 elements")
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_dis_flow(self.ctx.h, C.c_void_p(prev.data_ptr()), C.c_void_p(cur.data_ptr()), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters),
-                                                   int(max_shift_q8), int(min_eig), C.c_void_p(out.data_ptr()), C.c_void_p(q8.data_ptr()) if q8 is not None else None,
-                                                   C.c_void_p(stats.data_ptr()) if stats is not None else None, 1))
+        self._call(self.ctx.lib.vido_dis_flow, prev.data_ptr(), cur.data_ptr(), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
+                   out.data_ptr(), _p(q8), _p(stats), 1)
         return out
 
     def flow_consistency(self, fwd_q8, bwd_q8, status=None, out=None, stats=None, alpha_q10=None, beta_q16=None):
@@ -842,10 +773,8 @@ class HipOps:
             bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
         if stats is not None and stats.numel() < 4:
             bad("stats needs 4 elements")
-        self._adopt_stream()
-        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self.ctx._check(self.ctx.lib.vido_flow_consistency(self.ctx.h, vp(fwd_q8), vp(bwd_q8), H, W, int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10),
-                                                           int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), vp(status), vp(out), vp(stats), 1))
+        self._call(self.ctx.lib.vido_flow_consistency, _p(fwd_q8), _p(bwd_q8), H, W, int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10),
+                   int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), _p(status), _p(out), _p(stats), 1)
         return out
 
     def dis_flow_pair(self, prev, cur, out=None, fwd_q8=None, bwd_q8=None, status=None, stats=None, coarsest=4, iters=6, max_shift_q8=1024, min_eig=0, rgb_order=0,
@@ -884,11 +813,8 @@ class HipOps:
             bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
         if stats is not None and stats.numel() < 12:
             bad("stats needs 12 elements")
-        self._adopt_stream()
-        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self.ctx._check(self.ctx.lib.vido_dis_flow_pair(self.ctx.h, vp(prev), vp(cur), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
-                                                        int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10), int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16),
-                                                        vp(out), vp(fwd_q8), vp(bwd_q8), vp(status), vp(stats), 1))
+        self._call(self.ctx.lib.vido_dis_flow_pair, _p(prev), _p(cur), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
+                   int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10), int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), _p(out), _p(fwd_q8), _p(bwd_q8), _p(status), _p(stats), 1)
         return out
 
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
@@ -939,9 +865,7 @@ class HipOps:
             bad("lut needs 256 elements")
         if stats is not None and stats.numel() < 4:
             bad("stats needs 4 elements")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_associate(self.ctx.h, ptr(prev), ptr(cur), H, W, ptr(classes), n, int(hold), ptr(state), ptr(out), ptr(lut), ptr(stats)))
+        self._call(self.ctx.lib.vido_mask_associate, _p(prev), _p(cur), H, W, _p(classes), n, int(hold), _p(state), _p(out), _p(lut), _p(stats))
         return out
 
     def mask_components(self, mask, connectivity=8, min_area=1, id_base=0, cap=127, out=None, classes=None, areas=None, stats=None):
@@ -982,10 +906,7 @@ class HipOps:
                 bad("%s holds %d elements, cap = %d" % (name, t.numel(), cap))
         if stats is not None and stats.numel() < 4:
             bad("stats needs 4 elements")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_components(self.ctx.h, ptr(mask), H, W, int(connectivity), int(min_area), int(id_base), cap, ptr(out), ptr(classes), ptr(areas),
-                                                          ptr(stats)))
+        self._call(self.ctx.lib.vido_mask_components, _p(mask), H, W, int(connectivity), int(min_area), int(id_base), cap, _p(out), _p(classes), _p(areas), _p(stats))
         return out
 
     def mask_instance_image(self, masks, boxes, labels, H, W, thresh=0.5, padding=1, id_base=None, areas=False):
@@ -1003,11 +924,8 @@ class HipOps:
         if id_base is not None:
             assert id_base.is_cuda and id_base.dtype == torch.int32 and id_base.numel() == 1
         area = torch.empty((n,), device=masks.device, dtype=torch.int32) if areas else None
-        self._adopt_stream()
-        self.ctx._check(self.ctx.lib.vido_mask_instance_image(self.ctx.h, C.c_void_p(masks.data_ptr()) if n else None, C.c_void_p(boxes.data_ptr()) if n else None,
-                                                              C.c_void_p(labels.data_ptr()) if n else None, n, masks.shape[-1] if n else 28, padding, C.c_float(thresh), H, W,
-                                                              C.c_void_p(id_base.data_ptr()) if id_base is not None else None, C.c_void_p(out.data_ptr()),
-                                                              C.c_void_p(area.data_ptr()) if areas and n else None))
+        self._call(self.ctx.lib.vido_mask_instance_image, masks.data_ptr() if n else None, boxes.data_ptr() if n else None, labels.data_ptr() if n else None, n, masks.shape[-1] if n else 28,
+                   padding, thresh, H, W, _p(id_base), out.data_ptr(), area.data_ptr() if areas and n else None)
         return (out, area) if areas else out
 
 
@@ -1260,14 +1178,13 @@ def pack_conv_direct(w):
     import numpy as np
     from ..host import load_library
     lib = load_library()
-    lib.vido_conv_direct_packed_floats.restype = C.c_longlong
     cout, cin, kh, kw = (int(v) for v in w.shape)
     wh = np.ascontiguousarray(w.detach().to("cpu", torch.float32).numpy())
     n = int(lib.vido_conv_direct_packed_floats(cin, cout, kh, kw))
     if n <= 0:
         raise RuntimeError("vido_conv_direct_pack: no kernel for %d x %d taps" % (kh, kw))
     out = np.empty(n, np.float32)
-    rc = lib.vido_conv_direct_pack(C.c_void_p(wh.ctypes.data), cin, cout, kh, kw, C.c_void_p(out.ctypes.data))
+    rc = lib.vido_conv_direct_pack(wh.ctypes.data, cin, cout, kh, kw, out.ctypes.data)
     if rc != 0:
         raise RuntimeError("vido_conv_direct_pack: %d" % rc)
     return torch.from_numpy(out)
@@ -1280,13 +1197,12 @@ def pack_wino3x3(w, form=0):
     import numpy as np
     from ..host import load_library
     lib = load_library()
-    lib.vido_wino3x3_packed_floats_form.restype = C.c_longlong
-    cout, cin = int(w.shape[0]), int(w.shape[1])
+    cout, cin =int(w.shape[0]), int(w.shape[1])
     assert tuple(w.shape[2:]) == (3, 3) and form in (0, 1, 2)
     wh = np.ascontiguousarray(w.detach().to("cpu", torch.float32).numpy())
     n = int(lib.vido_wino3x3_packed_floats_form(cin, cout, int(form)))
     out = np.empty(n, np.float32)
-    rc = lib.vido_wino3x3_pack_form(C.c_void_p(wh.ctypes.data), cin, cout, int(form), C.c_void_p(out.ctypes.data))
+    rc = lib.vido_wino3x3_pack_form(wh.ctypes.data, cin, cout, int(form), out.ctypes.data)
     if rc != 0:
         raise RuntimeError("vido_wino3x3_pack_form: %d" % rc)
     kc = 8 if (((cout + 63) // 64) * 64 - cout) < 32 and form == 0 else 4

@@ -27,43 +27,11 @@ class SystemStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
-def _bind(lib):
-    if getattr(lib, "_vido_system_bound", False):
-        return lib
-    lib.vido_system_create.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-    lib.vido_system_destroy.argtypes = [C.c_void_p]
-    lib.vido_system_last_error.restype = C.c_char_p
-    lib.vido_system_last_error.argtypes = [C.c_void_p]
-    lib.vido_system_track_rgbd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
-    lib.vido_system_track_rgbd_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
-    lib.vido_system_get_stats.argtypes = [C.c_void_p, C.POINTER(SystemStats)]
-    lib.vido_system_save_results.argtypes = [C.c_void_p, C.c_char_p]
-    lib.vido_system_context.restype = C.c_void_p
-    lib.vido_system_context.argtypes = [C.c_void_p]
-    lib.vido_system_set_depth_noise_seed.argtypes = [C.c_void_p, C.c_uint]
-    lib.vido_system_set_zero_copy_maps.argtypes = [C.c_void_p, C.c_int]
-    lib.vido_system_prefetch_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.vido_system_get_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_system_mask_split_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    lib.vido_system_get_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.vido_system_get_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_system_get_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.vido_system_get_object_verify_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_system_get_object_verify_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.vido_system_get_object_recover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_system_get_object_recover_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.vido_system_get_object_refine_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.vido_system_get_object_refine_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib._vido_system_bound = True
-    return lib
-
-
 class System:
     MONOCULAR, STEREO, RGBD, IMU_RGBD = 0, 1, 2, 3      # System::eSensor (System.h:76-81)
 
     def __init__(self):
-        self.lib = _bind(load_library())
+        self.lib = load_library()
         self.h = None
         self._keep = None                                 # the arrays of the last call (the tracker holds shallow references to them)
 
@@ -106,7 +74,7 @@ class System:
     def PrefetchImageDevice(self, im_dev, channels, width, height, image_ready_event=None):
         """Put the ORB extraction of the next TrackRGBDDevice call's image on the tracker's stream now (it needs nothing but the image): call it, on the thread that tracks,
         while still waiting for the frame's networks; the track call for the same pointer then only collects (vido_system_prefetch_image_device)."""
-        rc = self.lib.vido_system_prefetch_image_device(self.h, C.c_void_p(im_dev), int(channels), int(width), int(height), C.c_void_p(image_ready_event) if image_ready_event else None)
+        rc = self.lib.vido_system_prefetch_image_device(self.h, im_dev, int(channels), int(width), int(height), image_ready_event)
         if rc != 0:
             raise VidoError(rc, self.lib.vido_system_last_error(self.h).decode())
 
@@ -125,8 +93,8 @@ class System:
         if self.h is None:
             raise VidoError(-1, "System.TrackRGBDDevice before Init")
         T = np.empty((4, 4), np.float32)
-        rc = self.lib.vido_system_track_rgbd_device(self.h, C.c_void_p(int(im_dev)), int(channels), int(width), int(height), C.c_void_p(int(depth_dev)), C.c_void_p(int(flow_dev)),
-                                                    C.c_void_p(int(mask_dev)) if mask_dev else None, C.c_void_p(int(ready_event)) if ready_event else None, float(timestamp), int(nImage), T.ctypes.data)
+        rc = self.lib.vido_system_track_rgbd_device(self.h, int(im_dev), int(channels), int(width), int(height), int(depth_dev), int(flow_dev), int(mask_dev or 0), int(ready_event or 0),
+                                                    float(timestamp), int(nImage), T.ctypes.data)
         if rc != VIDO_OK:
             raise VidoError(rc, self.lib.vido_system_last_error(self.h).decode())
         return T
