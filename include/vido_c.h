@@ -547,13 +547,16 @@ int vido_deconv4s2_depthwise(vido_ctx* ctx, const float* x, const float* weight,
  * the way in, so that the 1x1 convolution in front needs no pass of its own over its output.
  * vido_gconv3x3_supported: 1 when a kernel exists for the shape (8, 16 or a multiple of 32 channels per group and a row band that fits LDS); otherwise the call returns
  * VIDO_E_INVALID and the caller keeps the library convolution. */
-/* 1x1 convolution (stride 1, batch 1) + bias + residual + leaky-ReLU as one fp32 matrix-core GEMM (csrc/conv1x1.hip): conv1 / conv3 / the stride-1 shortcut of
+/* 1x1 convolution (stride 1, batch 1) + bias + residual + leaky-ReLU as one matrix-core GEMM (csrc/conv1x1.hip): conv1 / conv3 / the stride-1 shortcut of
  * BottleneckWithFixedBatchNorm with their folded FrozenBatchNorm2d (maskrcnn_benchmark/modeling/backbone/resnet.py:300-372, layers/batch_norm.py:19-31).  x [cin][hw],
  * y / residual [cout][hw], f32 DEVICE, 16-byte aligned, y != x; bias [cout] or NULL; residual NULL = none; w_packed: [cout][cin] in operand order
- * (vido_slam_amd/nets/ops.py::pack_conv1x1).  slope: 0 = ReLU, 1 = none.  vido_conv1x1_supported: cout % 128 == 0, cin % 32 == 0, hw >= 128. */
+ * (vido_slam_amd/nets/ops.py::pack_conv1x1) and `layout` the number of that order: 0 = fp32 [co / 32][k / 8][32 (k & 1) + co % 32][(k % 8) / 2] (4 cin cout bytes: the fp32
+ * matrix instruction), 2 = split-bf16 (6 cin cout bytes), 3 = split-fp16 (4 cin cout + 4 cout bytes), both described at vido_conv1x1_set_arith.  The launch runs the kernel
+ * of the layout it is given and reads that many bytes, whatever the arithmetic setting is by then; any other `layout` returns VIDO_E_INVALID.
+ * slope: 0 = ReLU, 1 = none.  vido_conv1x1_supported: cout % 128 == 0, cin % 32 == 0, hw >= 128. */
 int vido_conv1x1_supported(int cin, int cout, int hw);
-/* the weight packing vido_conv1x1_bias_act / _up2_act expect for a shape: 0 = [co / 32][k / 8][32 (k & 1) + co % 32][(k % 8) / 2] (128 x 128 tiles),
- * 1 = [co / 16][k / 16][16 (k & 3) + co % 16][(k % 16) / 4] (128 x 112 tiles: fewer idle CUs in the last round of workgroups) */
+/* the weight packing to MAKE for a shape under the current arithmetic setting (vido_conv1x1_set_arith): 3, 2 or 0.  A recommendation to the packer: a launch is told the
+ * layout of the weight it is handed and never asks this function. */
 int vido_conv1x1_layout(int cin, int cout, int hw);
 /* Arithmetic of the 1x1 GEMM (round 6): fp32-equivalent results from the 16-bit matrix instructions (error against float64 not above the fp32 instruction's:
  * tests/test_maskrcnn_gpu.py).
@@ -564,9 +567,10 @@ int vido_conv1x1_layout(int cin, int cout, int hw);
  *       that meets |x| >= 65504, an infinity or a NaN raises vido_conv1x1_range_flag (its outputs are not valid then).
  *   2 = split-bf16: three bf16 planes, the six plane products with i + j <= 2 on v_mfma_f32_32x32x16_bf16; fp32's range, twice the matrix work; layout 2 =
  *       [co / 32][k / 16][plane 3][32 ((k % 16) / 8) + co % 32][k % 8] bf16 (6 bytes per weight).
- *   1 = the fp32 matrix instruction (layouts 0 / 1 above).
- * Also selected by VIDO_CONV1X1_ARITH = f16x2 | bf16x3 | f32 in the environment.  Returns the previous setting; process-wide — set it before weights are packed (a packed
- * weight carries its layout, a mismatch is refused by the caller's shape check). */
+ *   1 = the fp32 matrix instruction (layout 0 above).
+ * Also selected by VIDO_CONV1X1_ARITH = f16x2 | bf16x3 | f32 in the environment.  Returns the previous setting; process-wide.  The setting selects what vido_conv1x1_layout
+ * recommends (and with it whether vido_deconv2x2_supported answers 1) and nothing else: weights already packed keep running in the arithmetic they were packed for,
+ * because every launch is handed its weight's layout. */
 int vido_conv1x1_set_arith(int arith);
 /* the current setting (0 / 1 / 2) */
 int vido_conv1x1_get_arith(void);
@@ -578,7 +582,7 @@ int vido_conv1x1_range_flag(vido_ctx* ctx, int reset);
  * the latch, and launches after it raise the flag afresh: a frame's latch names that frame even while the next frame's networks are already queued.  dst is not cleared:
  * the caller zeroes it before the launches it is to cover.  Capturable. */
 int vido_range_latch(vido_ctx* ctx, unsigned* dst);
-int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope);
+int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope, int layout);
 /* 2 x 2 stride-2 transposed convolution + bias + leaky-ReLU of a batch as one split-fp16 GEMM with a scatter epilogue (the mask head's conv5_mask,
  * roi_heads/mask_head/roi_mask_predictors.py:17-31): x [n][cin][h][w] -> y [n][cout][2 h][2 w]; w_packed: pack_conv1x1 layout 3 of [(2 a + b) cout + co][ci] = w[ci][co][a][b]
  * (vido_slam_amd/nets/ops.py::pack_deconv2x2).  vido_deconv2x2_supported: cout % 128 == 0, cin % 32 == 0, (h w) % 4 == 0, n h w >= 128, split-fp16 arithmetic selected. */
@@ -587,7 +591,7 @@ int vido_deconv2x2_bias_act(vido_ctx* ctx, const float* x, const float* w_packed
 /* ... of the first *n_live images only (see vido_mask_logit_select_n): a tile of columns that straddles the count reads zeros for the images behind it and stores nothing there. */
 int vido_deconv2x2_bias_act_n(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live);
 /* ... with the residual at half the resolution [cout][h/2][w/2], added nearest-upsampled: the FPN's lateral convolution + top-down sum (backbone/fpn.py:55-66); h, w even */
-int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual_half, float* y, int cin, int cout, int h, int w, float slope);
+int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual_half, float* y, int cin, int cout, int h, int w, float slope, int layout);
 
 /* k x k convolution (k = 3, 5, 7; stride 1, padding k / 2) to TWO output channels + bias + residual for one image (csrc/convsmall.hip): the last layer of LiteFlowNet's
  * matching / sub-pixel heads with the `flow + netMain(...)` behind it (flow_net/src/layers.py:152-160, 191-199).  x [cin][h][w], w [2][cin][k][k], bias [2] or NULL,

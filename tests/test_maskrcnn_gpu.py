@@ -243,43 +243,8 @@ def test_bottleneck_with_matrix_core_conv2_equals_library_path(vido, ctx):
     assert float((y_fast - y_lib).abs().max()) < 1e-4 * max(1.0, float(y_lib.abs().max()))
 
 
-_FORCED_C1 = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-import vido_slam_amd as V
-from vido_slam_amd.nets.ops import HipOps, pack_conv1x1
-cin, cout, H, W, layout = (int(a) for a in sys.argv[2:7])
-ctx = V.Context(width=640, height=480, max_batch=1); ops = HipOps(ctx)
-assert ops.conv1x1_layout(cin, cout, H * W) == layout
-g = torch.Generator().manual_seed(cin * 7 + H)
-x = torch.randn(1, cin, H, W, generator=g); w = torch.randn(cout, cin, 1, 1, generator=g) * (1.0 / cin ** 0.5); b = torch.randn(cout, generator=g); r = torch.randn(1, cout, H, W, generator=g)
-wp = pack_conv1x1(w, layout).cuda()
-ref0 = torch.nn.functional.conv2d(x.double(), w.double())
-for bias, res, slope in ((None, None, 1.0), (b, r, 0.0), (b, r, 0.1)):
-    y = ops.conv1x1_bias_act(x.cuda(), wp, bias.cuda() if bias is not None else None, res.cuda() if res is not None else None, slope).cpu()
-    ref = ref0 + (bias.double()[None, :, None, None] if bias is not None else 0.0) + (res.double() if res is not None else 0.0)
-    ref = torch.nn.functional.leaky_relu(ref, slope)
-    err = float((y.double() - ref).abs().max())
-    assert err < 2e-5 * max(1.0, float(ref.abs().max())), (cin, cout, H, W, slope, err)
-if H % 2 == 0 and W % 2 == 0:
-    rh = torch.randn(1, cout, H // 2, W // 2, generator=g)
-    y = ops.conv1x1_bias_act(x.cuda(), wp, b.cuda(), None, 1.0, residual_up2=rh.cuda()).cpu()
-    ref = ref0 + b.double()[None, :, None, None] + torch.nn.functional.interpolate(rh.double(), scale_factor=2, mode="nearest")
-    assert float((y.double() - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
-print("forced ok")
-"""
-
-
-def _run_forced_conv1x1(cin, cout, H, W, layout):
-    import subprocess, sys, os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VIDO_CONV1X1_TN="112" if layout == 1 else "128")
-    out = subprocess.run([sys.executable, "-c", _FORCED_C1, root, str(cin), str(cout), str(H), str(W), str(layout)], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "forced ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("layout", [None, 0, 1])      # None: the tile form the library picks for the shape; 0 / 1: forced 128 x 128 / 128 x 112 tiles (VIDO_CONV1X1_TN)
+@pytest.mark.parametrize("layout", [None])      # None: the layout the library recommends for the shape (the forced tile forms are gone; the parameter keeps the test ids)
 @pytest.mark.parametrize("cin,cout,H,W", [(64, 256, 40, 68), (256, 256, 50, 68), (256, 128, 37, 52), (1024, 1024, 10, 34), (512, 512, 25, 36), (32, 128, 12, 11), (2048, 256, 16, 16),
                                             (2048, 2048, 25, 34), (256, 128, 13, 11), (96, 128, 9, 15),      # the last three: H*W not a multiple of 4 (layer4: 850 positions)
                                             (256, 256, 200, 272), (1024, 1024, 50, 68), (512, 512, 100, 136)])      # the bench's own bottleneck shapes (layer1 / layer3 / layer2)
@@ -291,12 +256,7 @@ def test_conv1x1_matrix_core_gemm_equals_conv2d(vido, ctx, cin, cout, H, W, layo
     g = torch.Generator().manual_seed(cin * 7 + H)
     x = torch.randn(1, cin, H, W, generator=g); w = torch.randn(cout, cin, 1, 1, generator=g) * (1.0 / cin ** 0.5); b = torch.randn(cout, generator=g); r = torch.randn(1, cout, H, W, generator=g)
     assert ops.conv1x1_supported(cin, cout, H * W)
-    if layout is not None:
-        # the form is read once per process from VIDO_CONV1X1_TN: a forced form runs in a child process (below); here only the library's own choice
-        if cin % 64 and layout == 1:
-            pytest.skip("the 112-wide form needs input channels in multiples of 64")
-        _run_forced_conv1x1(cin, cout, H, W, layout); return
-    lay = ops.conv1x1_layout(cin, cout, H * W)
+    lay = ops.conv1x1_layout(cin, cout, H * W) if layout is None else layout
     wp = pack_conv1x1(w, lay).cuda()
     ref0 = torch.nn.functional.conv2d(x.double(), w.double())
     for bias, res, slope in ((None, None, 1.0), (b, None, 0.0), (b, r, 0.0), (b, r, 0.1), (None, r, 1.0)):
@@ -316,7 +276,7 @@ _C1_SHAPES = [(64, 256, 40, 68), (256, 256, 50, 68), (256, 128, 37, 52), (1024, 
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", [0, 1, 2, 3])      # VIDO_CONV1X1_B3_FORM: 0 = the form the library picks by shape; 1 / 2 / 3 = <1, 6> / <2, 4> / <1, 4> forced (a child process)
+@pytest.mark.parametrize("form", [0, 2, 3])      # VIDO_CONV1X1_B3_FORM: 0 = the form the library picks by shape; 2 / 3 = the two-group / the one-group ring forced (a child process)
 def test_split_bf16_conv1x1_is_no_less_accurate_than_the_fp32_instruction(vido, ctx, form):
     """The admissibility rule of the split-bf16 form: on EVERY shape of the 1x1 tests the max-abs error of k_conv1x1_b3 against float64 conv2d must
     not exceed 1.5 x the error of the fp32-matrix-instruction kernel on the same inputs — otherwise it would be narrower arithmetic than the reference's fp32 layers.
@@ -384,6 +344,70 @@ def test_split_fp16_conv1x1_over_its_range_and_past_it(vido, ctx):
         assert torch.isfinite(y).all() and float((y.double() - ref).abs().max()) < 1e-5 * float(ref.abs().max())
     finally:
         ops.conv1x1_set_arith(0)
+
+
+@pytest.mark.gpu
+def test_conv1x1_pack_runs_as_packed_whatever_the_setting(vido, ctx):
+    """The layout is an argument of the launch: a weight packed in any of the three layouts gives the SAME bits under every arithmetic setting (conv1x1_set_arith only
+    selects what conv1x1_layout recommends), each within the bound of test_conv1x1_matrix_core_gemm_equals_conv2d of float64 conv2d; the range flag stays down.
+    135 positions: a full 128-tile and a partial one, not a multiple of 4; 96 channels: the fp32 form's 32-channel chunk and the one-group ring; 512 with 2 tiles: the
+    two-group ring; 10 x 14: the half-resolution residual."""
+    from vido_slam_amd.nets.ops import HipOps, pack_conv1x1
+    F = torch.nn.functional
+    ops = HipOps(ctx)
+    try:
+        for cin, cout, H, W, up2 in ((96, 128, 9, 15, False), (512, 128, 9, 15, False), (96, 128, 10, 14, True)):
+            g = torch.Generator().manual_seed(cin * 7 + H)
+            x = torch.randn(1, cin, H, W, generator=g); w = torch.randn(cout, cin, 1, 1, generator=g) * (1.0 / cin ** 0.5); b = torch.randn(cout, generator=g)
+            r = torch.randn(1, cout, H // 2, W // 2, generator=g) if up2 else torch.randn(1, cout, H, W, generator=g)
+            ref = F.conv2d(x.double(), w.double(), b.double()) + (F.interpolate(r.double(), scale_factor=2, mode="nearest") if up2 else r.double())
+            ref = F.leaky_relu(ref, 0.1)
+            xc, bc, rc = x.cuda(), b.cuda(), r.cuda()
+            for layout in (0, 2, 3):
+                wp = pack_conv1x1(w, layout).cuda()
+                ys = []
+                for setting in (0, 1, 2):
+                    ops.conv1x1_set_arith(setting)
+                    ys.append(ops.conv1x1_bias_act(xc, wp, bc, None if up2 else rc, 0.1, residual_up2=rc if up2 else None).cpu())
+                assert torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2]), (cin, cout, H, W, layout)
+                err = float((ys[0].double() - ref).abs().max())
+                assert err < 2e-5 * max(1.0, float(ref.abs().max())), (cin, cout, H, W, layout, err)
+        assert ops.conv1x1_range_flag() == 0
+    finally:
+        ops.conv1x1_set_arith(0)
+
+
+@pytest.mark.gpu
+def test_conv1x1_refuses_a_layout_it_does_not_know_and_a_pack_of_another_shape(vido, ctx):
+    """vido_conv1x1_bias_act / _up2_act with a layout outside {0, 2, 3} return VIDO_E_INVALID with a message that names it and launch nothing; the transposed convolution
+    takes a layout-3 pack only; a layout-3 pack whose element count belongs to another (cin, cout) is refused by the wrapper before any launch."""
+    from vido_slam_amd.nets.ops import HipOps, pack_conv1x1, pack_deconv2x2
+    ops = HipOps(ctx); lib = ops.ctx.lib
+    cin, cout, H, W = 96, 128, 10, 14
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(1, cin, H, W, generator=g).cuda(); w = torch.randn(cout, cin, 1, 1, generator=g)
+    wp = pack_conv1x1(w, 3).cuda(); rh = torch.zeros(1, cout, H // 2, W // 2, device="cuda")
+    y = torch.full((1, cout, H, W), -7.0, device="cuda")
+    for bad in (1, -1, 4):
+        with pytest.raises(vido.VidoError, match="layout %d " % bad) as e:
+            ops._call(lib.vido_conv1x1_bias_act, x.data_ptr(), wp.data_ptr(), None, None, y.data_ptr(), cin, cout, H * W, 1.0, bad)
+        assert e.value.code == -1                                                  # VIDO_E_INVALID
+        with pytest.raises(vido.VidoError, match="layout %d " % bad):
+            ops._call(lib.vido_conv1x1_bias_up2_act, x.data_ptr(), wp.data_ptr(), None, rh.data_ptr(), y.data_ptr(), cin, cout, H, W, 1.0, bad)
+    torch.cuda.synchronize()
+    assert bool((y == -7.0).all())                                                 # nothing ran
+    # the transposed convolution: 64 -> 128 channels on 2 x 8 x 8 maps, handed the fp32 (layout 0) and the split-bf16 pack of its GEMM matrix
+    wt = torch.randn(64, 128, 2, 2, generator=g); xt = torch.randn(2, 64, 8, 8, generator=g).cuda()
+    assert lib.vido_deconv2x2_supported(2, 64, 128, 8, 8)
+    wm = wt.permute(2, 3, 1, 0).reshape(4 * 128, 64, 1, 1)
+    for layout in (0, 2):
+        with pytest.raises(ValueError, match="layout 3"):
+            ops.deconv2x2_bias_act(xt, pack_conv1x1(wm, layout).cuda(), None, 0.0)
+    assert ops.deconv2x2_bias_act(xt, pack_deconv2x2(wt).cuda(), None, 0.0).shape == (2, 128, 16, 16)
+    # a layout-3 pack of 64 -> 128 channels met by 96 input channels: 2 * 128 * 65 elements are no multiple of 2 * 97
+    with pytest.raises(ValueError, match="no pack_conv1x1 weight for 96 input channels"):
+        ops.conv1x1_bias_act(x, pack_conv1x1(torch.randn(128, 64, 1, 1, generator=g), 3).cuda(), None, None, 1.0)
+    assert ops.conv1x1_range_flag() == 0
 
 
 @pytest.mark.gpu

@@ -178,16 +178,6 @@ def test_pack_conv1x1_is_the_operand_order_of_the_kernel():
             co, k = (int(torch.randint(0, n, (1,), generator=g)) for n in (cout, cin))
             assert float(p[co // 32, k // 8, 32 * (k & 1) + co % 32, (k % 8) // 2]) == float(w[co, k, 0, 0])
     assert pack_conv1x1(torch.zeros(64, 32, 1, 1)) is None and pack_conv1x1(torch.zeros(128, 48, 1, 1)) is None and pack_conv1x1(torch.zeros(128, 32, 3, 3)) is None
-    # layout 1 (128 x 112 tiles on v_mfma_f32_16x16x4: lane l supplies A[row l % 16][k l / 16]): element (co, k) is the (k % 16) / 4-th operand that lane 16 * (k & 3) + co % 16
-    # reads for the group of four k-steps k / 16 of the 16-row fragment co / 16
-    for cout, cin in ((128, 64), (256, 128)):
-        w = torch.randn(cout, cin, 1, 1, generator=g)
-        p = pack_conv1x1(w, 1)
-        assert tuple(p.shape) == (cout // 16, cin // 16, 64, 4) and p.is_contiguous()
-        for _ in range(300):
-            co, k = (int(torch.randint(0, n, (1,), generator=g)) for n in (cout, cin))
-            assert float(p[co // 16, k // 16, 16 * (k & 3) + co % 16, (k % 16) // 4]) == float(w[co, k, 0, 0])
-    assert pack_conv1x1(torch.zeros(128, 96, 1, 1), 1) is None
     # layout 2 (the split-bf16 form, v_mfma_f32_32x32x16_bf16: lane l supplies A[row l % 32][k 8 (l / 32) .. + 7]): three bf16 planes whose sum is the weight EXACTLY
     from vido_slam_amd.nets.ops import split_bf16x3
     w = torch.randn(256, 64, 1, 1) * torch.logspace(-6, 3, 64)[None, :, None, None]
@@ -245,24 +235,27 @@ def test_pack_conv3x3_h_is_the_operand_order_of_the_direct_kernel():
     assert tuple(p24.shape) == (2 * 128 * (32 * 9 + 1),) and int((p24[:2 * 128 * 32 * 9].reshape(4, 2, 3, 3, 2, 64, 8)[:, 1, :, :, :, 32:, :] != 0).sum()) == 0
 
 
-def test_conv1x1_tile_form_is_chosen_by_rounds_of_workgroups():
-    """vido_conv1x1_layout (host side of csrc/conv1x1.hip).  Default: 128 x 128 tiles (the form that measured faster on the pipelined headline).  VIDO_CONV1X1_TN=0: 128 x 112
-    tiles where they need fewer (rounds of 256 CUs) x (tile width) — every bottleneck shape of X-101-32x8d at the 800 x 1088 feed (850 tiles of 128 x 128 = 3.3 rounds -> 972
-    of 128 x 112 = 3.8 rounds, each 7 / 8 of the work); 128 x 128 where the 112-wide form would add a round, or when the input channels are not a multiple of 64.  The switch
-    is read once per process: the rule is asked in a child process."""
-    import subprocess, sys
+def test_conv1x1_layout_recommendation_follows_the_arithmetic_setting():
+    """vido_conv1x1_layout (host side of csrc/conv1x1.hip): the packing to make under the arithmetic setting, the same for every shape — without any switch the split-fp16
+    form = layout 3, VIDO_CONV1X1_ARITH=bf16x3 the split-bf16 form = layout 2, VIDO_CONV1X1_ARITH=f32 the fp32 instruction = layout 0.  The variable is read once per process:
+    the rule is asked in a child process.  pack_conv1x1 knows exactly these three layouts."""
+    import subprocess, sys, pytest
     code = ("import sys; sys.path.insert(0, %r); from vido_slam_amd.host import load_library; lib = load_library(); "
             "print([lib.vido_conv1x1_layout(*a) for a in ((256, 256, 200 * 272), (512, 512, 100 * 136), (1024, 1024, 50 * 68), (96, 128, 4096), (256, 256, 128 * 128 * 2))])" % ROOT)
-    # (round 6: without any switch the split-fp16 form = layout 3 takes every shape, VIDO_CONV1X1_ARITH=bf16x3 the split-bf16 form = layout 2; VIDO_CONV1X1_ARITH=f32 or a
-    # forced tile width bring the fp32-instruction forms back)
-    for tn, want in (("0", [1, 1, 1, 0, 0]), ("128", [0, 0, 0, 0, 0]), ("112", [1, 1, 1, 0, 1]), (None, [3, 3, 3, 3, 3]), ("f32", [0, 0, 0, 0, 0]), ("bf16x3", [2, 2, 2, 2, 2])):
-        env = {k: v for k, v in os.environ.items() if k not in ("VIDO_CONV1X1_TN", "VIDO_CONV1X1_ARITH")}
-        if tn in ("f32", "bf16x3"):
-            env["VIDO_CONV1X1_ARITH"] = tn
-        elif tn is not None:
-            env["VIDO_CONV1X1_TN"] = tn
+    for arith, want in ((None, [3, 3, 3, 3, 3]), ("f32", [0, 0, 0, 0, 0]), ("bf16x3", [2, 2, 2, 2, 2])):
+        env = {k: v for k, v in os.environ.items() if k != "VIDO_CONV1X1_ARITH"}
+        if arith is not None:
+            env["VIDO_CONV1X1_ARITH"] = arith
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == str(want), (tn, out.stdout, out.stderr[-500:])
+        assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == str(want), (arith, out.stdout, out.stderr[-500:])
+    from vido_slam_amd.nets.ops import pack_conv1x1, packed_conv1x1_layout
+    w = torch.zeros(128, 64, 1, 1)
+    for bad in (1, 4):
+        with pytest.raises(ValueError):
+            pack_conv1x1(w, bad)
+    assert [packed_conv1x1_layout(pack_conv1x1(w, lay), 64) for lay in (0, 2, 3)] == [(0, 128), (2, 128), (3, 128)]
+    with pytest.raises(ValueError):
+        packed_conv1x1_layout(pack_conv1x1(w, 3), 96)                     # 2 * 128 * 65 elements: no layout-3 pack for 96 input channels
 
 
 def test_fc_h_split_rule_answers_without_a_gpu():

@@ -23,7 +23,7 @@ if has bench; then
 fi
 if has c1; then
   : > $OUT/conv1x1_microbench.txt
-  for tn in 128 112; do echo "== VIDO_CONV1X1_TN=$tn" >> $OUT/conv1x1_microbench.txt; VIDO_CONV1X1_TN=$tn timeout 300 python tools/prof_conv1x1.py 2>&1 | grep " -> " | cut -c1-270 >> $OUT/conv1x1_microbench.txt; done
+  timeout 300 python tools/prof_conv1x1.py 2>&1 | grep " -> " | cut -c1-270 >> $OUT/conv1x1_microbench.txt
 fi
 if has nodet; then VIDO_CALL_PROF=1 timeout 300 python tools/prof_nodet.py 80 2>&1 | grep -v "amdgpu.ids\|Warning\|warn" > $OUT/nodet_call_profile.txt; fi
 export TMPDIR=/tmp; cd /tmp

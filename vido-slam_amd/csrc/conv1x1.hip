@@ -1,23 +1,20 @@
-// 1x1 convolution + bias (+ residual) + activation of the detector's bottlenecks as ONE fp32 matrix-core GEMM launch (gfx950).
+// 1x1 convolution + bias (+ residual) + activation of the detector's bottlenecks as ONE matrix-core GEMM launch (gfx950), in three arithmetics.
 //
 // What it replaces: conv1 / conv3 of BottleneckWithFixedBatchNorm and the FPN's lateral convolutions (maskrcnn_benchmark/modeling/backbone/resnet.py:300-372,
 // backbone/fpn.py) at batch 1: 69 convolutions per frame of X-101-32x8d, 7.1 GFLOP each, which the library runs as rocBLAS GEMMs (MT64x64x16 ... MT128x128x32: 61-77 us
 // per call, 92-116 TFLOP/s, 62-67 % matrix-pipe occupancy) followed — for conv3 — by a separate bias + residual + ReLU pass over the output (33 launches, 0.33 ms).
 //
-// Formulation.  NCHW at batch 1 IS the GEMM  Out[co][q] = sum_k W[co][k] In[k][q]  with the flattened position q contiguous: M = Cout, N = H*W, K = Cin.
-//   * v_mfma_f32_32x32x2f32 with A = 32 output channels x 2 input channels, B = the same 2 channels x 32 positions: the D layout then keeps, in one register, one output
-//     channel of 32 consecutive positions per half wave — stores (and the residual reads) are whole 128-byte lines.
-//   * workgroup = 4 waves (one per SIMD) = 128 output channels x 128 positions, a wave 64 x 64 (four tiles, 64 accumulator registers).
-//   * The loop carries NO vector-ALU instruction: beside the fp32 matrix instruction each one costs ~5.5 cycles of matrix time whatever it is (tools/ubench/mfma_fillers*.hip).
-//     The second version of this kernel (8 waves of 32 x 64, weights from L2 into registers) had ~58 of them per 32 matrix instructions — register copies of its double
-//     buffer, LDS address adds for ds_read2_b32's short offsets, 64-bit pointer arithmetic — and ran at 82-98 TFLOP/s, below the library's 94-108.
-//   * Both operands go global -> LDS by buffer loads with the lds bit (16 bytes per lane, scalar-addressed: per-lane offsets are loop invariants, chunk and piece ride in
-//     the scalar offset).  The weights are packed on the host in OPERAND order ([32-channel block][group of four k-pairs][lane][4]): a 1 KB piece is one (block, group),
-//     a lane's four operands are one conflict-free ds_read_b128.  The activations land as [KC][128] rows; a B operand is one ds_read_b32 at an immediate offset.
-//     Two LDS buffers, ONE barrier per chunk of KC = 64 input channels (128 matrix instructions per wave), operands requested two groups of 16 instructions ahead.
-//   * epilogue in registers: + bias[co], + residual[co][q], leaky ReLU as max(v, slope v), store.
-// Work items (position tile, channel tile) are dealt so that an XCD walks a contiguous range with the channel tile fastest: the Cout / 128 workgroups that share a B tile
-// run back to back on one L2.
+// Formulation.  NCHW at batch 1 IS the GEMM  Out[co][q] = sum_k W[co][k] In[k][q]  with the flattened position q contiguous: M = Cout, N = H*W, K = Cin.  A workgroup owns a
+// tile of 128 output channels x 128 positions and walks all input channels; the epilogue (+ bias[co], + residual[co][q], leaky ReLU as max(v, slope v), store) runs in its
+// registers.  Work items (position tile, channel tile) are dealt so that an XCD walks a contiguous range with the channel tile fastest: the Cout / 128 workgroups that share
+// a B tile run back to back on one L2.
+//
+// The kernels, by the layout of the packed weight a launch is handed (c1_launch; vido_slam_amd/nets/ops.py::pack_conv1x1):
+//   3  k_conv1x1_b3<.., NP 2>  split-fp16, two planes and three products on v_mfma_f32_32x32x16_f16: the default (vido_conv1x1_set_arith 0), a ring of LDS slots; also the
+//                              batch form and the 2 x 2 transposed convolution (RES 3);
+//   2  k_conv1x1_b3<.., NP 3>  split-bf16, three planes and six products on v_mfma_f32_32x32x16_bf16 (setting 2): fp32's range, twice the matrix work;
+//   0  k_conv1x1               the fp32 instruction v_mfma_f32_32x32x2f32 (setting 1): the yardstick the two split forms are measured against.
+// The setting decides what vido_conv1x1_layout recommends to a packer, nothing else: a launch runs the kernel of the layout it is given.
 #include "common.hpp"
 #include <atomic>
 
@@ -31,6 +28,17 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct C1Args { const float* x; const float* wp; const float* bias; const float* res; float* y; int M, N, K, mt, total, nchunk; float slope; unsigned xbytes, wbytes; int W; unsigned* range_flag; int hwimg, c4; const int* n_live; };      // hwimg > 0 (k_conv1x1_b3 only): x is a BATCH [img][K][hwimg] and position p = img hwimg + hw; c4: RES 3; n_live (RES 3, may be null): device word, the first n_live images are computed
 
+// ---- the fp32 matrix instruction (round 4; layout 0) ------------------------------------------------------------------------------------------------------------------------
+//   * v_mfma_f32_32x32x2f32 with A = 32 output channels x 2 input channels, B = the same 2 channels x 32 positions: the D layout then keeps, in one register, one output
+//     channel of 32 consecutive positions per half wave — stores (and the residual reads) are whole 128-byte lines.
+//   * workgroup = 4 waves (one per SIMD) = 128 output channels x 128 positions, a wave 64 x 64 (four tiles, 64 accumulator registers).
+//   * The loop carries NO vector-ALU instruction: beside the fp32 matrix instruction each one costs ~5.5 cycles of matrix time whatever it is (tools/ubench/mfma_fillers*.hip).
+//     The second version of this kernel (8 waves of 32 x 64, weights from L2 into registers) had ~58 of them per 32 matrix instructions — register copies of its double
+//     buffer, LDS address adds for ds_read2_b32's short offsets, 64-bit pointer arithmetic — and ran at 82-98 TFLOP/s, below the library's 94-108.
+//   * Both operands go global -> LDS by buffer loads with the lds bit (16 bytes per lane, scalar-addressed: per-lane offsets are loop invariants, chunk and piece ride in
+//     the scalar offset).  The weights are packed on the host in OPERAND order ([32-channel block][group of four k-pairs][lane][4]): a 1 KB piece is one (block, group),
+//     a lane's four operands are one conflict-free ds_read_b128.  The activations land as [KC][128] rows; a B operand is one ds_read_b32 at an immediate offset.
+//     Two LDS buffers, ONE barrier per chunk of KC = 64 input channels (128 matrix instructions per wave), operands requested two groups of 16 instructions ahead.
 // RES: 1 a residual [cout][H*W] is added, 2 a residual at HALF the resolution [cout][H/2][W/2] is added nearest-upsampled (the FPN's top-down path: fpn.py
 // `F.interpolate(last_inner, scale_factor=2, mode="nearest") + inner_lateral`); KC: input channels per chunk and barrier (64: 128 KB of LDS, 128 matrix instructions per
 // wave between barriers; 32 for K % 64 != 0)
@@ -158,118 +166,6 @@ __global__ __launch_bounds__(256) void k_conv1x1(C1Args A)
         }
 }
 
-// ---- 128 x 112 tiles on the 16 x 16 x 4 matrix instruction (round 5) ------------------------------------------------------------------------------------------------------
-// Every bottleneck shape of X-101-32x8d has M * N = 13.9 M outputs = 850 tiles of 128 x 128 = 3.32 rounds of 256 CUs (layer3: 216 tiles, 0.84 rounds): a sixth of the
-// chip-time is CUs waiting for the last round.  128 x 112 tiles make it 972 tiles = 3.8 rounds (layer3: 248 tiles, one round on 97 % of the CUs), each 7 / 8 of the work.
-// 112 is not a multiple of 32, so the tile runs on v_mfma_f32_16x16x4_f32 (same 64 FLOP / clk / SIMD as 32x32x2): a wave owns 32 output channels x 112 positions =
-// 2 x 7 fragments (56 accumulator registers), a k-step (4 input channels) is 14 matrix instructions on 14 different accumulators (the 40-cycle dependent latency of this
-// instruction never shows).  What carries over from the kernel above: both operands global -> LDS by scalar-addressed 1 KB buffer copies, two LDS buffers and one barrier
-// per chunk, operands read at immediate offsets, no vector-ALU instruction in the loop.  What differs:
-//   * weights packed [co / 16][k / 16][lane][4] (pack_conv1x1 layout 1): a lane's 16-byte read = its A operands of four k-steps of one 16-row fragment;
-//   * a B operand of k-step s is rows 4 s .. 4 s + 3 x 16 positions: a copy piece carries rows (r, r + 2) and the two pieces of a k-step sit 272 floats apart, so that the
-//     four 16-lane groups of a ds_read_b32 fall into disjoint banks (rows at the plain pitch of 128 floats would collide two by two);
-//   * the copy's last four lanes of a row (positions 112 .. 127 of the 128 a piece could carry) carry an out-of-range offset: no fetch.
-#define C2_TN 112
-template <int RES, int KC>
-__global__ __launch_bounds__(256) void k_conv1x1_n112(C1Args A)
-{
-    constexpr int NS = KC / 4, NG = KC / 16;          // k-steps / groups of four k-steps per chunk
-    constexpr int A_BUF = 8 * NG * 256;               // floats: 8 fragments of 16 rows x NG pieces of 1 KB
-    constexpr int B_PIECE = 272, B_BUF = 2 * NS * B_PIECE;
-    constexpr int NPA = 2 * NG, NPB = NS / 2, NPW = NPA + NPB;      // copy pieces per wave and chunk
-    extern __shared__ __attribute__((aligned(16))) float c1_lds[];  // [2][A_BUF] [2][B_BUF]
-    float* Al = c1_lds; float* Bl = c1_lds + 2 * A_BUF;
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int per = gridDim.x >> 3, item = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (item >= A.total) return;
-    const int nt = item / A.mt, mtile = item - nt * A.mt, n0 = nt * C2_TN, m0 = mtile * C1_TM;
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)A.wp, 0, A.wbytes, 0x00020000);
-    const unsigned avo = 16u * (unsigned)lane;
-    const unsigned bvo = (lane & 31) < C2_TN / 4 ? 4u * ((unsigned)(lane >> 5) * 2u * (unsigned)A.N + (unsigned)(n0 + 4 * (lane & 31))) : 0xfffffff0u;      // lanes 0..31 row r, 32..63 row r + 2; the last four lanes of a row: out of range, no fetch
-    const int kg = A.K / 16;                          // pieces per 16-row fragment of the packed weight
-    auto issue = [&](int chunk, int buf, int first, int count) {
-#pragma unroll
-        for (int q = first; q < first + count; q++) {
-            if (q >= NPW) break;
-            const int i = 4 * q + w;                                      // (scalar) a wave's pieces of one q are of one kind
-            if (q < NPA) {
-                const int mb = i / NG, g = i - mb * NG;                   // fragment 0..7 of the tile, group
-                const unsigned so = 4u * (unsigned)((((m0 >> 4) + mb) * kg + chunk * NG + g) * 256);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (__attribute__((address_space(3))) void*)(Al + buf * A_BUF + i * 256), 16, avo, so, 0, 0);
-            } else {
-                const int p = i - 4 * NPA, s = p >> 1, h = p & 1;         // piece h of k-step s: rows 4 s + h and 4 s + h + 2
-                const unsigned so = 4u * (unsigned)(chunk * KC + 4 * s + h) * (unsigned)A.N;
-                const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)A.x + so), 0, A.xbytes - so, 0x00020000);      // (exact range check, see above)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void*)(Bl + buf * B_BUF + p * B_PIECE), 16, bvo, 0, 0, 0);
-            }
-        }
-    };
-    f32x4 acc[2][7];
-#pragma unroll
-    for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-        for (int j = 0; j < 7; j++) acc[mi][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    issue(0, 0, 0, NPW);
-    constexpr int PS = (NPW + NS - 3) / (NS - 2);     // pieces a wave sends per k-step: all of them gone two k-steps before the chunk ends
-    typedef const volatile __attribute__((address_space(3))) float* lds_f;      // (volatile: keeps the compiler from pairing the reads into ds_read2_b32, whose 8-bit offsets cost a vector add per pair)
-    for (int c = 0; c < A.nchunk; c++) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                              // chunk c has landed in buffer c & 1; everybody is done with buffer (c + 1) & 1
-        const int nb = (c + 1) & 1, cn = min(c + 1, A.nchunk - 1);
-        const float* Ab = Al + (c & 1) * A_BUF + (2 * w * NG) * 256 + lane * 4;       // fragment 2 w + mi, group g: + (mi NG + g) 256
-        lds_f Bb = (lds_f)(Bl + (c & 1) * B_BUF + ((lane >> 4) & 1) * B_PIECE + (lane >> 5) * 128 + (lane & 15));      // k-step s, fragment j: + s 2 B_PIECE + 16 j
-        asm("" : "+v"(Bb));
-        f32x4 a[2][2]; float b[3][7];
-        auto lda = [&](int g) {
-#pragma unroll
-            for (int mi = 0; mi < 2; mi++) a[g & 1][mi] = *(const f32x4*)(Ab + (mi * NG + g) * 256);
-        };
-        auto ldb = [&](int s) {
-#pragma unroll
-            for (int j = 0; j < 7; j++) b[s % 3][j] = Bb[s * 2 * B_PIECE + 16 * j];
-        };
-        lda(0); ldb(0); ldb(1);
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 2 < NS) ldb(s + 2);
-            if ((s & 3) == 1 && s / 4 + 1 < NG) lda(s / 4 + 1);
-            issue(cn, nb, s * PS, PS);
-#pragma unroll
-            for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-                for (int j = 0; j < 7; j++) acc[mi][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[(s >> 2) & 1][mi][s & 3], b[s % 3][j], acc[mi][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 14; i++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // (the last, unused copies)
-    // D of a 16 x 16 fragment: lane l, register r = output channel 4 (l >> 4) + r, position l & 15
-#pragma unroll
-    for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-        for (int j = 0; j < 7; j++) {
-            const int co0 = m0 + 32 * w + 16 * mi + 4 * (lane >> 4), q = n0 + 16 * j + (lane & 15);
-            if (q < A.N) {
-                float rv[4], bv[4];
-                size_t rq = (size_t)q, rn = (size_t)A.N;
-                if (RES == 2) { const int yy = q / A.W, xx = q - yy * A.W; rq = (size_t)(yy >> 1) * (A.W >> 1) + (xx >> 1); rn = (size_t)(A.N / A.W >> 1) * (A.W >> 1); }
-#pragma unroll
-                for (int r = 0; r < 4; r++) { bv[r] = A.bias ? A.bias[co0 + r] : 0.f; rv[r] = RES ? A.res[(size_t)(co0 + r) * rn + rq] : 0.f; }
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float v = acc[mi][j][r] + bv[r] + rv[r];
-                    A.y[(size_t)(co0 + r) * A.N + q] = fmaxf(v, v * A.slope);
-                }
-            }
-        }
-}
-
 // ---- fp32-equivalent arithmetic on the bf16 matrix instruction: 3-plane split, 6 products (round 6) ----------------------------------------------------------------------
 // The fp32 matrix instruction runs at the fp32 VECTOR rate (157 TFLOP/s); v_mfma_f32_32x32x16_bf16 does 16x the multiply-adds per cycle.  Every fp32 number is EXACTLY
 // the sum of three bf16 numbers  x = x0 + x1 + x2  (x0 = rne(x), x1 = rne(x - x0), x2 = x - x0 - x1: 3 x (8 significant bits + sign) cover the 24-bit significand),
@@ -324,11 +220,11 @@ __device__ __forceinline__ void b3_split2(float x0, float x1, unsigned& p0, unsi
 // the end — two waves per SIMD: measured with one (profiles/r6/conv1x1_b3_counters.txt) a wave issues 5.2 other instructions per matrix instruction, each 4 cycles of issue,
 // against the 8 slots a 32-cycle matrix instruction leaves: the matrix pipe was 61 % busy over a wave's life.  A partner wave on the same SIMD issues into those gaps.
 // A ring slot holds G k-steps (one per group), RB slots; copies run RB - 1 slots ahead; one workgroup barrier per slot.
-// Three forms (c1_launch picks by shape): <G 2, RB 4> one workgroup of 8 waves per CU (160 KB) for long contractions on launches of about one workgroup per CU;
-// <G 1, RB 4> 80 KB and <= 256 registers, so that TWO workgroups share a CU — the prologue / epilogue of one tile runs beside the other tile's loop (layer1: 16 k-steps of
-// ~0.4 us against ~6 us of fixed cost per tile, 3.3 rounds of tiles); <G 1, RB 6> the first form (one workgroup of 4 waves per CU, 120 KB), kept for comparison.
+// Two forms (c1_launch picks by shape; ring depths there): G 2, one workgroup of 8 waves per CU (160 KB) for long contractions on launches of about one workgroup per CU;
+// G 1, 80 KB and <= 256 registers, so that TWO workgroups share a CU — the prologue / epilogue of one tile runs beside the other tile's loop (layer1: 16 k-steps of
+// ~0.4 us against ~6 us of fixed cost per tile, 3.3 rounds of tiles).
 template <int RES, int G, int RB, int NP>
-__global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x1_b3(C1Args A)
+__global__ __launch_bounds__(256 * G, G == 1 ? 2 : G) void k_conv1x1_b3(C1Args A)
 {
     constexpr int B3_SLOT = B3_SLOTB(NP), B3_PW = B3_PWN(NP);
     constexpr int SLOTB = G * B3_SLOT;
@@ -397,19 +293,12 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
             for (int pl = 0; pl < NP; pl++) a[buf][rb][pl] = *(const __attribute__((address_space(3))) u32x4*)(Ab + (rb * NP + pl) * 1024);
     };
     auto ldb = [&](int slot) {
-#ifdef H2_PRESPLIT_EMU
-        if (NP == 2) return;
-#endif
         const __attribute__((address_space(3))) float* Bb = (const __attribute__((address_space(3))) float*)((lds_c)(L + slot * SLOTB) + b_lane);      // (not volatile: the compiler pairs the eight reads, 512 bytes apart, into four ds_read2st64_b32)
 #pragma unroll
         for (int i = 0; i < 8; i++) braw[i] = Bb[i * C1_TN];
     };
     auto split = [&](int buf) {
         if constexpr (NP == 2) {
-#ifdef H2_PRESPLIT_EMU      // (timing experiment: what the k-step would cost if the activations arrived already split — two wide LDS reads, no vector instruction; results are garbage)
-            { lds_c Bq = (lds_c)(L + (buf ? SLOTB : 0)) + 16u * (unsigned)lane; bp[buf][0] = *(const __attribute__((address_space(3))) u32x4*)(Bq + 8192); bp[buf][1] = *(const __attribute__((address_space(3))) u32x4*)(Bq + 9216); }
-            return;
-#endif
 #pragma unroll
             for (int pr = 0; pr < 4; pr++) {
                 const f32x2 v = {braw[2 * pr], braw[2 * pr + 1]};
@@ -426,11 +315,7 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
             }
         } else {
 #pragma unroll
-#ifdef B3_NOSPLIT
-            for (int pr = 0; pr < 4; pr++) { bp[buf][0][pr] = __float_as_uint(braw[2 * pr]); bp[buf][1][pr] = __float_as_uint(braw[2 * pr + 1]); bp[buf][2][pr] = __float_as_uint(braw[2 * pr]) ^ 1; }
-#else
             for (int pr = 0; pr < 4; pr++) { unsigned p0, p1, p2; b3_split2(braw[2 * pr], braw[2 * pr + 1], p0, p1, p2); bp[buf][0][pr] = p0; bp[buf][1][pr] = p1; bp[buf][2][pr] = p2; }
-#endif
         }
     };
     // The barrier is the bare instruction (no fence): __syncthreads() would drain the copies in flight (vmcnt(0)), which is the ring's whole point.  What it must order is
@@ -455,9 +340,6 @@ __global__ __launch_bounds__(256 * G, (G == 1 && RB != 6) ? 2 : G) void k_conv1x
 #pragma unroll
                     for (int rb = 0; rb < 4; rb++) {
                         f32x16& d = term == 2 ? acc[rb] : acl[rb];
-#ifdef B3_NOMFMA                  // (timing experiment: the operand stream and the barriers alone; one matrix instruction per step keeps the operands alive)
-                        if (term != 2 || rb != 0) continue;
-#endif
                         d = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[h][rb][PA[term]]), __builtin_bit_cast(f16x8, bp[h][PB[term]]), d, 0, 0, 0);
                     }
                 }
@@ -578,68 +460,53 @@ int vido_conv1x1_supported(int cin, int cout, int hw)
     return cin >= 32 && cin % 32 == 0 && cout >= C1_TM && cout % C1_TM == 0 && hw >= C1_TN && 4ll * cin * hw < (1ll << 32) && 4ll * cin * cout < (1ll << 32);
 }
 
-/* Which tile form (= which weight packing) the library uses for a shape: 0 = 128 x 128 tiles on 32x32x2 (pack layout 0), 1 = 128 x 112 tiles on 16x16x4 (pack layout 1).
- * The form with fewer (rounds of 256 CUs) x (tile width) wins; VIDO_CONV1X1_TN = 128 / 112 forces one.  The packer (vido_slam_amd/nets/ops.py::pack_conv1x1) asks this
- * function, vido_conv1x1_bias_act asks it again with the same shape. */
-static std::atomic<int>& c1_arith()          // 0 = split-fp16 (two planes, three products: the default), 1 = the fp32 instruction, 2 = split-bf16 (three planes, six products)
+/* The arithmetic setting: 0 = split-fp16 (two planes, three products: the default), 1 = the fp32 instruction, 2 = split-bf16 (three planes, six products); at start from
+ * VIDO_CONV1X1_ARITH = f16x2 | f32 | bf16x3.  It selects what vido_conv1x1_layout recommends to a packer (and what vido_deconv2x2_supported answers); no launch reads it. */
+static std::atomic<int>& c1_arith()
 {
-    static std::atomic<int> v{[] { const char* e = getenv("VIDO_CONV1X1_ARITH");
-                                   return (e && !strcmp(e, "f32")) || (!e && getenv("VIDO_CONV1X1_TN")) ? 1 : (e && (!strcmp(e, "bf16x3") || !strcmp(e, "bf16"))) ? 2 : 0; }()};
+    static std::atomic<int> v{[] { const char* e = getenv("VIDO_CONV1X1_ARITH"); return (e && !strcmp(e, "f32")) ? 1 : (e && (!strcmp(e, "bf16x3") || !strcmp(e, "bf16"))) ? 2 : 0; }()};
     return v;
 }
 
 int vido_conv1x1_set_arith(int arith) { return c1_arith().exchange(arith == 1 ? 1 : arith == 2 ? 2 : 0); }
 int vido_conv1x1_get_arith(void) { return c1_arith().load(std::memory_order_relaxed); }
 
-/* The range flag of the split-fp16 kernels (1x1, 3x3, fully connected, 2x2 transposed): non-zero when a launch since the last reset met an activation with |x| >= 65504, an
- * infinity or a NaN — its outputs are then not valid.
- * Host-visible memory written by the kernels: read it after the stream has been waited for.  reset != 0 clears it. */
-int vido_conv1x1_range_flag(vido_ctx* ctx, int reset)
-{
-    if (!ctx || !ctx->c1_range_flag) return 0;
-    // read and reset in ONE atomic step: a flag raised between a load and a store would be lost
-    return reset ? (int)__atomic_exchange_n(ctx->c1_range_flag, 0u, __ATOMIC_ACQ_REL) : (int)__atomic_load_n(ctx->c1_range_flag, __ATOMIC_ACQUIRE);
-}
-
+/* The weight packing to make for a shape under the current setting (pack_conv1x1 layout): 3 = split-fp16, 2 = split-bf16, 0 = the fp32 instruction.  The same for every shape. */
 int vido_conv1x1_layout(int cin, int cout, int hw)
 {
-    // Default 128: measured on the pipelined headline (two A/B pairs of 100 steps, profiles/r5/conv1x1_tile_form_ab.txt) the 112-wide form costs 2.5 % (88.3 -> 86.1 frames/s)
-    // although the detector ALONE gets faster (8.87 -> 8.65 ms): beside two other streams the CUs a 216-tile launch leaves idle are not idle — they run LiteFlowNet and the
-    // tracker — and the 112-wide form needs the same matrix time on 248 CUs plus more LDS reads per matrix instruction.  VIDO_CONV1X1_TN=0 lets the rounds rule below decide
-    // (a detector running alone), 112 / 128 force a form.
-    // round 6: the split-bf16 form (k_conv1x1_b3: fp32-equivalent arithmetic on the bf16 matrix instruction) is the default; VIDO_CONV1X1_ARITH=f32 (or a forced
-    // VIDO_CONV1X1_TN) brings the fp32-instruction forms back.
-    { const int ar = c1_arith().load(std::memory_order_relaxed); if (ar != 1) return ar == 2 ? 2 : 3; }
-    static const int force = [] { const char* e = getenv("VIDO_CONV1X1_TN"); return e ? atoi(e) : 128; }();
-    if (force == 128 || cin % 64 != 0) return 0;
-    if (force == 112) return 1;
-    const long long mt = cout / C1_TM, t128 = mt * ((hw + 127) / 128), t112 = mt * ((hw + C2_TN - 1) / C2_TN);
-    const long long c128 = ((t128 + 255) / 256) * 128, c112 = ((t112 + 255) / 256) * C2_TN;
-    return c112 < c128 ? 1 : 0;
+    const int ar = c1_arith().load(std::memory_order_relaxed);
+    return ar == 1 ? 0 : ar == 2 ? 2 : 3;
+}
+
+// VIDO_CONV1X1_B3_FORM = 2 / 3: every split launch on the two-group / the one-group ring (a test's hook to run a shape through both); anything else: by shape
+static int c1_forced_form()
+{
+    static const int f = [] { const char* e = getenv("VIDO_CONV1X1_B3_FORM"); const int v = e ? atoi(e) : 0; return v == 2 || v == 3 ? v : 0; }();
+    return f;
 }
 
 /* y = leaky_relu(conv2d(x, w) + bias + residual, slope) for one image, 1x1 kernel, stride 1: x [cin][hw], y / residual [cout][hw] f32 DEVICE tensors (16-byte aligned,
- * y != x), bias [cout] or NULL, residual NULL when there is none.  w_packed: the weight [cout][cin] in operand order — layout vido_conv1x1_layout(cin, cout, hw):
- *   0: element (co, k) at [co / 32][k / 8][32 * (k & 1) + co % 32][(k % 8) / 2];   1: at [co / 16][k / 16][16 * (k & 3) + co % 16][(k % 16) / 4]
- * (vido_slam_amd/nets/ops.py::pack_conv1x1).  slope 0 = ReLU, 1 = none (0 <= slope <= 1).  Enqueues on the adopted stream; capturable. */
-static int c1_launch(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, int res_mode, float* y, int cin, int cout, int hw, int w, float slope,
+ * y != x), bias [cout] or NULL, residual NULL when there is none.  w_packed: the weight [cout][cin] in operand order, `layout` says which (vido_slam_amd/nets/ops.py::pack_conv1x1):
+ *   0: fp32, element (co, k) at [co / 32][k / 8][32 * (k & 1) + co % 32][(k % 8) / 2];   2: three bf16 planes;   3: two fp16 planes + [cout] inverse channel scales.
+ * The kernel family and the bytes the weight descriptor spans follow from `layout` alone.  slope 0 = ReLU, 1 = none (0 <= slope <= 1).  Enqueues on the adopted stream; capturable. */
+static int c1_launch(vido_ctx* ctx, int layout, const float* x, const float* w_packed, const float* bias, const float* residual, int res_mode, float* y, int cin, int cout, int hw, int w, float slope,
                      int hwimg = 0, int c4 = 0, const int32_t* n_live = nullptr)
 {
     if (!ctx) return VIDO_E_INVALID;
+    if (layout != 0 && layout != 2 && layout != 3) return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1: layout %d is no weight packing (0 = fp32 instruction, 2 = split-bf16, 3 = split-fp16)", layout);
     if (!x || !w_packed || !y || x == y || !vido_conv1x1_supported(cin, cout, hw) || slope < 0.f || slope > 1.f || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)n_live) & 3) || ((uintptr_t)w_packed & 15))
         return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1: no kernel for %d -> %d channels at %d positions (or a pointer is misaligned, or slope outside [0, 1])", cin, cout, hw);
+    const int rm = res_mode == 3 ? 3 : (residual ? res_mode : 0);
+    if ((hwimg || rm == 3) && layout != 3) return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1: the batch / transposed-convolution forms exist in the split-fp16 arithmetic only (layout 3, not %d)", layout);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    const int rm = res_mode == 3 ? 3 : (residual ? res_mode : 0);
-    const int layout = vido_conv1x1_layout(cin, cout, hw);
-    if ((hwimg || rm == 3) && layout != 3) return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1: the batch / transposed-convolution forms exist in the split-fp16 arithmetic only");
+    const int mt = cout / C1_TM, ntl = (hw + C1_TN - 1) / C1_TN, total = mt * ntl;
+    const dim3 grid(8 * ((total + 7) / 8));
     if (layout >= 2) {
         const int np = layout == 3 ? 2 : 3;
-        const int mt = cout / C1_TM, ntl = (hw + C1_TN - 1) / C1_TN, total = mt * ntl;
         C1Args A{x, w_packed, bias, residual, y, cout, hw, cin, mt, total, cin / 16, slope, (unsigned)(4ll * cin * hw), (unsigned)(2ll * np * cin * cout), w, ctx->c1_range_flag, hwimg, c4, n_live};
-        // form: VIDO_CONV1X1_B3_FORM = 0 (default: by shape), 1 = <1, 6>, 2 = <2, 4>, 3 = <1, 4> two workgroups per CU
-        static const int force_form = [] { const char* e = getenv("VIDO_CONV1X1_B3_FORM"); return e ? atoi(e) : 0; }();
-        int form = force_form ? force_form : (cin >= 512 && total <= 320 ? 2 : 3);
+        // form 2 = two wave groups, one workgroup per CU; 3 = one group, two workgroups per CU
+        int form = c1_forced_form() ? c1_forced_form() : (cin >= 512 && total <= 320 ? 2 : 3);
         if (form == 2 && cin % 64) form = 3;                                // (two groups: an even number of slots of two k-steps)
         // ring depths: the bf16 form 4 slots of 20 KB (x 2 groups = 160 KB; one group: 80 KB, two workgroups per CU); the fp16 form's k-step is half as long and its slot
         // 16 KB: 5 slots (x 2 groups = 160 KB; one group: 80 KB) keep the copies as far ahead in time
@@ -647,46 +514,28 @@ static int c1_launch(vido_ctx* ctx, const float* x, const float* w_packed, const
         if (!attr3[ctx->device & 63]) {
 #define B3_ATTR(G_, RB_, NP_) for (const void* f : {(const void*)k_conv1x1_b3<0, G_, RB_, NP_>, (const void*)k_conv1x1_b3<1, G_, RB_, NP_>, (const void*)k_conv1x1_b3<2, G_, RB_, NP_>}) \
             HIP_TRY(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)RB_ * G_ * B3_SLOTB(NP_))))
-            B3_ATTR(1, 6, 3); B3_ATTR(2, 4, 3); B3_ATTR(1, 4, 3); B3_ATTR(2, 5, 2); B3_ATTR(1, 5, 2); B3_ATTR(1, 4, 2); B3_ATTR(1, 3, 2);
+            B3_ATTR(2, 4, 3); B3_ATTR(1, 4, 3); B3_ATTR(2, 5, 2); B3_ATTR(1, 5, 2);
 #undef B3_ATTR
             HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv1x1_b3<3, 2, 5, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)5 * 2 * B3_SLOTB(2))));
             HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_conv1x1_b3<3, 1, 5, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)5 * 1 * B3_SLOTB(2))));
             attr3[ctx->device & 63] = true;
         }
-        const dim3 grid(8 * ((total + 7) / 8));
 #define B3_LAUNCH(G_, RB_, NP_) do { const dim3 blk(256 * G_); const size_t lds = (size_t)RB_ * G_ * B3_SLOTB(NP_); \
             if (rm == 2) hipLaunchKernelGGL((k_conv1x1_b3<2, G_, RB_, NP_>), grid, blk, lds, st, A); else if (rm) hipLaunchKernelGGL((k_conv1x1_b3<1, G_, RB_, NP_>), grid, blk, lds, st, A); \
             else hipLaunchKernelGGL((k_conv1x1_b3<0, G_, RB_, NP_>), grid, blk, lds, st, A); } while (0)
-        static const int rb_short = [] { const char* e = getenv("VIDO_CONV1X1_H2_RB"); return e ? atoi(e) : 5; }();      // (experiment: ring depth of the one-group fp16 form)
         if (rm == 3) {      // (the transposed convolution: the fp16 form's two launch forms)
             if (form == 2) hipLaunchKernelGGL((k_conv1x1_b3<3, 2, 5, 2>), grid, dim3(512), (size_t)5 * 2 * B3_SLOTB(2), st, A);
             else hipLaunchKernelGGL((k_conv1x1_b3<3, 1, 5, 2>), grid, dim3(256), (size_t)5 * B3_SLOTB(2), st, A);
         }
-        else if (np == 2) { if (form == 2) B3_LAUNCH(2, 5, 2); else if (rb_short == 4) B3_LAUNCH(1, 4, 2); else if (rb_short == 3) B3_LAUNCH(1, 3, 2); else B3_LAUNCH(1, 5, 2); }
-        else if (form == 2) B3_LAUNCH(2, 4, 3); else if (form == 1) B3_LAUNCH(1, 6, 3); else B3_LAUNCH(1, 4, 3);
+        else if (np == 2) { if (form == 2) B3_LAUNCH(2, 5, 2); else B3_LAUNCH(1, 5, 2); }
+        else if (form == 2) B3_LAUNCH(2, 4, 3); else B3_LAUNCH(1, 4, 3);
 #undef B3_LAUNCH
         HIP_TRY(ctx, hipGetLastError());
         return VIDO_OK;
     }
-    if (layout == 1) {
-        const int mt = cout / C1_TM, ntl = (hw + C2_TN - 1) / C2_TN, total = mt * ntl;
-        C1Args A{x, w_packed, bias, residual, y, cout, hw, cin, mt, total, cin / 64, slope, (unsigned)(4ll * cin * hw), (unsigned)(4ll * cin * cout), w};
-        constexpr size_t LDS112 = (size_t)2 * (8 * 4 * 256 + 2 * 16 * 272) * 4;
-        static bool attr2[64] = {};
-        if (!attr2[ctx->device & 63]) {
-            for (const void* f : {(const void*)k_conv1x1_n112<0, 64>, (const void*)k_conv1x1_n112<1, 64>, (const void*)k_conv1x1_n112<2, 64>}) HIP_TRY(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS112));
-            attr2[ctx->device & 63] = true;
-        }
-        const dim3 grid(8 * ((total + 7) / 8)), blk(256);
-        if (rm == 2) hipLaunchKernelGGL((k_conv1x1_n112<2, 64>), grid, blk, LDS112, st, A); else if (rm) hipLaunchKernelGGL((k_conv1x1_n112<1, 64>), grid, blk, LDS112, st, A); else hipLaunchKernelGGL((k_conv1x1_n112<0, 64>), grid, blk, LDS112, st, A);
-        HIP_TRY(ctx, hipGetLastError());
-        return VIDO_OK;
-    }
-    const int mt = cout / C1_TM, ntl = (hw + C1_TN - 1) / C1_TN, total = mt * ntl;
-    static const int force_kc = [] { const char* e = getenv("VIDO_CONV1X1_KC"); return e ? atoi(e) : 0; }();
-    const int kc = (cin % 64 == 0 && force_kc != 32) ? 64 : 32;
+    const int kc = cin % 64 == 0 ? 64 : 32;
     C1Args A{x, w_packed, bias, residual, y, cout, hw, cin, mt, total, cin / kc, slope, (unsigned)(4ll * cin * hw), (unsigned)(4ll * cin * cout), w};
-    const dim3 grid(8 * ((total + 7) / 8)), blk(256);
+    const dim3 blk(256);
     constexpr size_t LDS64 = (size_t)2 * (4 * 8 * 256 + 64 * C1_TN) * 4, LDS32 = (size_t)2 * (4 * 4 * 256 + 32 * C1_TN) * 4;
     static bool attr[64] = {};
     if (!attr[ctx->device & 63]) {
@@ -717,20 +566,20 @@ int vido_deconv2x2_bias_act(vido_ctx* ctx, const float* x, const float* w_packed
 int vido_deconv2x2_bias_act_n(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, float* y, int n, int cin, int cout, int h, int w, float slope, const int32_t* n_live)
 {
     if (ctx && !vido_deconv2x2_supported(n, cin, cout, h, w)) return vido_set_error(ctx, VIDO_E_INVALID, "deconv2x2: no kernel for %d x %d -> %d channels at %d x %d", n, cin, cout, h, w);
-    return c1_launch(ctx, x, w_packed, bias, nullptr, 3, y, cin, 4 * cout, n * h * w, w, slope, h * w, cout, n_live);
+    return c1_launch(ctx, 3, x, w_packed, bias, nullptr, 3, y, cin, 4 * cout, n * h * w, w, slope, h * w, cout, n_live);
 }
 
-int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope)
+int vido_conv1x1_bias_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual, float* y, int cin, int cout, int hw, float slope, int layout)
 {
-    return c1_launch(ctx, x, w_packed, bias, residual, 1, y, cin, cout, hw, hw, slope);
+    return c1_launch(ctx, layout, x, w_packed, bias, residual, 1, y, cin, cout, hw, hw, slope);
 }
 
 /* The same with the residual at HALF the resolution, added nearest-upsampled: y[co][yy][xx] = act(conv + bias[co] + residual_half[co][yy / 2][xx / 2]) — the FPN's
  * lateral convolution + top-down sum (maskrcnn_benchmark/modeling/backbone/fpn.py:55-66) as one launch.  h, w even; residual_half [cout][h / 2][w / 2]. */
-int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual_half, float* y, int cin, int cout, int h, int w, float slope)
+int vido_conv1x1_bias_up2_act(vido_ctx* ctx, const float* x, const float* w_packed, const float* bias, const float* residual_half, float* y, int cin, int cout, int h, int w, float slope, int layout)
 {
     if (ctx && (h < 2 || w < 2 || (h & 1) || (w & 1) || !residual_half)) return vido_set_error(ctx, VIDO_E_INVALID, "conv1x1 (upsampled residual): %d x %d must be even and the residual given", h, w);
-    return c1_launch(ctx, x, w_packed, bias, residual_half, 2, y, cin, cout, h * w, w, slope);
+    return c1_launch(ctx, layout, x, w_packed, bias, residual_half, 2, y, cin, cout, h * w, w, slope);
 }
 
 }  // extern "C"

@@ -106,10 +106,19 @@ class HipOps:
         if not self.ctx.lib.vido_deconv2x2_supported(n, cin, cout, H, W):
             return None
         wp = cached_pack(conv, "_dc_w", w, x.device, (), lambda: pack_deconv2x2(w).to(x.device))
+        return self.deconv2x2_bias_act(x.contiguous(), wp, conv.bias, slope, n_live)
+
+    def deconv2x2_bias_act(self, x, w_packed, bias, slope, n_live=None):
+        """The launch of deconv2x2_conv on a packed weight: w_packed = pack_deconv2x2(w), i.e. pack_conv1x1 layout 3 of the [4 cout][cin] matrix — the only layout the
+        transposed form exists in; any other tensor is refused here."""
+        n, cin, H, W = (int(v) for v in x.shape)
+        layout, rows = packed_conv1x1_layout(w_packed, cin)
+        if layout != 3 or rows % 4:
+            raise ValueError("deconv2x2: the weight must be packed by pack_deconv2x2 (pack_conv1x1 layout 3 of 4 cout rows), not layout %d of %d rows" % (layout, rows))
+        cout = rows // 4
         out = torch.empty((n, cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
         self._count_flops(2.0 * n * cin * cout * 4 * H * W)
-        x = x.contiguous()
-        self._call(self.ctx.lib.vido_deconv2x2_bias_act_n, x.data_ptr(), wp.data_ptr(), _p(conv.bias), out.data_ptr(), n, cin, cout, H, W, slope, self._live_ptr(n_live))
+        self._call(self.ctx.lib.vido_deconv2x2_bias_act_n, x.data_ptr(), w_packed.data_ptr(), _p(bias), out.data_ptr(), n, cin, cout, H, W, slope, self._live_ptr(n_live))
         return out
 
     def det_order(self, scores, labels, n_det, confidence, count32=False):
@@ -299,32 +308,28 @@ class HipOps:
 
     def conv1x1_bias_act(self, x, w_packed, bias=None, residual=None, slope=1.0, residual_up2=None):
         """leaky_relu(conv2d(x, w) + bias + residual, slope) for one image, 1x1 kernel, stride 1, as one matrix-core GEMM launch (csrc/conv1x1.hip);
-        w_packed = pack_conv1x1(w, conv1x1_layout(cin, cout, H * W)).  slope 0 = ReLU, 1 = none.  residual_up2: a residual at half the resolution, added nearest-upsampled
-        (the FPN's top-down sum)."""
+        w_packed = pack_conv1x1(w, layout) of any layout — the launch runs in the arithmetic the weight was packed for, whatever conv1x1_set_arith says by now — or a
+        PackedConv1x1.  slope 0 = ReLU, 1 = none.  residual_up2: a residual at half the resolution, added nearest-upsampled (the FPN's top-down sum)."""
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == 1
         _, cin, H, W = x.shape
-        if isinstance(w_packed, PackedConv1x1):                     # packed on first use, in the tile form the library picks for this (cin, cout, H * W)
+        if isinstance(w_packed, PackedConv1x1):                     # packed on first use, in the layout the library recommends under the current arithmetic setting
             w_packed = w_packed.get(self.conv1x1_layout(cin, w_packed.cout, H * W), x.device)
-        cout = (w_packed.numel() // (2 * (cin + 1)) if w_packed.dim() == 1 else w_packed.numel() // cin // 3) if w_packed.dtype == torch.int16 else w_packed.numel() // cin
-        layout = self.conv1x1_layout(cin, cout, H * W)
-        assert not self.conv1x1_supported(cin, cout, H * W) or tuple(w_packed.shape) == {0: (cout // 32, cin // 8, 64, 4), 1: (cout // 16, cin // 16, 64, 4), 2: (cout // 32, cin // 16, 3, 64, 8),
-                                                                                         3: (2 * cout * (cin + 1),)}[layout], \
-            "conv1x1: weight packed for another form (pack_conv1x1(w, layout))"      # (an unsupported shape is refused by the library call below)
+        layout, cout = packed_conv1x1_layout(w_packed, cin)
         assert 0.0 <= slope <= 1.0 and (residual is None or residual_up2 is None)
         out = torch.empty((1, cout, H, W), device=x.device, dtype=torch.float32)
         self._count_flops(2.0 * cout * cin * H * W)
         if residual_up2 is not None:
             residual_up2 = residual_up2.contiguous(); assert tuple(residual_up2.shape) == (1, cout, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0
-            self._call(self.ctx.lib.vido_conv1x1_bias_up2_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), residual_up2.data_ptr(), out.data_ptr(), int(cin), int(cout), int(H), int(W), slope)
+            self._call(self.ctx.lib.vido_conv1x1_bias_up2_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), residual_up2.data_ptr(), out.data_ptr(), int(cin), int(cout), int(H), int(W), slope, layout)
             return out
         if residual is not None:
             residual = residual.contiguous(); assert residual.shape == out.shape
-        self._call(self.ctx.lib.vido_conv1x1_bias_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), _p(residual), out.data_ptr(), int(cin), int(cout), int(H * W), slope)
+        self._call(self.ctx.lib.vido_conv1x1_bias_act, x.data_ptr(), w_packed.data_ptr(), _p(bias), _p(residual), out.data_ptr(), int(cin), int(cout), int(H * W), slope, layout)
         return out
 
     def conv1x1_conv(self, conv, x, slope=1.0, residual=None, residual_up2=None):
         """The 1x1 convolution `conv` (nn.Conv2d, stride 1) + bias (+ residual) + activation through conv1x1_bias_act when the layer has that form, else None; the packed weight
-        is cached on the module (per tile form) and rebuilt when the weight tensor changes."""
+        is cached on the module (per layout) and rebuilt when the weight tensor changes."""
         w = conv.weight
         if (tuple(w.shape[2:]) != (1, 1) or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (0, 0) or conv.groups != 1 or not x.is_cuda or x.shape[0] != 1
                 or self._range_safe or not self.conv1x1_supported(w.shape[1], w.shape[0], x.shape[2] * x.shape[3])):
@@ -1030,19 +1035,21 @@ def split_f16x2(w):
 
 
 def pack_conv1x1(w, layout=0):
-    """1x1 convolution weight [cout, cin, 1, 1] (or [cout, cin]) -> the operand order of csrc/conv1x1.hip (layout = HipOps.conv1x1_layout(cin, cout, H * W) = vido_conv1x1_layout):
+    """1x1 convolution weight [cout, cin, 1, 1] (or [cout, cin]) -> the operand order of csrc/conv1x1.hip (layout = HipOps.conv1x1_layout(cin, cout, H * W) = vido_conv1x1_layout
+    for the current arithmetic setting, or any of the three by choice: a launch runs the layout it is handed):
     0: element (co, k) at [co / 32][k / 8][32 * (k & 1) + co % 32][(k % 8) / 2] (a lane's four operands of a group of four k-pairs are one 16-byte read; a (32-channel block, group)
-       is one 1 KB copy piece) — the 128 x 128 tiles on the 32 x 32 x 2 matrix instruction;
-    1: at [co / 16][k / 16][16 * (k & 3) + co % 16][(k % 16) / 4] (a lane's 16-byte read = its operands of four k-steps of a 16-row fragment) — the 128 x 112 tiles on 16 x 16 x 4;
+       is one 1 KB copy piece) — the fp32 matrix instruction (32 x 32 x 2);
     2: the weight split into three bf16 planes (split_bf16x3), plane p of element (co, k) at [co / 32][k / 16][p][32 * ((k % 16) / 8) + co % 32][k % 8] (int16 tensor: a 1 KB copy
        piece = the A operand of v_mfma_f32_32x32x16_bf16 for one (32-channel block, 16 input channels, plane)) — the split-bf16 form k_conv1x1_b3.
     3: the weight as two fp16 planes of its rows scaled by powers of two (split_f16x2), in the order of 2 with two planes, followed by the [cout] inverse row scales
        (flat int16 tensor of 2 cout (cin + 1) elements) — the split-fp16 form, the default.
-    None when the kernel does not take the shape."""
+    None when the kernel does not take the shape; ValueError for any other layout."""
+    if layout not in (0, 2, 3):
+        raise ValueError("pack_conv1x1: no layout %r (0 = fp32 instruction, 2 = split-bf16, 3 = split-fp16)" % (layout,))
     cout, cin = int(w.shape[0]), int(w.shape[1])
     if w.dim() == 4 and tuple(w.shape[2:]) != (1, 1):
         return None
-    if cout % 128 or cin % 32 or (layout == 1 and cin % 64):
+    if cout % 128 or cin % 32:
         return None
     if layout == 3:
         h, l, inv = split_f16x2(w.detach().reshape(cout, cin))
@@ -1053,11 +1060,21 @@ def pack_conv1x1(w, layout=0):
         p0, p1, p2 = split_bf16x3(w.detach().reshape(cout, cin).float())
         w6 = torch.stack([p0, p1, p2], 0).view(torch.int16).reshape(3, cout // 32, 32, cin // 16, 2, 8)      # [plane][mb][co32][step][k half][8]
         return w6.permute(1, 3, 0, 4, 2, 5).contiguous().reshape(cout // 32, cin // 16, 3, 64, 8)
-    if layout == 1:
-        w5 = w.detach().reshape(cout // 16, 16, cin // 16, 4, 4)         # [fragment][co16][group][e][kk]   with k = 16 group + 4 e + kk
-        return w5.permute(0, 2, 4, 1, 3).contiguous().reshape(cout // 16, cin // 16, 64, 4)
     w5 = w.detach().reshape(cout // 32, 32, cin // 8, 4, 2)            # [mb][co32][group][kk][half]
     return w5.permute(0, 2, 4, 1, 3).contiguous().reshape(cout // 32, cin // 8, 64, 4)
+
+
+def packed_conv1x1_layout(wp, cin):
+    """(layout, cout) of a tensor made by pack_conv1x1 for `cin` input channels, read off its dtype and shape: float32 (cout / 32, cin / 8, 64, 4) is layout 0, int16
+    (cout / 32, cin / 16, 3, 64, 8) layout 2, flat int16 of 2 cout (cin + 1) elements layout 3.  ValueError when it is none of them: a pack for another cin, or no pack."""
+    cin = int(cin); sh = tuple(int(v) for v in wp.shape)
+    if wp.dtype == torch.float32 and len(sh) == 4 and sh[1:] == (cin // 8, 64, 4) and cin % 8 == 0:
+        return 0, 32 * sh[0]
+    if wp.dtype == torch.int16 and len(sh) == 5 and sh[1:] == (cin // 16, 3, 64, 8) and cin % 16 == 0:
+        return 2, 32 * sh[0]
+    if wp.dtype == torch.int16 and len(sh) == 1 and sh[0] > 0 and sh[0] % (2 * (cin + 1)) == 0:
+        return 3, sh[0] // (2 * (cin + 1))
+    raise ValueError("conv1x1: a %s tensor of shape %s is no pack_conv1x1 weight for %d input channels" % (wp.dtype, sh, cin))
 
 
 def pack_conv3x3_h(w):
@@ -1085,8 +1102,8 @@ def pack_deconv2x2(w):
 
 
 class PackedConv1x1:
-    """A 1x1 convolution weight whose operand order depends on the map it meets (pack_conv1x1 layouts 0 / 1): packed lazily per (layout, device), outside any graph capture
-    (the warm-up calls of fuse.Graphed come first).  None-like when no layout takes the shape: use PackedConv1x1.make."""
+    """A 1x1 convolution weight whose operand order depends on the arithmetic setting at its first use (pack_conv1x1 layouts 0 / 2 / 3): packed lazily per (layout, device),
+    outside any graph capture (the warm-up calls of fuse.Graphed come first).  None-like when no layout takes the shape: use PackedConv1x1.make."""
 
     def __init__(self, w):
         self.w = w.detach(); self.cout = int(w.shape[0]); self.cin = int(w.shape[1]); self._p = {}
