@@ -726,7 +726,10 @@ int vido_roi_align_fpn_nhwc_n(vido_ctx* ctx, const float* const feat[4], const i
  * vp3DPointSta / vnAssoSta), vido_bawin_set_labels the tracklet-label changes ((frame, feature, tracklet, position) quads: Map::vnTrkSta / vnPosSta), vido_bawin_solve assembles
  * the window's graph on the device exactly like the Map walk does (observations in (frame, feature) order, landmark ids in order of first appearance, chains that start before
  * the window dropped), solves it in place and writes the refined landmarks back into the ring.  prob: cameras (n_cam = N - start), odometry factors, prior, weights and LM
- * parameters as for vido_ba_optimize; its observation / point fields are ignored.  vido_bawin_read_points: one stored frame's world points (f32 [n][3]). */
+ * parameters as for vido_ba_optimize; its observation / point fields are ignored.  vido_bawin_read_points: one stored frame's world points (f32 [n][3]).
+ * Order of the label quads: they apply in the order given, within one call and across calls, so when a (frame, feature) pair occurs more than once the LAST quad holds.
+ * Quads of a negative frame, of a frame that is not (or no longer) in the ring, or of a feature >= that frame's count are ignored; vido_bawin_push_frame resets the labels
+ * of the slot it fills. */
 int vido_bawin_create(vido_ctx* ctx, int cap_frames, int cap_features);
 int vido_bawin_push_frame(vido_ctx* ctx, int frame, int n, const double* meas, const float* xyz, const int32_t* asso);
 int vido_bawin_set_labels(vido_ctx* ctx, int n, const int32_t* quads);

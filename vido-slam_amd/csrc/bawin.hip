@@ -25,6 +25,7 @@ struct BaWin {
     int* d_counts = nullptr; int* h_counts = nullptr;              // [4]: n_obs, n_pt, overflow, max track
     char* h_stage = nullptr; size_t stage_cap = 0; char* d_stage = nullptr;
     std::vector<int> frame_of, nfeat;                               // per ring slot: the frame it holds (-1: empty), its feature count
+    std::vector<std::pair<unsigned, int> > lab_at; unsigned lab_stamp = 0;      // vido_bawin_set_labels: per ring row, where the current chunk staged its quad
     int last_start = -1, last_N = -1, last_nobs = 0;
 };
 
@@ -213,7 +214,7 @@ int vido_bawin_create(vido_ctx* ctx, int cap_frames, int cap_features)
     HIP_TRY(ctx, hipHostMalloc((void**)&B->h_stage, B->stage_cap)); HIP_TRY(ctx, hipMalloc((void**)&B->d_stage, B->stage_cap));
     HIP_TRY(ctx, hipMemset(B->d_trk, 0xff, nf * 4)); HIP_TRY(ctx, hipMemset(B->d_pos, 0, nf * 4)); HIP_TRY(ctx, hipMemset(B->d_nfeat, 0, cap_frames * 4));
     HIP_TRY(ctx, hipMemset(B->d_cnt, 0, nf * 4)); HIP_TRY(ctx, hipMemset(B->d_counts, 0, 16));
-    B->frame_of.assign(cap_frames, -1); B->nfeat.assign(cap_frames, 0);
+    B->frame_of.assign(cap_frames, -1); B->nfeat.assign(cap_frames, 0); B->lab_at.assign(nf, std::make_pair(0u, 0));
     return VIDO_OK;
 }
 
@@ -222,7 +223,8 @@ int vido_bawin_create(vido_ctx* ctx, int cap_frames, int cap_features)
  * tracklet"; vido_bawin_set_labels brings them in. */
 int vido_bawin_push_frame(vido_ctx* ctx, int frame, int n, const double* meas, const float* xyz, const int32_t* asso)
 {
-    if (!ctx || !ctx->bawin) return VIDO_E_INVALID;
+    if (!ctx) return VIDO_E_INVALID;
+    if (!ctx->bawin) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_push_frame: no window (vido_bawin_create first)");
     BaWin* B = ctx->bawin;
     if (frame < 0 || n < 0 || n > B->cap_n || (n && (!meas || !xyz))) return vido_set_error(ctx, n > B->cap_n ? VIDO_E_CAPACITY : VIDO_E_INVALID, "bawin_push_frame: %d features (capacity %d)", n, B->cap_n);
     hipStream_t st = ctx->stream; const int s = frame % B->cap_f;
@@ -248,7 +250,8 @@ int vido_bawin_push_frame(vido_ctx* ctx, int frame, int n, const double* meas, c
  * frames that have left the ring are ignored. */
 int vido_bawin_set_labels(vido_ctx* ctx, int n, const int32_t* quads)
 {
-    if (!ctx || !ctx->bawin) return VIDO_E_INVALID;
+    if (!ctx) return VIDO_E_INVALID;
+    if (!ctx->bawin) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_set_labels: no window (vido_bawin_create first)");
     BaWin* B = ctx->bawin;
     if (n < 0 || (n && !quads)) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_set_labels: bad arguments");
     hipStream_t st = ctx->stream;
@@ -257,9 +260,15 @@ int vido_bawin_set_labels(vido_ctx* ctx, int n, const int32_t* quads)
         const int m = std::min(per, n - a);
         HIP_TRY(ctx, hipStreamSynchronize(st));
         int* h = (int*)B->h_stage; int k = 0;
+        // k_bawin_labels stores a chunk's quads in no particular order, so a (frame, feature) pair is staged once per chunk: a later quad of the pair overwrites the staged
+        // one (the last quad holds; chunks follow each other on the stream).  lab_at[row] = (chunk stamp, staged index): one table lookup per quad, nothing to clear
+        const unsigned stamp = ++B->lab_stamp;
         for (int i = 0; i < m; i++) {
             const int32_t* q = quads + 4 * (size_t)(a + i);
             if (q[0] < 0 || B->frame_of[q[0] % B->cap_f] != q[0] || q[1] < 0 || q[1] >= B->nfeat[q[0] % B->cap_f]) continue;
+            std::pair<unsigned, int>& at = B->lab_at[(size_t)(q[0] % B->cap_f) * B->cap_n + q[1]];
+            if (at.first == stamp) { h[4 * at.second + 2] = q[2]; h[4 * at.second + 3] = q[3]; continue; }
+            at.first = stamp; at.second = k;
             h[4 * k] = q[0]; h[4 * k + 1] = q[1]; h[4 * k + 2] = q[2]; h[4 * k + 3] = q[3]; k++;
         }
         if (!k) continue;
@@ -275,7 +284,8 @@ int vido_bawin_set_labels(vido_ctx* ctx, int n, const int32_t* quads)
  * been written into the ring's xyz rows; n_obs_out / n_pt_out: size of the graph that was solved. */
 int vido_bawin_solve(vido_ctx* ctx, int start, int N, vido_ba_problem* prob, vido_ba_result* res, int32_t* n_obs_out, int32_t* n_pt_out)
 {
-    if (!ctx || !ctx->bawin) return VIDO_E_INVALID;
+    if (!ctx) return VIDO_E_INVALID;
+    if (!ctx->bawin) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_solve: no window (vido_bawin_create first)");
     BaWin* B = ctx->bawin;
     if (!prob || !res || start < 0 || N <= start || N - start >= B->cap_f || prob->n_cam != N - start) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_solve: bad window [%d, %d)", start, N);
     for (int f = start; f < N; f++) if (B->frame_of[f % B->cap_f] != f) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_solve: frame %d is not in the ring", f);
@@ -306,7 +316,8 @@ int vido_bawin_solve(vido_ctx* ctx, int start, int N, vido_ba_problem* prob, vid
 /* The world points of one stored frame (the Map's vp3DPointSta row as the solves have left it): xyz_out [n][3] f32. */
 int vido_bawin_read_points(vido_ctx* ctx, int frame, int n, float* xyz_out)
 {
-    if (!ctx || !ctx->bawin) return VIDO_E_INVALID;
+    if (!ctx) return VIDO_E_INVALID;
+    if (!ctx->bawin) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_read_points: no window (vido_bawin_create first)");
     BaWin* B = ctx->bawin;
     if (frame < 0 || B->frame_of[frame % B->cap_f] != frame || n < 0 || n > B->nfeat[frame % B->cap_f] || (n && !xyz_out)) return vido_set_error(ctx, VIDO_E_INVALID, "bawin_read_points: frame %d is not in the ring", frame);
     if (!n) return VIDO_OK;

@@ -747,22 +747,31 @@ def _ba_dynamic_struct(d):
     return s, b
 
 
-def ba_optimize(ctx, k, rank=0, world=1, shard=None, allreduce=None, dynamic=None):
-    """Mirror of Optimizer::PartialBatchOptimization / FullBatchOptimization (Optimizer.h:30-31) on the flat problem
-    dict built by vido_slam_amd.problems.synth_ba_problem (or by the C++ facade from Map).  Returns the updated
-    poses/points and LM statistics.  With world > 1 every rank calls this with its (rank, shard) and the hook."""
-    a = dict(cam_T=np.array(k["cam_T"], np.float64).reshape(-1, 12).copy(), pt_xyz=np.array(k["pt_xyz"], np.float64).reshape(-1, 3).copy(),
-             obs_cam=np.ascontiguousarray(k["obs_cam"], np.int32), obs_pt=np.ascontiguousarray(k["obs_pt"], np.int32),
-             obs_meas=np.ascontiguousarray(k["obs_meas"], np.float64).reshape(-1, 3), odo_i=np.ascontiguousarray(k["odo_i"], np.int32),
+def _ba_problem_struct(k, graph=True):
+    """The flat problem dict -> (BaProblem, the arrays it points into).  cam_T / pt_xyz are COPIES that the solver updates.  graph=False: the cameras, odometry factors, prior,
+    weights and LM parameters only; the observation / point fields stay empty (vido_bawin_solve takes them from the ring)."""
+    a = dict(cam_T=np.array(k["cam_T"], np.float64).reshape(-1, 12).copy(), odo_i=np.ascontiguousarray(k["odo_i"], np.int32),
              odo_j=np.ascontiguousarray(k["odo_j"], np.int32), odo_T=np.ascontiguousarray(k["odo_T"], np.float64).reshape(-1, 12))
     p = BaProblem()
-    p.n_cam, p.n_pt, p.n_obs, p.n_odo = k["n_cam"], k["n_pt"], len(a["obs_cam"]), len(a["odo_i"])
+    if graph:
+        a.update(pt_xyz=np.array(k["pt_xyz"], np.float64).reshape(-1, 3).copy(), obs_cam=np.ascontiguousarray(k["obs_cam"], np.int32),
+                 obs_pt=np.ascontiguousarray(k["obs_pt"], np.int32), obs_meas=np.ascontiguousarray(k["obs_meas"], np.float64).reshape(-1, 3))
+        p.n_pt, p.n_obs = k["n_pt"], len(a["obs_cam"])
+    p.n_cam, p.n_odo = k["n_cam"], len(a["odo_i"])
     p.prior_cam, p.use_huber, p.max_iters = k["prior_cam"], k["use_huber"], k["max_iters"]
-    for name in ("cam_T", "pt_xyz", "obs_cam", "obs_pt", "obs_meas", "odo_i", "odo_j", "odo_T"):
+    for name in a:
         setattr(p, name, a[name].ctypes.data)
     p.prior_T[:] = list(np.asarray(k["prior_T"], np.float64).reshape(12))
     for name in ("info_obs", "info_odo", "info_prior", "huber_obs", "huber_odo", "gain_threshold"):
         setattr(p, name, float(k[name]))
+    return p, a
+
+
+def ba_optimize(ctx, k, rank=0, world=1, shard=None, allreduce=None, dynamic=None):
+    """Mirror of Optimizer::PartialBatchOptimization / FullBatchOptimization (Optimizer.h:30-31) on the flat problem
+    dict built by vido_slam_amd.problems.synth_ba_problem (or by the C++ facade from Map).  Returns the updated
+    poses/points and LM statistics.  With world > 1 every rank calls this with its (rank, shard) and the hook."""
+    p, a = _ba_problem_struct(k)
     lo, hi = shard if shard is not None else (0, 0)
     p.pt_lo, p.pt_hi, p.rank, p.world = lo, hi, rank, world
     r = BaResult()
@@ -781,6 +790,43 @@ def ba_optimize(ctx, k, rank=0, world=1, shard=None, allreduce=None, dynamic=Non
     return dict(cam_T=a["cam_T"].reshape(-1, 3, 4), pt_xyz=a["pt_xyz"], iterations=r.iterations, lm_trials=r.lm_trials,
                 chi2_initial=r.chi2_initial, chi2_final=r.chi2_final, lambda_final=r.lambda_final, ms_setup=r.ms_setup,
                 ms_solve_loop=r.ms_solve_loop, ms_linearize_kernel=r.ms_linearize_kernel, ms_schur_kernel=r.ms_schur_kernel, **extra)
+
+
+class BaWindow:
+    """The local-BA window resident on the device (vido_bawin_*, csrc/bawin.hip): a ring of `cap_frames` frames with up to `cap_features` static features each.  One per
+    context; creating another drops the stored frames.  Every method raises VidoError with the library's code and message."""
+
+    def __init__(self, ctx, cap_frames, cap_features):
+        self.ctx = ctx
+        self.create(cap_frames, cap_features)
+
+    def create(self, cap_frames, cap_features):
+        self.ctx._check(self.ctx.lib.vido_bawin_create(self.ctx.h, int(cap_frames), int(cap_features)))
+
+    def push_frame(self, frame, meas, xyz, asso=None):
+        """meas [n][3] f64, xyz [n][3] f32, asso [n] i32 or None (every feature unassociated)"""
+        meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3); xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        asso = None if asso is None else np.ascontiguousarray(asso, np.int32)
+        self.ctx._check(self.ctx.lib.vido_bawin_push_frame(self.ctx.h, int(frame), len(meas), _ptr(meas), _ptr(xyz), _ptr(asso)))
+
+    def set_labels(self, quads):
+        """quads [n][4] i32: (frame, feature, tracklet, position); applied in the order given"""
+        q = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+        self.ctx._check(self.ctx.lib.vido_bawin_set_labels(self.ctx.h, len(q), _ptr(q)))
+
+    def solve(self, start, N, k):
+        """PartialBatchOptimization over the frames [start, N); k: the flat problem dict without its observation / point fields.  Returns the refined cameras, the LM
+        statistics and the size of the graph that was solved; the refined landmarks stay in the ring (read_points)."""
+        p, a = _ba_problem_struct(k, graph=False)
+        r = BaResult(); no = C.c_int32(-1); npt = C.c_int32(-1)
+        self.ctx._check(self.ctx.lib.vido_bawin_solve(self.ctx.h, int(start), int(N), C.byref(p), C.byref(r), C.byref(no), C.byref(npt)))
+        return dict(cam_T=a["cam_T"].reshape(-1, 3, 4), n_obs=no.value, n_pt=npt.value, iterations=r.iterations, lm_trials=r.lm_trials, chi2_initial=r.chi2_initial,
+                    chi2_final=r.chi2_final, lambda_final=r.lambda_final, ms_setup=r.ms_setup, ms_solve_loop=r.ms_solve_loop)
+
+    def read_points(self, frame, n):
+        out = np.empty((int(n), 3), np.float32)
+        self.ctx._check(self.ctx.lib.vido_bawin_read_points(self.ctx.h, int(frame), int(n), _ptr(out)))
+        return out
 
 
 def pnp_ransac(ctx, pts3d, pts2d, K, max_iters=500, reproj_err=0.4, confidence=0.98, seed=1):
