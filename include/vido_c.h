@@ -236,6 +236,37 @@ int vido_dis_flow_pair(vido_ctx* ctx, const uint8_t* img0, const uint8_t* img1, 
                        float* flow_out /* [h*w*2] marked, NULL ok */, int32_t* fwd_q8_out /* [h*w*2], NULL ok */, int32_t* bwd_q8_out /* [h*w*2], NULL ok */,
                        uint8_t* status_out /* [h*w], NULL ok */, int32_t* stats_out /* [12]: forward 4, backward 4, check 4; NULL ok */, int on_device);
 
+/* Semi-global stereo matching of a rectified pair: the disparity of every pixel of `left` against `right` to 1/16 px, entirely in integers (the reference receives such a
+ * disparity from outside, Tracking.cc:305-309; defined by tests/refimpl/stereo_sgm_np.py, exact to the bit).  16 <= width, height <= 4095; channels, rgb_order and stride
+ * as in vido_dis_flow; D = max_disp a multiple of 16 with 16 <= D <= 256 and width * height * D <= 2^28; 0 <= p1 <= p2 <= 1000; 0 <= uniqueness <= 99; 0 <= lr_tol <= 255;
+ * VIDO_E_INVALID otherwise, for a NULL image and when all four outputs are NULL.  Needs no extractor state and not the context's configured frame size.  In the order the
+ * rules apply:
+ *   grey        1 channel: the bytes; else (1868 B + 9617 G + 4899 R + 8192) >> 14
+ *   census      window 9 wide x 7 high around the pixel, coordinates clamped to the image; the 62 neighbours row-major, the centre skipped; bit = neighbour < centre:
+ *               a 64-bit word cL / cR per pixel of each image
+ *   cost        C(x, y, d) = popcount(cL(x, y) ^ cR(x - d, y)) for 0 <= d < D and x - d >= 0; C = 64 where x - d < 0
+ *   paths       eight directions r = (+-1, 0), (0, +-1), (+-1, +-1).  L_r(p, d) = C(p, d) at every pixel whose predecessor p - r lies outside the image (diagonal paths
+ *               restart at the side columns).  Elsewhere, with m = min_k L_r(p - r, k): L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + p1,
+ *               L_r(p - r, d + 1) + p1, m + p2) - m; a d +- 1 outside [0, D) is no candidate.  S = sum_r L_r.  L <= 64 + p2 <= 1064, S <= 8512
+ *   winner      d0 = argmin_d S(x, y, d), the lowest d on ties; s0 = S(d0)
+ *   right view  dR(x, y) = argmin_d S(x + d, y, d) over the d with x + d <= width - 1, the lowest d on ties
+ *   sub-pixel   sm = S(d0 - 1), sp = S(d0 + 1), den = sm + sp - 2 s0; off = rdiv(8 (sm - sp), den) when 1 <= d0 <= D - 2 and den > 0, else 0 (rdiv as in
+ *               vido_dis_flow: to the nearest, halves away from zero; |off| <= 8); q4 = 16 d0 + off, in 1/16 px
+ *   status      2 (left-right) x - d0 < 0 or |dR(x - d0, y) - d0| > lr_tol; else 1 (not unique) (100 - uniqueness) S2 <= 100 s0, S2 = min S(d) over |d - d0| > 1;
+ *               else 3 (zero disparity) q4 <= 0; else 0
+ * q4_out [h*w] = q4 of every pixel, whatever its status; disp_out [h*w] = q4 / 16 in pixels (exact) where the status is 0, -1 elsewhere (vido_frame_upload turns a
+ * negative raw depth into 0 and the lists drop depth 0: the front end's own "no depth"); status_out [h*w]; stats_out [4] = the count of each status (zeroed by the call).
+ * With the KITTI ChooseData code, DepthMapFactor 1 and Camera.bf = fx * baseline, the front end turns disp_out into metres as it does a KITTI disparity image
+ * (bf / (raw / DepthMapFactor)).  Any output may be NULL, not all.  on_device != 0: every pointer is a device pointer (disp_out, q4_out and stats_out 4-byte aligned) and
+ * the call only enqueues on the ctx stream (vido_set_stream's when one is set): five launches, no host synchronisation, so a call can sit inside a stream
+ * capture — except the first call of a size, which grows the op's own scratch (two grey planes, two census planes and the u16 S volume; shared with no other op).
+ * Otherwise the images and outputs are the caller's host arrays, staged through pinned buffers that grow on demand, and the call returns when the results are there.
+ * A result depends on nothing but the two images and the five parameters: the eight paths add into S with integer atomics, whose sums do not depend on the order. */
+int vido_stereo_sgm(vido_ctx* ctx, const uint8_t* left, const uint8_t* right, int channels, int rgb_order, int stride, int width, int height,
+                    int max_disp, int p1, int p2, int uniqueness, int lr_tol,
+                    float* disp_out /* [h*w], NULL ok */, int32_t* q4_out /* [h*w], NULL ok */, uint8_t* status_out /* [h*w], NULL ok */,
+                    int32_t* stats_out /* [4], NULL ok */, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device

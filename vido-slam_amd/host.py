@@ -362,6 +362,32 @@ class Context:
         self._check(self.lib.vido_dis_flow_pair(self.h, img0_ptr, img1_ptr, int(channels), int(rgb_order), int(stride), int(width), int(height), int(coarsest), int(iters),
                                                 int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), flow_ptr, fwd_ptr, bwd_ptr, status_ptr, stats_ptr, 1))
 
+    def stereo_sgm(self, left, right, max_disp=128, p1=10, p2=120, uniqueness=10, lr_tol=1, rgb_order=0):
+        """Semi-global matching of a rectified pair (vido_stereo_sgm; the statement is tests/refimpl/stereo_sgm_np.py): u8 H x W or H x W x 3|4 host arrays of one shape (a
+        row stride above the width is taken from the array's strides).  9 x 7 census, Hamming cost, eight paths with penalties p1 / p2 over max_disp disparities (a multiple
+        of 16 in 16..256), sub-pixel winner, left-right (lr_tol), uniqueness (percent) and zero-disparity verdicts, all in integers.  Returns (disp (H,W) f32 in pixels where
+        the status is 0 and -1 elsewhere, q4 (H,W) i32 = the disparity of every pixel in 1/16 px, status (H,W) u8: 0 valid, 1 not unique, 2 left-right, 3 zero disparity,
+        stats (4,) i32 = the count of each status).  Metres: depth = fx * baseline / disp; the front end does that division itself when the settings name the KITTI
+        ChooseData code (facade.cpp:876), DepthMapFactor: 1 and Camera.bf = fx * baseline, and takes disp as the depth image (-1 is its "no depth")."""
+        left, right = np.asarray(left), np.asarray(right)
+        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.shape != right.shape or left.ndim not in (2, 3):
+            raise VidoError(-1, "stereo_sgm: two u8 images of one shape, H x W or H x W x C, expected")
+        cn = 1 if left.ndim == 2 else left.shape[2]
+        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
+        if not rows(left) or not rows(right) or left.strides[0] != right.strides[0]:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+        h, w = left.shape[:2]
+        disp = np.empty((h, w), np.float32); q4 = np.empty((h, w), np.int32); status = np.empty((h, w), np.uint8); stats = np.empty(4, np.int32)
+        self._check(self.lib.vido_stereo_sgm(self.h, left.ctypes.data, right.ctypes.data, cn, int(rgb_order), left.strides[0], w, h, int(max_disp), int(p1), int(p2),
+                                             int(uniqueness), int(lr_tol), _ptr(disp), _ptr(q4), _ptr(status), _ptr(stats), 0))
+        return disp, q4, status, stats
+
+    def stereo_sgm_device(self, left_ptr, right_ptr, channels, stride, width, height, max_disp=128, p1=10, p2=120, uniqueness=10, lr_tol=1, rgb_order=0, disp_ptr=None,
+                          q4_ptr=None, status_ptr=None, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the op's scratch); any output pointer may be None, not all."""
+        self._check(self.lib.vido_stereo_sgm(self.h, left_ptr, right_ptr, int(channels), int(rgb_order), int(stride), int(width), int(height), int(max_disp), int(p1), int(p2),
+                                             int(uniqueness), int(lr_tol), disp_ptr, q4_ptr, status_ptr, stats_ptr, 1))
+
     def orb_timing(self):
         t = np.zeros(8, np.float32)
         self._check(self.lib.vido_orb_last_timing(self.h, _ptr(t)))

@@ -822,6 +822,44 @@ class HipOps:
                    int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10), int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), _p(out), _p(fwd_q8), _p(bwd_q8), _p(status), _p(stats), 1)
         return out
 
+    def stereo_sgm(self, left, right, out=None, q4=None, status=None, stats=None, max_disp=128, p1=10, p2=120, uniqueness=10, lr_tol=1, rgb_order=0):
+        """vido_stereo_sgm on device tensors: left, right uint8 [H,W] or [H,W,3|4] of one shape (a rectified pair) -> the disparity of left's pixels, float32 [H,W] in pixels
+        where the status is 0 and -1 elsewhere (`out`, or a new tensor).  q4: an int32 [H,W] tensor that receives every pixel's disparity in 1/16 px, or None; status: a
+        uint8 [H,W] tensor that receives 0 valid / 1 not unique / 2 left-right / 3 zero disparity, or None; stats: an int32 tensor of >= 4 elements that receives the four
+        counts, or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/stereo_sgm_np.py.  Enqueued on torch's current stream, nothing is waited for;
+        the first call of a size grows the op's scratch, so it comes before a graph capture.  The argument checks are dis_flow's: CPU tensors, other dtypes or shapes and
+        non-contiguous tensors raise."""
+        from ..host import VidoError
+        def bad(why):
+            raise VidoError(-1, "stereo_sgm: " + why)
+        for name, t, dt in (("left", left, torch.uint8), ("right", right, torch.uint8), ("out", out, torch.float32), ("q4", q4, torch.int32), ("status", status, torch.uint8),
+                            ("stats", stats, torch.int32)):
+            if t is None and name not in ("left", "right"):
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != left.device:
+                bad("%s is on another device than left" % name)
+        if left.dim() not in (2, 3) or (left.dim() == 3 and left.shape[2] not in (3, 4)):
+            bad("left must be [H, W] or [H, W, 3|4], got %s" % (tuple(left.shape),))
+        if tuple(right.shape) != tuple(left.shape):
+            bad("right must have left's shape %s, got %s" % (tuple(left.shape), tuple(right.shape)))
+        H, W = int(left.shape[0]), int(left.shape[1]); cn = 1 if left.dim() == 2 else int(left.shape[2])
+        if out is None:
+            out = torch.empty((H, W), device=left.device, dtype=torch.float32)
+        for name, t in (("out", out), ("q4", q4), ("status", status)):
+            if t is not None and tuple(t.shape) != (H, W):
+                bad("%s must be [%d, %d], got %s" % (name, H, W, tuple(t.shape)))
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        self._call(self.ctx.lib.vido_stereo_sgm, left.data_ptr(), right.data_ptr(), cn, int(rgb_order), W * cn, W, H, int(max_disp), int(p1), int(p2), int(uniqueness), int(lr_tol),
+                   out.data_ptr(), _p(q4), _p(status), _p(stats), 1)
+        return out
+
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
         """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
         (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),

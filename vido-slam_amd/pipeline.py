@@ -231,15 +231,26 @@ class NetNodes:
     from one pyramid build, and every vector whose backward flow does not bring it back, or whose target leaves the image, is NaN.  The front end drops a NaN vector by
     failing comparisons, and vido_mask_propagate defines a NaN source as not voting — which is what an occluded pixel should do: it has no counterpart in the next frame,
     so it carries no label there.  flow_status: the uint8 HxW status image of the last frame (0 consistent, 1 inconsistent, 2 leaves the image, 3 not a flow), valid in
-    stream order with the flow; None when off.  Anything else raises ValueError before anything is built, and so does dis_consistency with flow_source = "net"."""
+    stream order with the flow; None when off.  Anything else raises ValueError before anything is built, and so does dis_consistency with flow_source = "net".
+
+    depth_source = "stereo" (default "net": MonoDepth2, and nothing below applies): the depth is HipOps.stereo_sgm of the frame and its rectified right view
+    (csrc/stereosgm.hip; stereo_params: a dict of max_disp / p1 / p2 / uniqueness / lr_tol, the op's defaults otherwise) on the detector's context and
+    the depth stream, captured into g_depth like MonoDepth2.  MonoDepth2 is neither constructed nor launched (depth_net is None).  infer() then needs right_bgr, and the
+    depth it returns is the op's disp_out: the disparity in pixels where the match is valid, -1 elsewhere.  That image is metric once the tracker knows the rig: with the
+    KITTI ChooseData code (facade.cpp:876: the depth image is a disparity), DepthMapFactor: 1 and Camera.bf = fx * baseline in the settings, the front end computes
+    bf / disparity metres and treats -1 as "no depth".  stereo_status: the uint8 HxW status image of the last frame (0 valid, 1 not unique, 2 left-right, 3 zero
+    disparity), valid in stream order with the depth; None with "net".  Anything else raises ValueError before anything is built, and so do stereo_params with
+    depth_source = "net" and a right_bgr handed to infer() under "net"."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
-                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None):
+                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None, depth_source="net", stereo_params=None):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
+        self.depth_source, self.stereo_params = self._check_depth_source(depth_source, stereo_params)
+        self.stereo_status = None
         self.flow_source, self.dis_params = self._check_flow_source(flow_source, dis_params)
         self.dis_consistency = self._check_dis_consistency(dis_consistency, flow_source)
         self.flow_status = None
@@ -271,7 +282,7 @@ class NetNodes:
         self.flow_net = None if self.flow_source == "dis" else _nets.fill_deterministic(
             _nets.LiteFlowNet(self.ops_flow.correlation, epilogue=self.ops_flow.bias_act_, warp=self.ops_flow.backwarp, fused=None if _os.environ.get("VIDO_LFN_NO_FUSED") else self.ops_flow,
                               pair_batch=not _os.environ.get("VIDO_LFN_NO_PAIR_BATCH")), seed).eval().to(dev)
-        self.depth_net = _nets.fill_deterministic(_nets.MonoDepth2(), seed + 1).eval().to(dev)
+        self.depth_net = None if self.depth_source == "stereo" else _nets.fill_deterministic(_nets.MonoDepth2(), seed + 1).eval().to(dev)
         self.mask_net = _nets.fill_maskrcnn(_nets.MaskRCNN(ops), seed + 2).eval().to(dev)
         if label_mode == "instance" and self.mask_net.config.detections_per_img > self.ID_BASES[1]:
             raise ValueError("label_mode='instance': detections_per_img = %d, each id range holds %d" % (self.mask_net.config.detections_per_img, self.ID_BASES[1]))
@@ -295,7 +306,7 @@ class NetNodes:
                 self.score_scale = _nets.calibrate_detector_scores(self.mask_net, _nets.maskrcnn.image_to_feed(cal, dev, mask_feed, ops=ops))
         self.folded = 0
         if optimize:
-            self.folded = _nets.fold_batchnorm(self.depth_net, ops) + _nets.fold_batchnorm(self.mask_net, ops)
+            self.folded = (0 if self.depth_net is None else _nets.fold_batchnorm(self.depth_net, ops)) + _nets.fold_batchnorm(self.mask_net, ops)
         # streams: False = the three networks back to back on the caller's stream; True = one stream each; "depth" = MonoDepth2 alone on a side stream (its ~120 launches of a
         # few microseconds leave most CUs idle: next to the detector's convolutions they cost next to nothing, while three full networks side by side evict each other's L2 sets)
         if isinstance(streams, str):                              # e.g. "depth", "flow", "flow+depth" (those networks share ONE side stream), "flow,depth" (a side stream each)
@@ -320,6 +331,11 @@ class NetNodes:
         else:
             self._flow_fn = lambda a, b: _nets.analyse_flow(self.flow_net, a, b)
         self._depth_fn = lambda a: _nets.analyse_depth(self.depth_net, a, feed=self.depth_feed, ops=ops).to(torch.float32)
+        dex = [ex]
+        if self.depth_source == "stereo":                             # the op on (left, right); the status image is the nodes' own buffer, written by eager calls and replays alike
+            self.stereo_status = torch.zeros((height, width), dtype=torch.uint8, device=dev)
+            self._depth_fn = lambda a, b: ops.stereo_sgm(a, b, status=self.stereo_status, **self.stereo_params)
+            dex = [ex, ex]                                            # (its first call of the size, below, grows the op's scratch: before any capture)
         self._trunk_fn = lambda a: self.mask_net.trunk(_nets.maskrcnn.image_to_feed(a, dev, self.mask_feed, ops=ops))
         # the whole detector with static shapes (nets/maskrcnn.py: heads_static / analyse_image_static): trunk + device-side RPN selection + box head + fixed-slot
         # post-processing + mask head + label image, no host synchronisation -> ONE hipGraph; returns (mask i32 HxW, labels [cap], n_labels, n_det)
@@ -331,7 +347,7 @@ class NetNodes:
         self._det_fn = _det_fn
         with torch.no_grad():
             for _ in range(2):                                          # first calls: MIOpen compiles / finds its kernels
-                self._flow_fn(ex, ex); self._depth_fn(ex); self._trunk_fn(ex)
+                self._flow_fn(ex, ex); self._depth_fn(*dex); self._trunk_fn(ex)
             # the mask head's detection-count buckets: every batch size its convolutions will ever see is compiled now, not in the middle of a sequence
             mh = self.mask_net.roi_heads.mask
             feats = self.mask_net.trunk(_nets.maskrcnn.image_to_feed(ex, dev, self.mask_feed, ops=ops))[0][:4]
@@ -341,7 +357,7 @@ class NetNodes:
             if graphs:
                 try:
                     self.g_flow = _nets.Graphed(self._flow_fn, [ex, ex])
-                    self.g_depth = _nets.Graphed(self._depth_fn, [ex])
+                    self.g_depth = _nets.Graphed(self._depth_fn, dex)
                     self.g_trunk = _nets.Graphed(self._trunk_fn, [ex])
                     if not _os.environ.get("VIDO_NO_MASK_GRAPHS"):
                         mh.capture_buckets(self.g_trunk.static_out[0][:4], _nets.Graphed)      # the mask head per detection-count bucket, over the trunk's static feature maps
@@ -359,8 +375,9 @@ class NetNodes:
                         torch.cuda.synchronize()
 
     @torch.no_grad()
-    def infer(self, prev_bgr, cur_bgr, range_words=None):
-        """prev_bgr / cur_bgr: u8 HxWx3 device tensors.  Returns (flow HxWx2 f32, depth HxW f32, mask HxW i32, labels, events): work enqueued on the caller's stream after
+    def infer(self, prev_bgr, cur_bgr, range_words=None, right_bgr=None):
+        """prev_bgr / cur_bgr: u8 HxWx3 device tensors; right_bgr: with depth_source="stereo" the rectified right view of cur_bgr, u8 HxWx3 (required; the depth returned
+        is then the op's disparity image, see the class docstring), with "net" it must be None.  Returns (flow HxWx2 f32, depth HxW f32, mask HxW i32, labels, events): work enqueued on the caller's stream after
         this call sees the complete outputs (the caller's stream waits for the side stream's events); another stream or the host waits for the three events.
         label_mode="instance": the mask holds per-frame instance ids above this frame's id base (self.id_base: ID_BASES alternate frame by frame), labels[id - id_base - 1]
         is an id's class.
@@ -369,6 +386,8 @@ class NetNodes:
         readable on the host once the caller's stream has passed this point."""
         if self._ids is not None and getattr(self, "skip_detector", False):
             raise ValueError("stable_ids with skip_detector: a frame without a detector image would leave the carried image and the id state behind the sequence")
+        if (right_bgr is None) == (self.depth_source == "stereo"):
+            raise ValueError("right_bgr: required with depth_source='stereo' and only there (depth_source=%r, right_bgr %s)" % (self.depth_source, "missing" if right_bgr is None else "given"))
         cur = torch.cuda.current_stream()
         ss = [s or cur for s in self.streams] if self.streams else [cur, cur, cur]
         for s in ss:
@@ -378,7 +397,7 @@ class NetNodes:
             flow = (self.g_flow or self._flow_fn)(prev_bgr, cur_bgr)
             e0 = torch.cuda.Event(); e0.record()
         with torch.cuda.stream(ss[1]):
-            depth = (self.g_depth or self._depth_fn)(cur_bgr)
+            depth = (self.g_depth or self._depth_fn)(cur_bgr) if right_bgr is None else (self.g_depth or self._depth_fn)(cur_bgr, right_bgr)
             e1 = torch.cuda.Event(); e1.record()
         det_frame = self.detect_every == 1 or self._calls % self.detect_every == 0
         self._calls += 1
@@ -441,6 +460,17 @@ class NetNodes:
             range_words.zero_()
             self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
+
+    DEPTH_SOURCES = ("net", "stereo")
+    STEREO_PARAMS = ("max_disp", "p1", "p2", "uniqueness", "lr_tol")
+
+    @classmethod
+    def _check_depth_source(cls, depth_source, stereo_params):
+        if depth_source not in cls.DEPTH_SOURCES:
+            raise ValueError("depth_source: one of %s, not %r" % (cls.DEPTH_SOURCES, depth_source))
+        if stereo_params is not None and (depth_source != "stereo" or not isinstance(stereo_params, dict) or any(k not in cls.STEREO_PARAMS for k in stereo_params)):
+            raise ValueError("stereo_params: with depth_source='stereo', a dict with keys among %s, not %r" % (cls.STEREO_PARAMS, stereo_params))
+        return depth_source, dict(stereo_params or {})
 
     FLOW_SOURCES = ("net", "dis")
     DIS_PARAMS = ("coarsest", "iters", "max_shift_q8", "min_eig")
@@ -549,12 +579,12 @@ class NetNodes:
         return out
 
     @torch.no_grad()
-    def infer_checked(self, prev_bgr, cur_bgr):
+    def infer_checked(self, prev_bgr, cur_bgr, right_bgr=None):
         """infer() for callers outside EndToEnd, with this frame's range check: infer, wait for the caller's stream, and when a context tripped raise (on_range="raise") or
         recompute the tripped networks (on_range="recompute", see recompute()).  Returns infer()'s tuple; its events are recorded after any recomputation."""
         if self._range_words is None:
             self._range_words = torch.zeros((2,), dtype=torch.int32).pin_memory()
-        flow, depth, mask, labels, evs = self.infer(prev_bgr, cur_bgr, range_words=self._range_words)
+        flow, depth, mask, labels, evs = self.infer(prev_bgr, cur_bgr, range_words=self._range_words, right_bgr=right_bgr)
         torch.cuda.current_stream().synchronize()
         hit_flow, hit_det = bool(self._range_words[0]), bool(self._range_words[1])
         if not (hit_flow or hit_det):
@@ -641,6 +671,9 @@ class EndToEnd:
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         self.dev = [dict(bgr=mk((h, w, 3), torch.uint8), flow=mk((h, w, 2), torch.float32), depth=mk((h, w), torch.float32), mask=mk((h, w), torch.int32),
                          gflow=mk((h, w, 2), torch.float32), gdepth=mk((h, w), torch.float32), gmask=mk((h, w), torch.int32)) for _ in range(self.RING)]
+        if getattr(nodes, "depth_source", "net") == "stereo":          # the right view of every frame in flight: a pinned and a device buffer per ring slot
+            for hb, db in zip(self.host, self.dev):
+                hb["right"] = pin((h, w, 3), torch.uint8); db["right"] = mk((h, w, 3), torch.uint8)
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.q = _queue.Queue(maxsize=1)      # the networks run at most one frame ahead of the tracker (+ the one in flight)
         self.poses, self.stats, self.err = [], [], None
@@ -741,11 +774,16 @@ class EndToEnd:
             self.net_stream.synchronize()
 
     @torch.no_grad()
-    def push(self, bgr, given=None):
-        """bgr: HxWx3 u8 numpy.  given = (depth f32 HxW raw sensor units, flow f32 HxWx2, mask i32 HxW) for feed == "given" (copied: the caller's arrays are not modified,
+    def push(self, bgr, given=None, right=None):
+        """bgr: HxWx3 u8 numpy.  right: HxWx3 u8 numpy, the rectified right view of bgr — with NetNodes(depth_source="stereo") only, where it is required: it is uploaded next
+        to the frame and the depth parked in the ring is the stereo op's disparity image (metres in the tracker through the KITTI ChooseData code, DepthMapFactor: 1 and
+        Camera.bf = fx * baseline: NetNodes' docstring).  given = (depth f32 HxW raw sensor units, flow f32 HxWx2, mask i32 HxW) for feed == "given" (copied: the caller's arrays are not modified,
         although the tracker rescales the depth map it is handed in place)."""
         if self.err is not None:
             raise self.err
+        stereo = getattr(self.nodes, "depth_source", "net") == "stereo"
+        if (right is None) == stereo:
+            raise ValueError("right: required with NetNodes(depth_source='stereo') and only there")
         t0 = _time.perf_counter()
         self.net_stream = torch.cuda.current_stream()
         slot = self.k % self.RING
@@ -754,6 +792,9 @@ class EndToEnd:
         cur = db["bgr"]
         cur.copy_(hb["bgr"], non_blocking=True)                          # the only upload of the frame on the network side
         img_ev = torch.cuda.Event(); img_ev.record()                     # the image is on the device: all the tracker's ORB extraction needs (prefetched in _track_loop)
+        if stereo:
+            hb["right"].numpy()[...] = right
+            db["right"].copy_(hb["right"], non_blocking=True)
         if given is not None:
             hb["depth"].numpy()[...] = given[0]; hb["flow"].numpy()[...] = given[1]; hb["mask"].numpy()[...] = given[2]
             if self.handover == "device":                                # the stand-in maps go up next to the frame (feed == "nets" uploads nothing but the frame)
@@ -762,7 +803,10 @@ class EndToEnd:
                 hb["given"] = (hb["depth"].numpy().copy(), hb["flow"].numpy().copy(), hb["mask"].numpy().copy())
         prev = cur if self.prev is None else self.prev                   # first frame: RunNet has no previous image yet; the tracker ignores the flow of frame 0's predecessor
         with self.net_lock:
-            flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None)
+            if stereo:
+                flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None, right_bgr=db["right"])
+            else:
+                flow, depth, mask, labels, evs = self.nodes.infer(prev, cur, range_words=hb["range"] if self.nodes.on_range == "recompute" else None)
             hb["id_base"] = self.nodes.id_base                           # (label_mode="instance": a later recomputation of this frame paints under the same ids)
             hb["propagated"] = bool(getattr(self.nodes, "last_propagated", False))      # (detect_every > 1: the mask was warped from the frame before, no detector ran)
         # graph outputs are static buffers that the next replay overwrites: park them in this slot's device buffers (three device-to-device copies of 4.8 MB in stream order)

@@ -155,6 +155,17 @@ class Scene3D:
         g8 = np.clip(np.rint(gray), 0, 255).astype(np.uint8)
         return g8, depth, flow, mask
 
+    def stereo_frame(self, k, baseline):
+        """A rectified pair at frame k: (left u8, right u8, depth f32, mask i32).  left, depth and mask are frame(k)'s; right is frame(k) rendered from the poses
+        right-multiplied by a translation of `baseline` metres along camera x (the second camera sits to the right of the first, same orientation, same K).  A surface
+        point at depth z in the left view at column x lies at column x - fx * baseline / z of the right view: the true disparity is K[0] * baseline / depth."""
+        import copy
+        left, depth, _, mask = self.frame(k)
+        Tb = np.eye(4); Tb[0, 3] = float(baseline)
+        other = copy.copy(self)
+        other.poses = [P @ Tb for P in self.poses]
+        return left, other.frame(k)[0], depth, mask
+
 
 def convoy_scene(n_frames, w=640, h=480, seed=5, step=0.25):
     """BASELINE configs[1]-[3] chained: a 640x480 Scene3D with FIVE dynamic objects that drive ahead of the camera at roughly its own
