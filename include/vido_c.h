@@ -267,6 +267,31 @@ int vido_stereo_sgm(vido_ctx* ctx, const uint8_t* left, const uint8_t* right, in
                     float* disp_out /* [h*w], NULL ok */, int32_t* q4_out /* [h*w], NULL ok */, uint8_t* status_out /* [h*w], NULL ok */,
                     int32_t* stats_out /* [4], NULL ok */, int on_device);
 
+/* Speckle filter of a disparity image: removes the small islands of valid disparity that semi-global matching leaves at occlusion edges, and makes the depth plane that
+ * vido_mask_propagate takes for its collisions (defined by tests/refimpl/stereo_filter_np.py, exact to the bit; no reference counterpart).  q4 / status: vido_stereo_sgm's
+ * q4_out / status_out, or any images of that form.  1 <= width, height <= 4095; 0 <= max_diff_q4 <= 65535; 1 <= min_region <= 2^24; bf finite and > 0 when depth_out is
+ * given (ignored otherwise); VIDO_E_INVALID otherwise, for a NULL input, when all three image outputs and stats_out are NULL, for a status_out that overlaps status
+ * without being it, and for a misaligned device output.  Needs no other state of the context and not its configured frame size.  In the order the rules apply:
+ *   valid       status == 0 and 1 <= q4 <= 65535.  A status-0 pixel with q4 outside that range gets status_out = 3 (vido_stereo_sgm gives such a pixel status 3 itself);
+ *               every other input status, values above 3 included, is copied through and is not valid
+ *   edge        two 4-neighbours (left / right, up / down), both valid, with |q4a - q4b| <= max_diff_q4
+ *   region      a connected component of the valid pixels under these edges; its area is its pixel count.  The relation is NOT transitive: a ramp 16, 32, 48, ... with
+ *               max_diff_q4 = 16 is one region whose ends differ arbitrarily, and two pixels may share a region through a detour only
+ *   speckle     a valid pixel whose region has area < min_region gets status_out = 4.  min_region = 1 removes nothing, and the call then launches no labelling
+ * status_out [h*w] as above (it may BE status); disp_out [h*w] = q4 / 16 in pixels (exact) where status_out is 0, -1 elsewhere (vido_stereo_sgm's disp_out convention);
+ * depth_out [h*w] = bf / disp_out, ONE correctly rounded fp32 division, where status_out is 0, FLT_MAX elsewhere: finite and positive, so vido_mask_propagate still
+ * scatters such a source, which loses every collision against a measured depth and falls back to "smaller label" against another unknown; stats_out [4] = valid pixels
+ * in, regions removed, pixels removed, valid pixels out (zeroed by a kernel of the call).  Any output may be NULL, not all.  on_device != 0: every pointer is a device
+ * pointer (disp_out, depth_out and stats_out 4-byte aligned) and the call only enqueues on the ctx stream (vido_set_stream's when one is set): one launch with
+ * min_region = 1, else four (tile labelling in LDS, seam merge, flatten + areas, write), no host synchronisation, so a call can sit inside a stream capture — except the
+ * first call of a size, which grows the op's own scratch (two i32 planes: parent and area; shared with no other op).  Otherwise the arrays are the caller's host arrays,
+ * staged through pinned buffers that grow on demand, and the call returns when the results are there.  A result depends on nothing but the two images and the three
+ * parameters: the labelling uses integer minima and sums only, whose results do not depend on the order. */
+int vido_stereo_filter(vido_ctx* ctx, const int32_t* q4 /* [h*w], 1/16 px */, const uint8_t* status /* [h*w] */, int width, int height,
+                       int max_diff_q4, int min_region, float bf,
+                       float* disp_out /* [h*w], NULL ok */, uint8_t* status_out /* [h*w], NULL ok; may BE status */, float* depth_out /* [h*w], NULL ok */,
+                       int32_t* stats_out /* [4], NULL ok */, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device

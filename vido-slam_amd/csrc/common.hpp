@@ -53,6 +53,7 @@ struct vido_ctx {
     struct DisFlowState* disflow = nullptr;  // disflow.hip: pyramids, per-level fields and staging of vido_dis_flow
     struct FlowCheckState* flowcheck = nullptr; // flowcheck.hip: staging of vido_flow_consistency's host form
     struct StereoState* stereo = nullptr;    // stereosgm.hip: grey and census planes, the S volume and staging of vido_stereo_sgm
+    struct StereoFilterState* sfilter = nullptr; // stereofilter.hip: parent and area planes and staging of vido_stereo_filter
     struct PoseState* pose = nullptr;
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
@@ -106,6 +107,7 @@ void patchrefine_state_destroy(vido_ctx* ctx);
 void disflow_state_destroy(vido_ctx* ctx);
 void flowcheck_state_destroy(vido_ctx* ctx);
 void stereo_state_destroy(vido_ctx* ctx);
+void stereofilter_state_destroy(vido_ctx* ctx);
 // (flowcheck.hip) for disflow.hip's vido_dis_flow_pair: the parameter rules of the check (0 = fine), and its memset + launch on device pointers
 int flowcheck_params(vido_ctx* ctx, const char* who, int alpha_q10, int beta_q16);
 hipError_t flowcheck_enqueue(hipStream_t st, const int32_t* fwd, const int32_t* bwd, int H, int W, int alpha_q10, int beta_q16, uint8_t* status, float* marked, int32_t* stats);

@@ -100,6 +100,7 @@ void vido_destroy(vido_ctx* ctx)
     patchrefine_state_destroy(ctx);
     disflow_state_destroy(ctx);
     stereo_state_destroy(ctx);
+    stereofilter_state_destroy(ctx);
     flowcheck_state_destroy(ctx);
     pose_state_destroy(ctx);
     ba_state_destroy(ctx);

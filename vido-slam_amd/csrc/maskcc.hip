@@ -16,6 +16,7 @@
 // The area plane is cleared by the memset in FRONT of the first launch, never by a kernel afterwards (the key plane's reasons).  Both planes are addressed
 // from an element offset chosen per call so that they reach a 16-byte boundary at the same pixel as `out`.  Integer minima and sums only: no execution order matters.
 #include "common.hpp"
+#include "ccunion.hpp"                                          // cc_lfind / cc_lunion (LDS) and cc_gfind / cc_gunion (global, agent-scope atomics)
 
 struct MaskCCState {
     int32_t* d_parent = nullptr;                                  // [cap_px + 8] parent index per pixel, -1 = background
@@ -28,39 +29,6 @@ struct MaskCCState {
 #define CC_T 32                                                   // tile edge
 #define CC_PX (CC_T * CC_T)
 #define CC_ROWS 4096
-
-// ---- union-find in LDS (workgroup scope) -------------------------------------------------------------
-__device__ __forceinline__ int cc_lfind(int* par, int i)
-{
-    for (;;) { const int p = __hip_atomic_load(par + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); if (p == i) return i; i = p; }
-}
-__device__ __forceinline__ void cc_lunion(int* par, int a, int b)
-{
-    for (;;) {
-        a = cc_lfind(par, a); b = cc_lfind(par, b);
-        if (a == b) return;
-        if (a < b) { const int s = a; a = b; b = s; }              // a > b: a's root goes under the smaller index
-        const int old = __hip_atomic_fetch_min(par + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (old == a) return;
-        a = old;                                                    // somebody moved a meanwhile: go on from where it points
-    }
-}
-// ---- union-find in global memory, every access an agent-scope atomic ---------------------------------
-__device__ __forceinline__ int cc_gfind(int32_t* par, int i)
-{
-    for (;;) { const int p = __hip_atomic_load(par + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (p == i) return i; i = p; }
-}
-__device__ __forceinline__ void cc_gunion(int32_t* par, int a, int b)
-{
-    for (;;) {
-        a = cc_gfind(par, a); b = cc_gfind(par, b);
-        if (a == b) return;
-        if (a < b) { const int s = a; a = b; b = s; }
-        const int old = __hip_atomic_fetch_min(par + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // One workgroup per 32 x 32 tile, four pixels per thread (rows ry0, ry0 + 8, ...).  Local index l = ry * 32 + rx orders like the raster index inside the tile, so the local
 // root is the tile part's smallest raster index.  A pixel starts under the first pixel of its horizontal run (half a wave holds a tile row: the run's start is the highest

@@ -100,6 +100,10 @@ def load_library():
 FLOW_ALPHA_Q10 = 10
 FLOW_BETA_Q16 = 32768
 
+# defaults of vido_stereo_filter: neighbours within 16 / 16 = 1 px share an edge, regions below 10 px go (tools/measure_stereo_filter.py, profiles/r26/stereo_filter_cpu.txt)
+STEREO_FILTER_MAX_DIFF_Q4 = 16
+STEREO_FILTER_MIN_REGION = 10
+
 # defaults of vido_orb_patch_points' verdict = the tracker's Verify.PatchMinStd 6 / Verify.PatchMinZncc 920 / 1024 (profiles/r16/patch_verify.txt)
 PATCH_MIN_VAR = 64 * 64 * 6 * 6
 PATCH_MIN_ZNCC_Q10 = 920
@@ -387,6 +391,28 @@ class Context:
         """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the op's scratch); any output pointer may be None, not all."""
         self._check(self.lib.vido_stereo_sgm(self.h, left_ptr, right_ptr, int(channels), int(rgb_order), int(stride), int(width), int(height), int(max_disp), int(p1), int(p2),
                                              int(uniqueness), int(lr_tol), disp_ptr, q4_ptr, status_ptr, stats_ptr, 1))
+
+    def stereo_filter(self, q4, status, max_diff_q4=STEREO_FILTER_MAX_DIFF_Q4, min_region=STEREO_FILTER_MIN_REGION, bf=None):
+        """Speckle filter of a disparity image (vido_stereo_filter; the statement is tests/refimpl/stereo_filter_np.py): q4 (H,W) i32 in 1/16 px and status (H,W) u8 host
+        arrays, stereo_sgm's or of that form.  A pixel is valid with status 0 and 1 <= q4 <= 65535; valid 4-neighbours whose q4 differ by at most max_diff_q4 share an edge;
+        a valid pixel whose connected region holds fewer than min_region pixels becomes status 4 (min_region = 1: nothing does).  Returns (disp (H,W) f32 = q4 / 16 where
+        the new status is 0 and -1 elsewhere, status (H,W) u8, depth (H,W) f32 = bf / disp where the new status is 0 and FLT_MAX elsewhere — mask_propagate's collision
+        depth — or None without bf, stats (4,) i32 = valid pixels in, regions removed, pixels removed, valid pixels out)."""
+        q4, status = np.ascontiguousarray(q4), np.ascontiguousarray(status)
+        if q4.dtype != np.int32 or status.dtype != np.uint8 or q4.ndim != 2 or q4.shape != status.shape:
+            raise VidoError(-1, "stereo_filter: an i32 and a u8 image of one shape H x W expected")
+        h, w = q4.shape
+        disp = np.empty((h, w), np.float32); out = np.empty((h, w), np.uint8); depth = None if bf is None else np.empty((h, w), np.float32); stats = np.empty(4, np.int32)
+        self._check(self.lib.vido_stereo_filter(self.h, _ptr(q4), _ptr(status), w, h, int(max_diff_q4), int(min_region), 0.0 if bf is None else float(bf), _ptr(disp), _ptr(out),
+                                                None if depth is None else _ptr(depth), _ptr(stats), 0))
+        return disp, out, depth, stats
+
+    def stereo_filter_device(self, q4_ptr, status_ptr, width, height, max_diff_q4=STEREO_FILTER_MAX_DIFF_Q4, min_region=STEREO_FILTER_MIN_REGION, bf=0.0, disp_ptr=None,
+                             status_out_ptr=None, depth_ptr=None, stats_ptr=None):
+        """Device-pointer form: only enqueues on the context's stream (the first call of a size grows the op's scratch); any output pointer may be None, not all;
+        status_out_ptr may be status_ptr."""
+        self._check(self.lib.vido_stereo_filter(self.h, q4_ptr, status_ptr, int(width), int(height), int(max_diff_q4), int(min_region), float(bf), disp_ptr, status_out_ptr,
+                                                depth_ptr, stats_ptr, 1))
 
     def orb_timing(self):
         t = np.zeros(8, np.float32)

@@ -860,6 +860,45 @@ class HipOps:
                    out.data_ptr(), _p(q4), _p(status), _p(stats), 1)
         return out
 
+    def stereo_filter(self, q4, status, out=None, status_out=None, depth=None, stats=None, bf=None, max_diff_q4=None, min_region=None):
+        """vido_stereo_filter on device tensors: q4 int32 [H,W] in 1/16 px and status uint8 [H,W] (stereo_sgm's, or of that form) -> the filtered disparity, float32 [H,W]:
+        q4 / 16 where the new status is 0 and -1 elsewhere (`out`, or a new tensor).  A valid pixel (status 0, 1 <= q4 <= 65535) whose region — connected through valid
+        4-neighbours that differ by at most max_diff_q4 — holds fewer than min_region pixels gets status 4.  status_out: a uint8 [H,W] tensor that receives the new status
+        (it may be `status`), or None; depth: a float32 [H,W] tensor that receives bf / disparity where the new status is 0 and FLT_MAX elsewhere (mask_propagate's
+        collision depth; needs bf, a float > 0), or None; stats: an int32 tensor of >= 4 elements that receives valid in / regions removed / pixels removed / valid out,
+        or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/stereo_filter_np.py.  Enqueued on torch's current stream, nothing is waited for; the
+        first call of a size grows the op's scratch, so it comes before a graph capture.  CPU tensors, other dtypes or shapes and non-contiguous tensors raise."""
+        from ..host import VidoError, STEREO_FILTER_MAX_DIFF_Q4, STEREO_FILTER_MIN_REGION
+        def bad(why):
+            raise VidoError(-1, "stereo_filter: " + why)
+        for name, t, dt in (("q4", q4, torch.int32), ("status", status, torch.uint8), ("out", out, torch.float32), ("status_out", status_out, torch.uint8),
+                            ("depth", depth, torch.float32), ("stats", stats, torch.int32)):
+            if t is None and name not in ("q4", "status"):
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                bad("%s must be a device tensor; there is no CPU fallback" % name)
+            if t.dtype != dt:
+                bad("%s must be %s, got %s" % (name, dt, t.dtype))
+            if not t.is_contiguous():
+                bad("%s must be contiguous" % name)
+            if t.device != q4.device:
+                bad("%s is on another device than q4" % name)
+        if q4.dim() != 2:
+            bad("q4 must be [H, W], got %s" % (tuple(q4.shape),))
+        H, W = int(q4.shape[0]), int(q4.shape[1])
+        if out is None:
+            out = torch.empty((H, W), device=q4.device, dtype=torch.float32)
+        for name, t in (("status", status), ("out", out), ("status_out", status_out), ("depth", depth)):
+            if t is not None and tuple(t.shape) != (H, W):
+                bad("%s must be [%d, %d], got %s" % (name, H, W, tuple(t.shape)))
+        if stats is not None and stats.numel() < 4:
+            bad("stats needs 4 elements")
+        if depth is not None and bf is None:
+            bad("depth needs bf")
+        self._call(self.ctx.lib.vido_stereo_filter, q4.data_ptr(), status.data_ptr(), W, H, int(STEREO_FILTER_MAX_DIFF_Q4 if max_diff_q4 is None else max_diff_q4),
+                   int(STEREO_FILTER_MIN_REGION if min_region is None else min_region), 0.0 if bf is None else float(bf), out.data_ptr(), _p(status_out), _p(depth), _p(stats), 1)
+        return out
+
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
         """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
         (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),

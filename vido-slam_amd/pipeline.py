@@ -127,7 +127,8 @@ class InstanceIds:
     previous frame into this one, or None on the first frame of a sequence.  The image handed over last is warped through the flow (HipOps.mask_propagate) and associated
     with inst_mask (HipOps.mask_associate): an instance takes over the id it overlaps with IoU > 1/2, any other gets a fresh id; an id the detector misses stays in the
     image at its flow-predicted place for `hold` detector frames.  propagated(flow): a frame without a detector run, the last image warped through the flow.  Both return
-    the frame's mask, one of the two images: valid until the next call.  mask is the image handed over last (writable: the next call starts from it),
+    the frame's mask, one of the two images: valid until the next call.  depth (both calls; default None): the metric depth of the PREVIOUS frame, float32 HxW — the frame
+    the warped image belongs to — handed to mask_propagate, which then gives a pixel two labels land on to the nearer source.  mask is the image handed over last (writable: the next call starts from it),
     classes_by_id an int64 [255] device tensor refreshed in stream order by detected(): [id - 1] is the class of id, 0 when the id is neither live nor held.
 
     from_classes(class_mask, flow=None, connectivity=8, min_area=1): the same for a CLASS label image (the reference node's sum of mask * class index, a dataset's semantic
@@ -165,13 +166,13 @@ class InstanceIds:
         for m in self._img:
             m.zero_()
 
-    def detected(self, inst_mask, classes, flow=None):
+    def detected(self, inst_mask, classes, flow=None, depth=None):
         last, other = self._img[self._i], self._img[self._i ^ 1]
         if flow is None:
             out = self.ops.mask_associate(None, inst_mask, self.state, classes=classes, hold=self.hold, out=other, stats=self.stats)
             self._i ^= 1
         else:
-            self.ops.mask_propagate(last, flow, out=other)
+            self.ops.mask_propagate(last, flow, depth=depth, out=other)
             out = self.ops.mask_associate(other, inst_mask, self.state, classes=classes, hold=self.hold, out=last, stats=self.stats)
         self.classes_by_id.copy_(self.state[257:512], non_blocking=True)
         return out
@@ -180,8 +181,8 @@ class InstanceIds:
         self.ops.mask_components(class_mask, connectivity=connectivity, min_area=min_area, id_base=0, cap=127, out=self._inst, classes=self._inst_classes, stats=self.split_stats)
         return self.detected(self._inst, self._inst_classes, flow)
 
-    def propagated(self, flow):
-        out = self.ops.mask_propagate(self._img[self._i], flow, out=self._img[self._i ^ 1])
+    def propagated(self, flow, depth=None):
+        out = self.ops.mask_propagate(self._img[self._i], flow, depth=depth, out=self._img[self._i ^ 1])
         self._i ^= 1
         return out
 
@@ -203,7 +204,8 @@ class NetNodes:
 
     detect_every = N (an integer >= 1; default 1: the detector runs on every frame and nothing below applies): the detector runs on calls 0, N, 2N, ...; on the calls in
     between it is not launched, and the frame's mask is the previous frame's mask warped through this call's flow (HipOps.mask_propagate, csrc/maskprop.hip) on the
-    detector's stream behind the flow's event, into one of two buffers the nodes own (a graph's static output is overwritten by the next replay).  No depth is passed: the
+    detector's stream behind the flow's event, into one of two buffers the nodes own (a graph's static output is overwritten by the next replay).  No depth is passed
+    (unless propagate_bf is set, below): the
     networks' depth is a normalised disparity, not metric, so where two objects land on one pixel the SMALLER LABEL wins, not the nearer object.  A propagated frame returns
     the last detector frame's labels and reports no detections (so no overflow); label_mode="instance": the id base advances per detector RUN, a propagated frame keeps its
     source's ids and base (self.id_base).  carried_mask is the image the next propagated frame starts from — a device tensor an external detector or a test may write;
@@ -240,17 +242,30 @@ class NetNodes:
     KITTI ChooseData code (facade.cpp:876: the depth image is a disparity), DepthMapFactor: 1 and Camera.bf = fx * baseline in the settings, the front end computes
     bf / disparity metres and treats -1 as "no depth".  stereo_status: the uint8 HxW status image of the last frame (0 valid, 1 not unique, 2 left-right, 3 zero
     disparity), valid in stream order with the depth; None with "net".  Anything else raises ValueError before anything is built, and so do stereo_params with
-    depth_source = "net" and a right_bgr handed to infer() under "net"."""
+    depth_source = "net" and a right_bgr handed to infer() under "net".
+
+    stereo_filter (with depth_source = "stereo" only; default None: off, and the depth function is exactly the one above): True, or a dict that may hold max_diff_q4 and
+    min_region (the op's defaults otherwise: 16 and 10) — SGM is followed by HipOps.stereo_filter (csrc/stereofilter.hip) in the same capture: a valid
+    pixel whose region of similar disparity holds fewer than min_region pixels is dropped.  infer() returns the filtered disparity, and stereo_status shows 4 on speckles.
+
+    propagate_bf (default None: off) = fx x baseline, a float > 0; needs depth_source = "stereo" and detect_every > 1 or stable_ids = True.  The filter op also writes
+    the collision depth of the frame (bf / disparity metres where the status is 0, FLT_MAX elsewhere; without stereo_filter the op runs with min_region = 1: it makes the
+    plane and launches no labelling) into one of two planes the nodes alternate between, and EVERY mask_propagate call of the nodes, the one inside InstanceIds included,
+    receives the PREVIOUS frame's plane as its depth — the frame the carried mask belongs to: where two labels land on one pixel the nearer source wins, and a source
+    without a measured depth loses to one with.  On the first frame of a sequence no depth is passed.  Any other combination raises ValueError before anything is built."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
 
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
-                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None, depth_source="net", stereo_params=None):
+                 detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None, depth_source="net", stereo_params=None,
+                 stereo_filter=None, propagate_bf=None):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
         self.depth_source, self.stereo_params = self._check_depth_source(depth_source, stereo_params)
+        self.stereo_filter, self.propagate_bf = self._check_stereo_filter(stereo_filter, propagate_bf, depth_source, detect_every, stable_ids)
         self.stereo_status = None
+        self._coll = None; self._coll_static = None; self._coll_i = 0; self._coll_have = False      # propagate_bf: the collision-depth planes (the last one written: _coll_i)
         self.flow_source, self.dis_params = self._check_flow_source(flow_source, dis_params)
         self.dis_consistency = self._check_dis_consistency(dis_consistency, flow_source)
         self.flow_status = None
@@ -335,6 +350,16 @@ class NetNodes:
         if self.depth_source == "stereo":                             # the op on (left, right); the status image is the nodes' own buffer, written by eager calls and replays alike
             self.stereo_status = torch.zeros((height, width), dtype=torch.uint8, device=dev)
             self._depth_fn = lambda a, b: ops.stereo_sgm(a, b, status=self.stereo_status, **self.stereo_params)
+            if self.stereo_filter is not None or self.propagate_bf is not None:      # SGM, then the filter on its q4 / status: the status in place, the collision depth when asked for
+                self._stereo_q4 = torch.zeros((height, width), dtype=torch.int32, device=dev)
+                if self.propagate_bf is not None:                     # the plane the (captured) op writes, and the two the frames alternate between
+                    self._coll_static = torch.zeros((height, width), dtype=torch.float32, device=dev)
+                    self._coll = [torch.zeros((height, width), dtype=torch.float32, device=dev) for _ in range(2)]
+                filt = self.stereo_filter if self.stereo_filter is not None else dict(min_region=1)
+                def _stereo_fn(a, b):
+                    disp = ops.stereo_sgm(a, b, q4=self._stereo_q4, status=self.stereo_status, **self.stereo_params)
+                    return ops.stereo_filter(self._stereo_q4, self.stereo_status, out=disp, status_out=self.stereo_status, depth=self._coll_static, bf=self.propagate_bf, **filt)
+                self._depth_fn = _stereo_fn
             dex = [ex, ex]                                            # (its first call of the size, below, grows the op's scratch: before any capture)
         self._trunk_fn = lambda a: self.mask_net.trunk(_nets.maskrcnn.image_to_feed(a, dev, self.mask_feed, ops=ops))
         # the whole detector with static shapes (nets/maskrcnn.py: heads_static / analyse_image_static): trunk + device-side RPN selection + box head + fixed-slot
@@ -398,7 +423,13 @@ class NetNodes:
             e0 = torch.cuda.Event(); e0.record()
         with torch.cuda.stream(ss[1]):
             depth = (self.g_depth or self._depth_fn)(cur_bgr) if right_bgr is None else (self.g_depth or self._depth_fn)(cur_bgr, right_bgr)
+            if self._coll is not None:                                  # this frame's collision depth, kept past the next call (the next frame's propagation reads it)
+                self._coll[self._coll_i ^ 1].copy_(self._coll_static, non_blocking=True)
             e1 = torch.cuda.Event(); e1.record()
+        # the depth the carried mask belongs to: the previous frame's plane (written on the depth stream a call ago; this call's streams wait for the caller's, which waited for it)
+        prev_depth = self._coll[self._coll_i] if self._coll is not None and self._coll_have else None
+        if self._coll is not None:
+            self._coll_i ^= 1; self._coll_have = True
         det_frame = self.detect_every == 1 or self._calls % self.detect_every == 0
         self._calls += 1
         with torch.cuda.stream(ss[2]):
@@ -409,12 +440,12 @@ class NetNodes:
                 self._id_word.copy_(self._base_word(self.id_base), non_blocking=True)
             if not det_frame and self._ids is not None:                 # stable ids: the image handed over last through this call's flow
                 ss[2].wait_event(e0)
-                mask, labels = self._ids.propagated(flow), self._ids.classes_by_id
+                mask, labels = self._ids.propagated(flow, depth=prev_depth), self._ids.classes_by_id
                 self.last_counts = None if self._last_nlab is None else (self._last_nlab, self._zero_count)
             elif not det_frame:                                         # the previous frame's mask through this call's flow; the detector is not launched
                 ss[2].wait_event(e0)
                 dst = self._carry[self._carry_i ^ 1]
-                self.ops.mask_propagate(self._carry[self._carry_i], flow, out=dst)
+                self.ops.mask_propagate(self._carry[self._carry_i], flow, depth=prev_depth, out=dst)
                 self._carry_i ^= 1
                 mask, labels = dst, self._last_labels
                 self.last_counts = None if self._last_nlab is None else (self._last_nlab, self._zero_count)
@@ -437,7 +468,7 @@ class NetNodes:
                     ss[2].wait_event(e0)
                 if not torch.is_tensor(labels):
                     labels = torch.as_tensor(labels, dtype=torch.int64)
-                mask = self._ids.detected(mask.contiguous(), labels.to(device=self.dev, dtype=torch.int64).contiguous(), None if first else flow)
+                mask = self._ids.detected(mask.contiguous(), labels.to(device=self.dev, dtype=torch.int64).contiguous(), None if first else flow, depth=None if first else prev_depth)
                 labels = self._ids.classes_by_id
                 self._last_nlab = None if self.last_counts is None else self.last_counts[0]
             if det_frame:
@@ -471,6 +502,31 @@ class NetNodes:
         if stereo_params is not None and (depth_source != "stereo" or not isinstance(stereo_params, dict) or any(k not in cls.STEREO_PARAMS for k in stereo_params)):
             raise ValueError("stereo_params: with depth_source='stereo', a dict with keys among %s, not %r" % (cls.STEREO_PARAMS, stereo_params))
         return depth_source, dict(stereo_params or {})
+
+    STEREO_FILTER = ("max_diff_q4", "min_region")
+
+    @classmethod
+    def _check_stereo_filter(cls, stereo_filter, propagate_bf, depth_source, detect_every, stable_ids):
+        """-> (None (off) or the filter's parameters as a dict (empty: the op's defaults), None (off) or bf as a float)"""
+        import math as _math
+        import numbers as _numbers
+        filt = None
+        if stereo_filter is not None:
+            ok = stereo_filter is True or (isinstance(stereo_filter, dict) and all(
+                k in cls.STEREO_FILTER and isinstance(v, _numbers.Integral) and not isinstance(v, bool) for k, v in stereo_filter.items()))
+            if depth_source != "stereo" or not ok:
+                raise ValueError("stereo_filter: with depth_source='stereo', None, True or a dict with integer values under keys among %s, not %r" % (cls.STEREO_FILTER, stereo_filter))
+            filt = {} if stereo_filter is True else {k: int(v) for k, v in stereo_filter.items()}
+            if not 0 <= filt.get("max_diff_q4", 0) <= 65535 or not 1 <= filt.get("min_region", 1) <= 1 << 24:
+                raise ValueError("stereo_filter: max_diff_q4 in 0..65535 and min_region in 1..2^24 expected, not %r" % (stereo_filter,))
+        bf = None
+        if propagate_bf is not None:
+            if isinstance(propagate_bf, bool) or not isinstance(propagate_bf, _numbers.Real) or not _math.isfinite(propagate_bf) or not propagate_bf > 0:
+                raise ValueError("propagate_bf: a finite float > 0 (fx x baseline), not %r" % (propagate_bf,))
+            if depth_source != "stereo" or not (detect_every > 1 or stable_ids):
+                raise ValueError("propagate_bf needs depth_source='stereo' (a metric depth) and detect_every > 1 or stable_ids=True (a mask that is propagated)")
+            bf = float(propagate_bf)
+        return filt, bf
 
     FLOW_SOURCES = ("net", "dis")
     DIS_PARAMS = ("coarsest", "iters", "max_shift_q8", "min_eig")
@@ -525,6 +581,7 @@ class NetNodes:
         the next infer() is a detector frame under id base 0.  Not part of the interface; never while frames are in flight."""
         self._check_detect_every(detect_every, self.on_range)
         self.detect_every = int(detect_every); self._calls = 0; self._frames = 0; self.id_base = 0; self.last_propagated = False
+        self._coll_have = False                                       # (the first frame of a sequence passes no depth)
         if self._ids is not None:                                     # stable ids: InstanceIds owns the images; a new sequence starts with no id live
             self._ids.reset(); self._last_nlab = None
             return
