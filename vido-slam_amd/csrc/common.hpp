@@ -29,6 +29,29 @@ struct PyrDev {                    // passed by value to kernels
 struct CellDesc { int level, x0, y0, sw, sh, pad0, pad1, pad2; };   // FAST sub-image of one cell (level coords)
 struct BlurTile { int level, tx, ty, pad; };
 
+// Host staging (ctx.cpp): the one device + pinned buffer pair behind every host form (on_device = 0).  A call declares its fields in order — inputs, outputs, then
+// fields read and written in one slot — each by the address of the pointer it will launch with, which holds the caller's HOST pointer: staging_upload copies the inputs
+// over and repoints every such pointer at the field's device slot (offsets are multiples of 16); staging_download brings back each output that was asked for and waits
+// for the stream.  A field whose host pointer is NULL takes no copy and gets a null device pointer, unless it was declared with keep(): then the slot is there for the
+// kernels and nothing comes back.  One user at a time: a host form ends in staging_download's wait, so the buffers are free at every entry; the device forms never
+// touch them.
+struct HostStaging {
+    static constexpr int MAX_FIELDS = 12;
+    struct Field { void **in, **out; const void* src; void* dst; size_t bytes, off; bool keep; };
+    uint8_t *d = nullptr, *h = nullptr; size_t cap = 0;
+    Field f[MAX_FIELDS]; int n = 0; size_t total = 0;
+    void begin() { n = 0; total = 0; }
+    void add(void** in, void** out, size_t bytes, bool keep)
+    {
+        if (n < MAX_FIELDS) f[n] = Field{in, out, in ? *in : nullptr, out ? *out : nullptr, bytes, total, keep};
+        n++; total += (bytes + 15) & ~(size_t)15;
+    }
+    template <class T> void in(const T** p, size_t bytes) { add((void**)p, nullptr, bytes, false); }
+    template <class T> void out(T** p, size_t bytes) { add(nullptr, (void**)p, bytes, false); }
+    template <class T> void keep(T** p, size_t bytes) { add(nullptr, (void**)p, bytes, true); }                    // an output whose slot the kernels need even when the caller passes NULL
+    template <class T> void inout(const T** pi, T** po, size_t bytes) { add((void**)pi, (void**)po, bytes, false); }
+};
+
 struct OrbState;                   // orb.hip
 struct TrackState;                 // track.hip
 struct BaState;                    // ba.hip
@@ -46,14 +69,11 @@ struct vido_ctx {
     TrackState* trk = nullptr;
     BaState* ba = nullptr;
     struct HamState* ham = nullptr;
-    struct HamWinState* hamwin = nullptr;    // hamwin.hip: chunk partials, owner plane and staging of vido_hamming_match_window
-    struct PatchPtsState* patchpts = nullptr; // patchpts.hip: staging of vido_orb_patch_points' host form
-    struct PatchSearchState* patchsearch = nullptr; // patchsearch.hip: staging of vido_orb_patch_search's host form
-    struct PatchRefineState* patchrefine = nullptr; // patchrefine.hip: staging of vido_orb_patch_refine's host form
-    struct DisFlowState* disflow = nullptr;  // disflow.hip: pyramids, per-level fields and staging of vido_dis_flow
-    struct FlowCheckState* flowcheck = nullptr; // flowcheck.hip: staging of vido_flow_consistency's host form
-    struct StereoState* stereo = nullptr;    // stereosgm.hip: grey and census planes, the S volume and staging of vido_stereo_sgm
-    struct StereoFilterState* sfilter = nullptr; // stereofilter.hip: parent and area planes and staging of vido_stereo_filter
+    struct HamWinState* hamwin = nullptr;    // hamwin.hip: chunk partials, owner plane and spare counters of vido_hamming_match_window
+    struct DisFlowState* disflow = nullptr;  // disflow.hip: pyramids and per-level fields of vido_dis_flow
+    struct StereoState* stereo = nullptr;    // stereosgm.hip: grey and census planes and the S volume of vido_stereo_sgm
+    struct StereoFilterState* sfilter = nullptr; // stereofilter.hip: parent and area planes of vido_stereo_filter
+    HostStaging staging;                     // the buffers of every host form (above)
     struct PoseState* pose = nullptr;
     struct NetState* net = nullptr;
     struct PnpState* pnp = nullptr;
@@ -68,6 +88,13 @@ struct vido_ctx {
 };
 
 int vido_set_error(vido_ctx* ctx, int code, const char* fmt, ...);
+// (ctx.cpp) the two halves of a host form around its launches, over the fields declared on ctx->staging since begin()
+int staging_upload(vido_ctx* ctx, hipStream_t st);
+int staging_download(vido_ctx* ctx, hipStream_t st);
+// (ctx.cpp) device scratch of at least `need` bytes: growing waits for the call's stream, and for the context's if that is another one (earlier calls may still use the
+// old buffer), frees, records capacity 0 and allocates `need` bytes (GROW_EXACT) or need + need / 2 + 512 (GROW_HEADROOM)
+enum GrowPolicy { GROW_EXACT, GROW_HEADROOM };
+int vido_grow_device(vido_ctx* ctx, hipStream_t st, void** p, size_t* cap, size_t need, GrowPolicy policy);
 // VIDO_CALL_PROF=1: named host-side sections inside the library (ctx.cpp keeps the table, prints it at exit next to the facade's per-call table).  A section that ends with
 // `sync` waits for the stream first, so that the section owns the device time of what it enqueued (diagnosis only: the waits change the overlap they measure).
 bool vido_prof_on();
@@ -101,11 +128,7 @@ void maskassoc_state_destroy(vido_ctx* ctx);
 void maskcc_state_destroy(vido_ctx* ctx);
 void ham_state_destroy(vido_ctx* ctx);
 void hamwin_state_destroy(vido_ctx* ctx);
-void patchpts_state_destroy(vido_ctx* ctx);
-void patchsearch_state_destroy(vido_ctx* ctx);
-void patchrefine_state_destroy(vido_ctx* ctx);
 void disflow_state_destroy(vido_ctx* ctx);
-void flowcheck_state_destroy(vido_ctx* ctx);
 void stereo_state_destroy(vido_ctx* ctx);
 void stereofilter_state_destroy(vido_ctx* ctx);
 // (flowcheck.hip) for disflow.hip's vido_dis_flow_pair: the parameter rules of the check (0 = fine), and its memset + launch on device pointers

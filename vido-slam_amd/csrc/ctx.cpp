@@ -16,6 +16,65 @@ int vido_set_error(vido_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
+int vido_grow_device(vido_ctx* ctx, hipStream_t st, void** p, size_t* cap, size_t need, GrowPolicy policy)
+{
+    if (need <= *cap) return VIDO_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (st != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*p) { HIP_TRY(ctx, hipFree(*p)); *p = nullptr; }
+    *cap = 0;
+    const size_t n = policy == GROW_HEADROOM ? need + need / 2 + 512 : need;
+    HIP_TRY(ctx, hipMalloc(p, n));
+    *cap = n;
+    return VIDO_OK;
+}
+
+// ---- host staging (common.hpp) -----------------------------------------------------------------------------------------------------------------------------
+// both buffers hold the declared fields: growing waits for the stream, frees both and records capacity 0 before it allocates the need plus half
+static int staging_reserve(vido_ctx* ctx, hipStream_t st)
+{
+    HostStaging& T = ctx->staging;
+    if (T.n > HostStaging::MAX_FIELDS) return vido_set_error(ctx, VIDO_E_INVALID, "host staging: %d fields declared, %d fit", T.n, HostStaging::MAX_FIELDS);
+    if (T.total <= T.cap) return VIDO_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (T.d) { HIP_TRY(ctx, hipFree(T.d)); T.d = nullptr; }
+    if (T.h) { HIP_TRY(ctx, hipHostFree(T.h)); T.h = nullptr; }
+    T.cap = 0;
+    const size_t n = (T.total + T.total / 2 + 4095) & ~(size_t)4095;
+    HIP_TRY(ctx, hipMalloc((void**)&T.d, n)); HIP_TRY(ctx, hipHostMalloc((void**)&T.h, n));
+    T.cap = n;
+    return VIDO_OK;
+}
+
+int staging_upload(vido_ctx* ctx, hipStream_t st)
+{
+    if (int rc = staging_reserve(ctx, st)) return rc;
+    HostStaging& T = ctx->staging;
+    for (int i = 0; i < T.n; i++) if (T.f[i].src && T.f[i].bytes) memcpy(T.h + T.f[i].off, T.f[i].src, T.f[i].bytes);
+    for (int i = 0; i < T.n; i++) {                                        // one copy over each run of inputs
+        if (!T.f[i].src || !T.f[i].bytes) continue;
+        int j = i;
+        while (j + 1 < T.n && T.f[j + 1].src && T.f[j + 1].bytes) j++;
+        HIP_TRY(ctx, hipMemcpyAsync(T.d + T.f[i].off, T.h + T.f[i].off, T.f[j].off + T.f[j].bytes - T.f[i].off, hipMemcpyHostToDevice, st));
+        i = j;
+    }
+    for (int i = 0; i < T.n; i++) {
+        const HostStaging::Field& F = T.f[i];
+        if (F.in) *F.in = F.src ? T.d + F.off : nullptr;
+        if (F.out) *F.out = F.dst || F.keep ? T.d + F.off : nullptr;
+    }
+    return VIDO_OK;
+}
+
+int staging_download(vido_ctx* ctx, hipStream_t st)
+{
+    HostStaging& T = ctx->staging;
+    for (int i = 0; i < T.n; i++) if (T.f[i].dst && T.f[i].bytes) HIP_TRY(ctx, hipMemcpyAsync(T.h + T.f[i].off, T.d + T.f[i].off, T.f[i].bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (int i = 0; i < T.n; i++) if (T.f[i].dst && T.f[i].bytes) memcpy(T.f[i].dst, T.h + T.f[i].off, T.f[i].bytes);
+    return VIDO_OK;
+}
+
 extern "C" {
 
 void vido_config_default(vido_config* c)
@@ -95,18 +154,16 @@ void vido_destroy(vido_ctx* ctx)
     maskcc_state_destroy(ctx);
     ham_state_destroy(ctx);
     hamwin_state_destroy(ctx);
-    patchpts_state_destroy(ctx);
-    patchsearch_state_destroy(ctx);
-    patchrefine_state_destroy(ctx);
     disflow_state_destroy(ctx);
     stereo_state_destroy(ctx);
     stereofilter_state_destroy(ctx);
-    flowcheck_state_destroy(ctx);
     pose_state_destroy(ctx);
     ba_state_destroy(ctx);
     net_state_destroy(ctx);
     pnp_state_destroy(ctx);
     bawin_state_destroy(ctx);
+    if (ctx->staging.d) { hipFree(ctx->staging.d); ctx->staging.d = nullptr; }
+    if (ctx->staging.h) { hipHostFree(ctx->staging.h); ctx->staging.h = nullptr; }
     if (ctx->detpost_buf) { hipFree(ctx->detpost_buf); ctx->detpost_buf = nullptr; }
     if (ctx->c1_range_flag) { hipHostFree(ctx->c1_range_flag); ctx->c1_range_flag = nullptr; }
     if (ctx->stream) hipStreamDestroy(ctx->stream);

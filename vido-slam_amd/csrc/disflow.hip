@@ -19,8 +19,6 @@ struct DisFlowState {
     // the pair call: the last two per direction, and both level-0 fields (the check reads them whether or not the caller asks for them)
     uint8_t* d_scratch = nullptr; size_t scratch_cap = 0;
     int32_t* d_stats = nullptr;                                    // the counters (12 words) of a call without a caller's stats buffer
-    // host form: device + pinned staging [img0 | img1 | flow | q8 | stats], the pair call [img0 | img1 | flow | fwd | bwd | stats | status]
-    uint8_t *d_io = nullptr, *h_io = nullptr; size_t io_cap = 0;
 };
 
 struct DisGeom {
@@ -240,8 +238,6 @@ void disflow_state_destroy(vido_ctx* ctx)
     if (!S) return;
     if (S->d_scratch) (void)hipFree(S->d_scratch);
     if (S->d_stats) (void)hipFree(S->d_stats);
-    if (S->d_io) (void)hipFree(S->d_io);
-    if (S->h_io) (void)hipHostFree(S->h_io);
     delete S; ctx->disflow = nullptr;
 }
 
@@ -266,30 +262,7 @@ static int df_prepare(vido_ctx* ctx, hipStream_t st, const DisGeom& G)
     if (!ctx->disflow) ctx->disflow = new DisFlowState();
     DisFlowState* S = ctx->disflow;
     if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 48));
-    if (G.total > S->scratch_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (st != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (S->d_scratch) { HIP_TRY(ctx, hipFree(S->d_scratch)); S->d_scratch = nullptr; }
-        S->scratch_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_scratch, G.total));
-        S->scratch_cap = G.total;
-    }
-    return VIDO_OK;
-}
-
-// the host form's staging of io_total bytes
-static int df_staging(vido_ctx* ctx, hipStream_t st, size_t io_total)
-{
-    DisFlowState* S = ctx->disflow;
-    if (io_total > S->io_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
-        if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
-        S->io_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
-        S->io_cap = io_total;
-    }
-    return VIDO_OK;
+    return vido_grow_device(ctx, st, (void**)&S->d_scratch, &S->scratch_cap, G.total, GROW_EXACT);
 }
 
 // The launches of one call on device pointers: the counters' memset (16 bytes per direction), ingest, the pyramid, and per level k_dis_patch and k_dis_densify over ndir
@@ -334,27 +307,15 @@ extern "C" int vido_dis_flow(vido_ctx* ctx, const uint8_t* img0, const uint8_t* 
     if (int rc = df_prepare(ctx, st, G)) return rc;
     DisFlowState* S = ctx->disflow;
     const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
-    const size_t o_img1 = (img_bytes + 15) & ~(size_t)15, o_flow = 2 * o_img1, o_q8 = o_flow + px * 8, o_stats = o_q8 + px * 8, io_total = o_stats + 16;
-    const uint8_t *d_img0 = img0, *d_img1 = img1; float* d_flow = flow_out; int32_t *d_q8 = q8_out, *d_stats = stats ? stats : S->d_stats;
-    if (!on_device) {
-        if (int rc = df_staging(ctx, st, io_total)) return rc;
-        memcpy(S->h_io, img0, img_bytes); memcpy(S->h_io + o_img1, img1, img_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_img1 + img_bytes, hipMemcpyHostToDevice, st));
-        d_img0 = S->d_io; d_img1 = S->d_io + o_img1;
-        d_flow = flow_out ? (float*)(S->d_io + o_flow) : nullptr; d_q8 = q8_out ? (int32_t*)(S->d_io + o_q8) : nullptr; d_stats = (int32_t*)(S->d_io + o_stats);
+    int32_t* q8[2] = {q8_out, nullptr};
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&img0, img_bytes); T.in(&img1, img_bytes); T.out(&flow_out, px * 8); T.out(&q8[0], px * 8); T.keep(&stats, 16);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    int32_t* const q8[2] = {d_q8, nullptr};
-    HIP_TRY(ctx, df_enqueue(S, st, G, 1, d_img0, d_img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, d_flow, q8, d_stats));
+    HIP_TRY(ctx, df_enqueue(S, st, G, 1, img0, img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, flow_out, q8, stats ? stats : S->d_stats));
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        if (flow_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_flow, S->d_io + o_flow, px * 8, hipMemcpyDeviceToHost, st));
-        if (q8_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_q8, S->d_io + o_q8, px * 8, hipMemcpyDeviceToHost, st));
-        if (stats) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_stats, S->d_io + o_stats, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (flow_out) memcpy(flow_out, S->h_io + o_flow, px * 8);
-        if (q8_out) memcpy(q8_out, S->h_io + o_q8, px * 8);
-        if (stats) memcpy(stats, S->h_io + o_stats, 16);
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }
 
@@ -374,26 +335,17 @@ extern "C" int vido_dis_flow_pair(vido_ctx* ctx, const uint8_t* img0, const uint
     if (int rc = df_prepare(ctx, st, G)) return rc;
     DisFlowState* S = ctx->disflow;
     const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
-    const size_t o_img1 = (img_bytes + 15) & ~(size_t)15, o_flow = 2 * o_img1, o_fwd = o_flow + px * 8, o_bwd = o_fwd + px * 8, o_stats = o_bwd + px * 8, o_status = o_stats + 48, io_total = o_status + px;
-    const uint8_t *d_img0 = img0, *d_img1 = img1; float* d_flow = flow_out; uint8_t* d_status = status_out;
-    int32_t* q8[2] = {fwd_q8_out ? fwd_q8_out : (int32_t*)(S->d_scratch + G.q8_off[0]), bwd_q8_out ? bwd_q8_out : (int32_t*)(S->d_scratch + G.q8_off[1])};
+    int32_t* q8[2] = {fwd_q8_out, bwd_q8_out};                             // the check reads both fields whether or not the caller asks for them
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&img0, img_bytes); T.in(&img1, img_bytes); T.out(&flow_out, px * 8); T.keep(&q8[0], px * 8); T.keep(&q8[1], px * 8); T.keep(&stats_out, 48); T.out(&status_out, px);
+        if (int rc = staging_upload(ctx, st)) return rc;
+    }
+    for (int d = 0; d < 2; d++) if (!q8[d]) q8[d] = (int32_t*)(S->d_scratch + G.q8_off[d]);
     int32_t* d_stats = stats_out ? stats_out : S->d_stats;
-    if (!on_device) {
-        if (int rc = df_staging(ctx, st, io_total)) return rc;
-        memcpy(S->h_io, img0, img_bytes); memcpy(S->h_io + o_img1, img1, img_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_img1 + img_bytes, hipMemcpyHostToDevice, st));
-        d_img0 = S->d_io; d_img1 = S->d_io + o_img1;
-        d_flow = flow_out ? (float*)(S->d_io + o_flow) : nullptr; d_status = status_out ? S->d_io + o_status : nullptr;
-        q8[0] = (int32_t*)(S->d_io + o_fwd); q8[1] = (int32_t*)(S->d_io + o_bwd); d_stats = (int32_t*)(S->d_io + o_stats);
-    }
-    HIP_TRY(ctx, df_enqueue(S, st, G, 2, d_img0, d_img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, nullptr, q8, d_stats));
-    HIP_TRY(ctx, flowcheck_enqueue(st, q8[0], q8[1], height, width, alpha_q10, beta_q16, d_status, d_flow, d_stats + 8));
+    HIP_TRY(ctx, df_enqueue(S, st, G, 2, img0, img1, channels, rgb_order, stride, width, height, coarsest, iters, max_shift_q8, min_eig, nullptr, q8, d_stats));
+    HIP_TRY(ctx, flowcheck_enqueue(st, q8[0], q8[1], height, width, alpha_q10, beta_q16, status_out, flow_out, d_stats + 8));
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        const struct { void* dst; size_t off, n; } back[5] = {{flow_out, o_flow, px * 8}, {fwd_q8_out, o_fwd, px * 8}, {bwd_q8_out, o_bwd, px * 8}, {stats_out, o_stats, 48}, {status_out, o_status, px}};
-        for (const auto& b : back) if (b.dst) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + b.off, S->d_io + b.off, b.n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        for (const auto& b : back) if (b.dst) memcpy(b.dst, S->h_io + b.off, b.n);
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

@@ -8,11 +8,6 @@
 constexpr int FC_LIMIT = 1 << 19;                                  // a component at or past it is not a flow
 constexpr unsigned FC_NAN = 0x7FC00000u;
 
-struct FlowCheckState {
-    // host form: device + pinned staging [fwd | bwd | marked | stats | status]
-    uint8_t *d_io = nullptr, *h_io = nullptr; size_t io_cap = 0;
-};
-
 // |v| >= 2^19 as one unsigned comparison (v + 2^19 - 1 wraps for no int32 v at or above -(2^19 - 1), and lands above the bound for every other)
 __device__ __forceinline__ bool fc_past(int v) { return (unsigned)v + (unsigned)(FC_LIMIT - 1) > 2u * (FC_LIMIT - 1); }
 __device__ __forceinline__ bool fc_not_flow(int2 v) { return fc_past(v.x) || fc_past(v.y); }
@@ -83,15 +78,6 @@ int flowcheck_params(vido_ctx* ctx, const char* who, int alpha_q10, int beta_q16
     return VIDO_OK;
 }
 
-void flowcheck_state_destroy(vido_ctx* ctx)
-{
-    FlowCheckState* S = ctx->flowcheck;
-    if (!S) return;
-    if (S->d_io) (void)hipFree(S->d_io);
-    if (S->h_io) (void)hipHostFree(S->h_io);
-    delete S; ctx->flowcheck = nullptr;
-}
-
 extern "C" int vido_flow_consistency(vido_ctx* ctx, const int32_t* fwd_q8, const int32_t* bwd_q8, int H, int W, int alpha_q10, int beta_q16, uint8_t* status_out, float* flow_marked_out,
                                      int32_t* stats_out, int on_device)
 {
@@ -103,34 +89,15 @@ extern "C" int vido_flow_consistency(vido_ctx* ctx, const int32_t* fwd_q8, const
     if (on_device && ((((uintptr_t)fwd_q8 | (uintptr_t)bwd_q8 | (uintptr_t)flow_marked_out) & 7) != 0 || ((uintptr_t)stats_out & 3) != 0))
         return vido_set_error(ctx, VIDO_E_INVALID, "flow_consistency: device fields and the marked flow must be 8-byte aligned, stats 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->flowcheck) ctx->flowcheck = new FlowCheckState();
-    FlowCheckState* S = ctx->flowcheck;
     hipStream_t st = on_device && ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
-    if (on_device) {
-        HIP_TRY(ctx, flowcheck_enqueue(st, fwd_q8, bwd_q8, H, W, alpha_q10, beta_q16, status_out, flow_marked_out, stats_out));
-        HIP_TRY(ctx, hipGetLastError());
-        return VIDO_OK;
+    if (!on_device) {                                                      // the host form: from here on the five pointers are their slots of the staging buffer
+        const size_t px = (size_t)W * H;
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&fwd_q8, px * 8); T.in(&bwd_q8, px * 8); T.out(&flow_marked_out, px * 8); T.out(&stats_out, 16); T.out(&status_out, px);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    const size_t px = (size_t)W * H, o_bwd = px * 8, o_marked = 2 * px * 8, o_stats = 3 * px * 8, o_status = o_stats + 16, io_total = o_status + px;
-    if (io_total > S->io_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
-        if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
-        S->io_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
-        S->io_cap = io_total;
-    }
-    memcpy(S->h_io, fwd_q8, px * 8); memcpy(S->h_io + o_bwd, bwd_q8, px * 8);
-    HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, 2 * px * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, flowcheck_enqueue(st, (const int32_t*)S->d_io, (const int32_t*)(S->d_io + o_bwd), H, W, alpha_q10, beta_q16, status_out ? S->d_io + o_status : nullptr,
-                                   flow_marked_out ? (float*)(S->d_io + o_marked) : nullptr, stats_out ? (int32_t*)(S->d_io + o_stats) : nullptr));
+    HIP_TRY(ctx, flowcheck_enqueue(st, fwd_q8, bwd_q8, H, W, alpha_q10, beta_q16, status_out, flow_marked_out, stats_out));
     HIP_TRY(ctx, hipGetLastError());
-    if (flow_marked_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_marked, S->d_io + o_marked, px * 8, hipMemcpyDeviceToHost, st));
-    if (stats_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_stats, S->d_io + o_stats, 16, hipMemcpyDeviceToHost, st));
-    if (status_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + o_status, S->d_io + o_status, px, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (flow_marked_out) memcpy(flow_marked_out, S->h_io + o_marked, px * 8);
-    if (stats_out) memcpy(stats_out, S->h_io + o_stats, 16);
-    if (status_out) memcpy(status_out, S->h_io + o_status, px);
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

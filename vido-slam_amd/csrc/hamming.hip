@@ -61,31 +61,13 @@ __global__ void k_hamming_finish(const unsigned long long* __restrict__ part, in
     else { idx[i] = (int)(uint32_t)v; dist[i] = (int)(v >> 32); }
 }
 
-// Persistent, growable device/pinned buffers (no per-call stream-ordered allocations: inputs are staged
-// through pinned memory so every transfer is ordered on the ctx stream).
-struct HamState {
-    uint8_t *d_a = nullptr, *d_b = nullptr; int *d_idx = nullptr, *d_dist = nullptr; unsigned long long* d_part = nullptr;
-    uint8_t* h_stage = nullptr;
-    size_t cap_a = 0, cap_b = 0, cap_part = 0, cap_stage = 0;
-};
-
-template <class T>
-static int grow(vido_ctx* ctx, T** p, size_t* cap, size_t need, bool pinned = false)
-{
-    if (need <= *cap) return VIDO_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*p) { if (pinned) HIP_TRY(ctx, hipHostFree(*p)); else HIP_TRY(ctx, hipFree(*p)); *p = nullptr; }
-    const size_t n = need + need / 2 + 64;
-    if (pinned) HIP_TRY(ctx, hipHostMalloc((void**)p, n * sizeof(T))); else HIP_TRY(ctx, hipMalloc((void**)p, n * sizeof(T)));
-    *cap = n;
-    return VIDO_OK;
-}
+struct HamState { unsigned long long* d_part = nullptr; size_t cap_part = 0; };      // [na][slabs] smallest key of a slab (capacity in bytes)
 
 void ham_state_destroy(vido_ctx* ctx)
 {
     HamState* S = ctx->ham;
     if (!S) return;
-    hipFree(S->d_a); hipFree(S->d_b); hipFree(S->d_idx); hipFree(S->d_dist); hipFree(S->d_part); hipHostFree(S->h_stage);
+    hipFree(S->d_part);
     delete S; ctx->ham = nullptr;
 }
 
@@ -105,38 +87,18 @@ extern "C" int vido_hamming_match(vido_ctx* ctx, const uint8_t* a, int na, const
     int nsl = std::max(1, std::min((nb + 63) / 64, (2048 + qblocks - 1) / qblocks));
     int slab = ((std::max(nb, 1) + nsl - 1) / nsl + 63) & ~63;
     nsl = std::max(1, (nb + slab - 1) / slab);
-    int rc;
-    if ((rc = grow(ctx, &S->d_part, &S->cap_part, (size_t)na * nsl))) return rc;
-    const uint8_t *da = a, *db = b; int *didx = idx_out, *ddist = dist_out;
-    if (!on_device) {
-        size_t capi = S->cap_a;
-        if ((rc = grow(ctx, &S->d_a, &S->cap_a, (size_t)na * 32))) return rc;
-        if (S->cap_a != capi || !S->d_idx) {
-            if (S->d_idx) { HIP_TRY(ctx, hipFree(S->d_idx)); HIP_TRY(ctx, hipFree(S->d_dist)); }
-            HIP_TRY(ctx, hipMalloc((void**)&S->d_idx, S->cap_a / 32 * 4 + 64)); HIP_TRY(ctx, hipMalloc((void**)&S->d_dist, S->cap_a / 32 * 4 + 64));
-        }
-        if ((rc = grow(ctx, &S->d_b, &S->cap_b, (size_t)std::max(nb, 1) * 32))) return rc;
-        const size_t bytes_in = ((size_t)na + nb) * 32, bytes_out = (size_t)na * 8;
-        if ((rc = grow(ctx, &S->h_stage, &S->cap_stage, std::max(bytes_in, bytes_out), true))) return rc;
-        memcpy(S->h_stage, a, (size_t)na * 32);
-        if (nb > 0) memcpy(S->h_stage + (size_t)na * 32, b, (size_t)nb * 32);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_a, S->h_stage, (size_t)na * 32, hipMemcpyHostToDevice, st));
-        if (nb > 0) HIP_TRY(ctx, hipMemcpyAsync(S->d_b, S->h_stage + (size_t)na * 32, (size_t)nb * 32, hipMemcpyHostToDevice, st));
-        da = S->d_a; db = S->d_b; didx = S->d_idx; ddist = S->d_dist;
+    if (int rc = vido_grow_device(ctx, st, (void**)&S->d_part, &S->cap_part, (size_t)na * nsl * 8, GROW_HEADROOM)) return rc;
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&a, (size_t)na * 32); T.in(&b, (size_t)nb * 32); T.out(&idx_out, (size_t)na * 4); T.out(&dist_out, (size_t)na * 4);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
     if (nb > 0)
-        hipLaunchKernelGGL(k_hamming, dim3(qblocks, nsl), dim3(256), 0, st, (const uint32_t*)da, na, (const uint32_t*)db, nb, slab, nsl, S->d_part);
+        hipLaunchKernelGGL(k_hamming, dim3(qblocks, nsl), dim3(256), 0, st, (const uint32_t*)a, na, (const uint32_t*)b, nb, slab, nsl, S->d_part);
     else
         HIP_TRY(ctx, hipMemsetAsync(S->d_part, 0xff, (size_t)na * nsl * 8, st));
-    hipLaunchKernelGGL(k_hamming_finish, dim3((na + 255) / 256), dim3(256), 0, st, S->d_part, nsl, na, didx, ddist);
+    hipLaunchKernelGGL(k_hamming_finish, dim3((na + 255) / 256), dim3(256), 0, st, S->d_part, nsl, na, idx_out, dist_out);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));        // staging buffer is reused for the results
-        int* hs = (int*)S->h_stage;
-        HIP_TRY(ctx, hipMemcpyAsync(hs, S->d_idx, (size_t)na * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(hs + na, S->d_dist, (size_t)na * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        memcpy(idx_out, hs, (size_t)na * 4); memcpy(dist_out, hs + na, (size_t)na * 4);
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

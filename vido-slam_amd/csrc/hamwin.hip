@@ -20,11 +20,9 @@ typedef hw_u32x4 hw_u32x4_a4 __attribute__((aligned(4)));                     //
 struct HwDesc { hw_u32x4_a4 lo, hi; };
 
 struct HamWinState {
-    unsigned long long* d_part = nullptr; size_t cap_part = 0;     // [nq][chunks][2] smallest and second smallest key of a chunk
+    unsigned long long* d_part = nullptr; size_t cap_part = 0;     // [nq][chunks][2] smallest and second smallest key of a chunk (capacities in bytes)
     unsigned long long* d_owner = nullptr; size_t cap_owner = 0;   // [nt] owner plane of the one-to-one rule
-    uint8_t* d_in = nullptr; size_t cap_in = 0;                    // host form: staged inputs
-    int32_t* d_out = nullptr; size_t cap_out = 0;                  // host form: idx, dist, dist2, status [nq each] + 5 counters; a device call without a counter array counts into its first 5 words
-    uint8_t* h_stage = nullptr; size_t cap_stage = 0;              // pinned mirror of both
+    int32_t* d_stats = nullptr;                                    // the five counters of a device call without a counter array
 };
 
 __device__ __forceinline__ void hw_insert(unsigned long long& k1, unsigned long long& k2, unsigned long long key)
@@ -146,31 +144,15 @@ __global__ __launch_bounds__(256) void k_hamwin_resolve(const unsigned long long
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-template <class T>
-static int hw_grow(vido_ctx* ctx, T** p, size_t* cap, size_t need, bool pinned = false)
-{
-    if (need <= *cap) return VIDO_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*p) { if (pinned) HIP_TRY(ctx, hipHostFree(*p)); else HIP_TRY(ctx, hipFree(*p)); *p = nullptr; *cap = 0; }
-    const size_t n = need + need / 2 + 64;
-    if (pinned) HIP_TRY(ctx, hipHostMalloc((void**)p, n * sizeof(T))); else HIP_TRY(ctx, hipMalloc((void**)p, n * sizeof(T)));
-    *cap = n;
-    return VIDO_OK;
-}
-
 void hamwin_state_destroy(vido_ctx* ctx)
 {
     HamWinState* S = ctx->hamwin;
     if (!S) return;
     if (S->d_part) (void)hipFree(S->d_part);
     if (S->d_owner) (void)hipFree(S->d_owner);
-    if (S->d_in) (void)hipFree(S->d_in);
-    if (S->d_out) (void)hipFree(S->d_out);
-    if (S->h_stage) (void)hipHostFree(S->h_stage);
+    if (S->d_stats) (void)hipFree(S->d_stats);
     delete S; ctx->hamwin = nullptr;
 }
-
-static inline size_t hw_up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 extern "C" int vido_hamming_match_window(vido_ctx* ctx, const uint8_t* q_desc, const float* q_xy, const int32_t* q_level, int nq,
                                          const uint8_t* t_desc, const float* t_xy, const int32_t* t_level, int nt,
@@ -193,42 +175,25 @@ extern "C" int vido_hamming_match_window(vido_ctx* ctx, const uint8_t* q_desc, c
     if (!ctx->hamwin) ctx->hamwin = new HamWinState();
     HamWinState* S = ctx->hamwin;
     const int nch = std::max(1, (nt + HW_CH - 1) / HW_CH);
-    int rc;
-    if ((rc = hw_grow(ctx, &S->d_part, &S->cap_part, (size_t)nq * nch * 2))) return rc;
-    if (unique && (rc = hw_grow(ctx, &S->d_owner, &S->cap_owner, (size_t)std::max(nt, 1)))) return rc;
-    if ((rc = hw_grow(ctx, &S->d_out, &S->cap_out, (size_t)(on_device ? 0 : 4 * (size_t)nq) + 8))) return rc;
-    const uint8_t *dqd = q_desc, *dtd = t_desc; const float *dqxy = q_xy, *dtxy = t_xy; const int32_t *dql = q_level, *dtl = t_level;
-    int32_t *didx = idx_out, *ddist = dist_out, *ddist2 = dist2_out, *dstatus = status_out, *dstats = stats_out ? stats_out : S->d_out;
-    const size_t o_qd = 0, o_qxy = hw_up16(o_qd + (size_t)nq * 32), o_ql = hw_up16(o_qxy + (size_t)nq * 8), o_td = hw_up16(o_ql + (size_t)nq * 4),
-                 o_txy = hw_up16(o_td + (size_t)nt * 32), o_tl = hw_up16(o_txy + (size_t)nt * 8), bytes_in = hw_up16(o_tl + (size_t)nt * 4);
-    const size_t bytes_out = (4 * (size_t)nq + 5) * sizeof(int32_t);
-    if (!on_device) {
-        if ((rc = hw_grow(ctx, &S->d_in, &S->cap_in, bytes_in))) return rc;
-        if ((rc = hw_grow(ctx, &S->h_stage, &S->cap_stage, std::max(bytes_in, bytes_out), true))) return rc;
-        memcpy(S->h_stage + o_qd, q_desc, (size_t)nq * 32); memcpy(S->h_stage + o_qxy, q_xy, (size_t)nq * 8); memcpy(S->h_stage + o_ql, q_level, (size_t)nq * 4);
-        if (nt > 0) { memcpy(S->h_stage + o_td, t_desc, (size_t)nt * 32); memcpy(S->h_stage + o_txy, t_xy, (size_t)nt * 8); memcpy(S->h_stage + o_tl, t_level, (size_t)nt * 4); }
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_in, S->h_stage, bytes_in, hipMemcpyHostToDevice, st));
-        dqd = S->d_in + o_qd; dqxy = (const float*)(S->d_in + o_qxy); dql = (const int32_t*)(S->d_in + o_ql);
-        dtd = S->d_in + o_td; dtxy = (const float*)(S->d_in + o_txy); dtl = (const int32_t*)(S->d_in + o_tl);
-        didx = S->d_out; ddist = didx + nq; ddist2 = ddist + nq; dstatus = ddist2 + nq; dstats = dstatus + nq;
+    if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 5 * sizeof(int32_t)));
+    if (int rc = vido_grow_device(ctx, st, (void**)&S->d_part, &S->cap_part, (size_t)nq * nch * 16, GROW_HEADROOM)) return rc;
+    if (unique) if (int rc = vido_grow_device(ctx, st, (void**)&S->d_owner, &S->cap_owner, (size_t)std::max(nt, 1) * 8, GROW_HEADROOM)) return rc;
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&q_desc, (size_t)nq * 32); T.in(&q_xy, (size_t)nq * 8); T.in(&q_level, (size_t)nq * 4); T.in(&t_desc, (size_t)nt * 32); T.in(&t_xy, (size_t)nt * 8); T.in(&t_level, (size_t)nt * 4);
+        T.out(&idx_out, (size_t)nq * 4); T.out(&dist_out, (size_t)nq * 4); T.out(&dist2_out, (size_t)nq * 4); T.out(&status_out, (size_t)nq * 4); T.keep(&stats_out, 5 * sizeof(int32_t));
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
+    int32_t* dstats = stats_out ? stats_out : S->d_stats;
     unsigned long long* owner = unique ? S->d_owner : nullptr;
     const int qblocks = (nq + 4 * HW_QW - 1) / (4 * HW_QW);
-    hipLaunchKernelGGL(k_hamwin, dim3(qblocks, nch), dim3(256), 0, st, (const uint32_t*)dqd, dqxy, dql, nq, (const HwDesc*)dtd, dtxy, dtl, nt, radius, level_tol, nch,
+    hipLaunchKernelGGL(k_hamwin, dim3(qblocks, nch), dim3(256), 0, st, (const uint32_t*)q_desc, q_xy, q_level, nq, (const HwDesc*)t_desc, t_xy, t_level, nt, radius, level_tol, nch,
                        S->d_part, owner, dstats);
     hipLaunchKernelGGL(k_hamwin_finish, dim3((nq + 255) / 256), dim3(256), 0, st, (const unsigned long long*)S->d_part, nch, nq, max_dist, ratio_num, ratio_den, owner,
-                       didx, ddist, ddist2, dstatus, dstats);
+                       idx_out, dist_out, dist2_out, status_out, dstats);
     if (unique)
-        hipLaunchKernelGGL(k_hamwin_resolve, dim3((nq + 255) / 256), dim3(256), 0, st, (const unsigned long long*)owner, nq, didx, (const int32_t*)ddist, dstatus, dstats);
+        hipLaunchKernelGGL(k_hamwin_resolve, dim3((nq + 255) / 256), dim3(256), 0, st, (const unsigned long long*)owner, nq, idx_out, (const int32_t*)dist_out, status_out, dstats);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));        // the staging buffer is reused for the results
-        HIP_TRY(ctx, hipMemcpyAsync(S->h_stage, S->d_out, bytes_out, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        const int32_t* hs = (const int32_t*)S->h_stage;
-        memcpy(idx_out, hs, (size_t)nq * 4); memcpy(dist_out, hs + nq, (size_t)nq * 4); memcpy(dist2_out, hs + 2 * (size_t)nq, (size_t)nq * 4);
-        memcpy(status_out, hs + 3 * (size_t)nq, (size_t)nq * 4);
-        if (stats_out) memcpy(stats_out, hs + 4 * (size_t)nq, 5 * sizeof(int32_t));
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

@@ -2,10 +2,6 @@
 // caller-given reference patch as an integer verdict (gfx950 only).  The statement is tests/refimpl/patch_points_np.py; every output is equal to it bit for bit.
 #include "common.hpp"
 
-struct PatchPtsState {
-    // host form: device + pinned staging of `cap` points, each [xyl 12 B | reference 64 B] in and [patch 64 B | sums 12 B | status 4 B] out
-    uint8_t *d_buf = nullptr, *h_buf = nullptr; int cap = 0;
-};
 
 // One wave per point, four points per workgroup, lane = pixel (row lane >> 3, column lane & 7), points in caller order; a wave reads nothing but its own point's row of the
 // inputs and its own 8 x 8 pixels, so a result depends neither on n nor on the order.  The pixel is ONE byte load per lane: the 8 rows are 8 runs of 8 bytes, i.e. the same
@@ -50,15 +46,6 @@ __global__ __launch_bounds__(256) void k_patch_points(const uint8_t* __restrict_
     status_out[kk] = st;
 }
 
-void patchpts_state_destroy(vido_ctx* ctx)
-{
-    PatchPtsState* S = ctx->patchpts;
-    if (!S) return;
-    if (S->d_buf) (void)hipFree(S->d_buf);
-    if (S->h_buf) (void)hipHostFree(S->h_buf);
-    delete S; ctx->patchpts = nullptr;
-}
-
 extern "C" int vido_orb_patch_points(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int min_var, int min_zncc_q10,
                                      uint8_t* patch_out, int32_t* sums_out, int32_t* status_out, int on_device)
 {
@@ -76,39 +63,13 @@ extern "C" int vido_orb_patch_points(vido_ctx* ctx, int frame, const int32_t* xy
     if (n == 0 || (!patch_out && !sums_out && !status_out)) return VIDO_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int* d_xyl = xyl; const uint8_t* d_ref = ref_patch; uint8_t* d_patch = patch_out; int *d_sums = sums_out, *d_status = status_out;
-    PatchPtsState* S = nullptr;
-    size_t o_ref = 0, o_patch = 0, o_sums = 0, o_status = 0;
-    if (!on_device) {
-        if (!ctx->patchpts) ctx->patchpts = new PatchPtsState();
-        S = ctx->patchpts;
-        if (n > S->cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (S->d_buf) { HIP_TRY(ctx, hipFree(S->d_buf)); S->d_buf = nullptr; }
-            if (S->h_buf) { HIP_TRY(ctx, hipHostFree(S->h_buf)); S->h_buf = nullptr; }
-            S->cap = 0;
-            const int cap = n + n / 2 + 64;
-            HIP_TRY(ctx, hipMalloc((void**)&S->d_buf, (size_t)cap * 156)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_buf, (size_t)cap * 156));
-            S->cap = cap;
-        }
-        o_ref = (size_t)n * 12; o_patch = o_ref + (size_t)n * 64; o_sums = o_patch + (size_t)n * 64; o_status = o_sums + (size_t)n * 12;
-        memcpy(S->h_buf, xyl, (size_t)n * 12);
-        if (ref_patch) memcpy(S->h_buf + o_ref, ref_patch, (size_t)n * 64);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_buf, S->h_buf, ref_patch ? o_patch : o_ref, hipMemcpyHostToDevice, st));
-        d_xyl = (const int*)S->d_buf; d_ref = ref_patch ? S->d_buf + o_ref : nullptr;
-        d_patch = patch_out ? S->d_buf + o_patch : nullptr; d_sums = sums_out ? (int*)(S->d_buf + o_sums) : nullptr; d_status = status_out ? (int*)(S->d_buf + o_status) : nullptr;
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&xyl, (size_t)n * 12); T.in(&ref_patch, (size_t)n * 64); T.out(&patch_out, (size_t)n * 64); T.out(&sums_out, (size_t)n * 12); T.out(&status_out, (size_t)n * 4);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    hipLaunchKernelGGL(k_patch_points, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, d_xyl, n, d_ref, min_var, (unsigned)min_zncc_q10, d_patch, d_sums, d_status);
+    hipLaunchKernelGGL(k_patch_points, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, xyl, n, ref_patch, min_var, (unsigned)min_zncc_q10, patch_out, sums_out, status_out);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        // only what was asked for comes back (the tracker's verification wants 4 bytes per point, its patch taking 64)
-        if (patch_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_patch, S->d_buf + o_patch, (size_t)n * 64, hipMemcpyDeviceToHost, st));
-        if (sums_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_sums, S->d_buf + o_sums, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-        if (status_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_status, S->d_buf + o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (patch_out) memcpy(patch_out, S->h_buf + o_patch, (size_t)n * 64);
-        if (sums_out) memcpy(sums_out, S->h_buf + o_sums, (size_t)n * 12);
-        if (status_out) memcpy(status_out, S->h_buf + o_status, (size_t)n * 4);
-    }
+    if (!on_device) return staging_download(ctx, st);              // only what was asked for comes back (the tracker's verification wants 4 bytes per point, its patch taking 64)
     return VIDO_OK;
 }

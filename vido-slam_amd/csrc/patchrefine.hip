@@ -2,11 +2,6 @@
 // slab, to 1/256 px and entirely in integers (gfx950 only).  The statement is tests/refimpl/patch_refine_np.py; every output is equal to it bit for bit.
 #include "common.hpp"
 
-struct PatchRefineState {
-    // host form: device + pinned staging of `cap` points, each [xyl 12 B | reference 64 B] in and (from the next 8-byte boundary) [cost 16 B | q8 8 B | iters 4 B | status 4 B]
-    // out, then stats 16 B
-    uint8_t *d_buf = nullptr, *h_buf = nullptr; int cap = 0;
-};
 
 constexpr int PR_N = 36;                                           // interior pixels of the patch: r, c in 1..6
 constexpr int PR_MAX_ITERS = 8, PR_MAX_SHIFT_Q8 = 512;
@@ -135,15 +130,6 @@ __global__ __launch_bounds__(256) void k_patch_refine(const uint8_t* __restrict_
     }
 }
 
-void patchrefine_state_destroy(vido_ctx* ctx)
-{
-    PatchRefineState* S = ctx->patchrefine;
-    if (!S) return;
-    if (S->d_buf) (void)hipFree(S->d_buf);
-    if (S->h_buf) (void)hipHostFree(S->h_buf);
-    delete S; ctx->patchrefine = nullptr;
-}
-
 extern "C" int vido_orb_patch_refine(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int iters, int max_shift_q8, int min_eig, int32_t* q8_out,
                                      int64_t* cost_out, int32_t* iters_out, int32_t* status_out, int32_t* stats_out, int on_device)
 {
@@ -167,45 +153,15 @@ extern "C" int vido_orb_patch_refine(vido_ctx* ctx, int frame, const int32_t* xy
         return VIDO_OK;
     }
     if (!q8_out && !cost_out && !iters_out && !status_out && !stats_out) return VIDO_OK;
-    const int* d_xyl = xyl; const uint8_t* d_ref = ref_patch; int *d_q8 = q8_out, *d_iters = iters_out, *d_status = status_out, *d_stats = stats_out; long long* d_cost = (long long*)cost_out;
-    PatchRefineState* S = nullptr;
-    size_t o_ref = 0, o_cost = 0, o_q8 = 0, o_iters = 0, o_status = 0, o_stats = 0;
-    if (!on_device) {
-        if (!ctx->patchrefine) ctx->patchrefine = new PatchRefineState();
-        S = ctx->patchrefine;
-        if (n > S->cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (S->d_buf) { HIP_TRY(ctx, hipFree(S->d_buf)); S->d_buf = nullptr; }
-            if (S->h_buf) { HIP_TRY(ctx, hipHostFree(S->h_buf)); S->h_buf = nullptr; }
-            S->cap = 0;
-            const int cap = n + n / 2 + 64;
-            HIP_TRY(ctx, hipMalloc((void**)&S->d_buf, (size_t)cap * 108 + 32)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_buf, (size_t)cap * 108 + 32));
-            S->cap = cap;
-        }
-        o_ref = (size_t)n * 12; o_cost = (o_ref + (size_t)n * 64 + 7) & ~(size_t)7; o_q8 = o_cost + (size_t)n * 16; o_iters = o_q8 + (size_t)n * 8; o_status = o_iters + (size_t)n * 4;
-        o_stats = o_status + (size_t)n * 4;
-        memcpy(S->h_buf, xyl, (size_t)n * 12); memcpy(S->h_buf + o_ref, ref_patch, (size_t)n * 64);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_buf, S->h_buf, o_ref + (size_t)n * 64, hipMemcpyHostToDevice, st));
-        d_xyl = (const int*)S->d_buf; d_ref = S->d_buf + o_ref;
-        d_cost = cost_out ? (long long*)(S->d_buf + o_cost) : nullptr; d_q8 = q8_out ? (int*)(S->d_buf + o_q8) : nullptr; d_iters = iters_out ? (int*)(S->d_buf + o_iters) : nullptr;
-        d_status = status_out ? (int*)(S->d_buf + o_status) : nullptr; d_stats = stats_out ? (int*)(S->d_buf + o_stats) : nullptr;
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&xyl, (size_t)n * 12); T.in(&ref_patch, (size_t)n * 64); T.out(&cost_out, (size_t)n * 16); T.out(&q8_out, (size_t)n * 8); T.out(&iters_out, (size_t)n * 4);
+        T.out(&status_out, (size_t)n * 4); T.out(&stats_out, 4 * sizeof(int32_t));
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    if (d_stats) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 4 * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_patch_refine, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, d_xyl, n, d_ref, iters, max_shift_q8, (long long)min_eig, d_q8, d_cost, d_iters, d_status, d_stats);
+    if (stats_out) HIP_TRY(ctx, hipMemsetAsync(stats_out, 0, 4 * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_patch_refine, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, xyl, n, ref_patch, iters, max_shift_q8, (long long)min_eig, q8_out, (long long*)cost_out, iters_out, status_out, stats_out);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        // one copy per output keeps the NULL case simple (4 to 16 bytes per point each)
-        if (cost_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_cost, S->d_buf + o_cost, (size_t)n * 16, hipMemcpyDeviceToHost, st));
-        if (q8_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_q8, S->d_buf + o_q8, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        if (iters_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_iters, S->d_buf + o_iters, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (status_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_status, S->d_buf + o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (stats_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_stats, S->d_buf + o_stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (cost_out) memcpy(cost_out, S->h_buf + o_cost, (size_t)n * 16);
-        if (q8_out) memcpy(q8_out, S->h_buf + o_q8, (size_t)n * 8);
-        if (iters_out) memcpy(iters_out, S->h_buf + o_iters, (size_t)n * 4);
-        if (status_out) memcpy(status_out, S->h_buf + o_status, (size_t)n * 4);
-        if (stats_out) memcpy(stats_out, S->h_buf + o_stats, 4 * sizeof(int32_t));
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

@@ -3,10 +3,6 @@
 // is equal to it bit for bit.
 #include "common.hpp"
 
-struct PatchSearchState {
-    // host form: device + pinned staging of `cap` points, each [xyl 12 B | reference 64 B] in and [dxy 8 B | sums 12 B | second 8 B | status 4 B] out, then stats 20 B
-    uint8_t *d_buf = nullptr, *h_buf = nullptr; int cap = 0;
-};
 
 constexpr int PS_MAX_R = 16;
 constexpr int PS_ROWS = 2 * PS_MAX_R + 8;                          // window rows at the largest radius
@@ -172,15 +168,6 @@ __global__ __launch_bounds__(256) void k_patch_search(const uint8_t* __restrict_
     }
 }
 
-void patchsearch_state_destroy(vido_ctx* ctx)
-{
-    PatchSearchState* S = ctx->patchsearch;
-    if (!S) return;
-    if (S->d_buf) (void)hipFree(S->d_buf);
-    if (S->h_buf) (void)hipHostFree(S->h_buf);
-    delete S; ctx->patchsearch = nullptr;
-}
-
 extern "C" int vido_orb_patch_search(vido_ctx* ctx, int frame, const int32_t* xyl, int n, int blurred, const uint8_t* ref_patch, int radius, int excl, int min_var, int min_zncc_q10,
                                      int peak_ratio_q10, int32_t* dxy_out, int32_t* sums_out, int32_t* second_out, int32_t* status_out, int32_t* stats_out, int on_device)
 {
@@ -206,45 +193,16 @@ extern "C" int vido_orb_patch_search(vido_ctx* ctx, int frame, const int32_t* xy
         return VIDO_OK;
     }
     if (!dxy_out && !sums_out && !second_out && !status_out && !stats_out) return VIDO_OK;
-    const int* d_xyl = xyl; const uint8_t* d_ref = ref_patch; int *d_dxy = dxy_out, *d_sums = sums_out, *d_second = second_out, *d_status = status_out, *d_stats = stats_out;
-    PatchSearchState* S = nullptr;
-    size_t o_ref = 0, o_dxy = 0, o_sums = 0, o_second = 0, o_status = 0, o_stats = 0;
-    if (!on_device) {
-        if (!ctx->patchsearch) ctx->patchsearch = new PatchSearchState();
-        S = ctx->patchsearch;
-        if (n > S->cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (S->d_buf) { HIP_TRY(ctx, hipFree(S->d_buf)); S->d_buf = nullptr; }
-            if (S->h_buf) { HIP_TRY(ctx, hipHostFree(S->h_buf)); S->h_buf = nullptr; }
-            S->cap = 0;
-            const int cap = n + n / 2 + 64;
-            HIP_TRY(ctx, hipMalloc((void**)&S->d_buf, (size_t)cap * 108 + 32)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_buf, (size_t)cap * 108 + 32));
-            S->cap = cap;
-        }
-        o_ref = (size_t)n * 12; o_dxy = o_ref + (size_t)n * 64; o_sums = o_dxy + (size_t)n * 8; o_second = o_sums + (size_t)n * 12; o_status = o_second + (size_t)n * 8; o_stats = o_status + (size_t)n * 4;
-        memcpy(S->h_buf, xyl, (size_t)n * 12); memcpy(S->h_buf + o_ref, ref_patch, (size_t)n * 64);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_buf, S->h_buf, o_dxy, hipMemcpyHostToDevice, st));
-        d_xyl = (const int*)S->d_buf; d_ref = S->d_buf + o_ref;
-        d_dxy = dxy_out ? (int*)(S->d_buf + o_dxy) : nullptr; d_sums = sums_out ? (int*)(S->d_buf + o_sums) : nullptr; d_second = second_out ? (int*)(S->d_buf + o_second) : nullptr;
-        d_status = status_out ? (int*)(S->d_buf + o_status) : nullptr; d_stats = stats_out ? (int*)(S->d_buf + o_stats) : nullptr;
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&xyl, (size_t)n * 12); T.in(&ref_patch, (size_t)n * 64); T.out(&dxy_out, (size_t)n * 8); T.out(&sums_out, (size_t)n * 12); T.out(&second_out, (size_t)n * 8);
+        T.out(&status_out, (size_t)n * 4); T.out(&stats_out, 5 * sizeof(int32_t));
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    if (d_stats) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 5 * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_patch_search, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, d_xyl, n, d_ref, radius, excl, min_var, (unsigned)min_zncc_q10, (unsigned)peak_ratio_q10,
-                       d_dxy, d_sums, d_second, d_status, d_stats);
+    if (stats_out) HIP_TRY(ctx, hipMemsetAsync(stats_out, 0, 5 * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_patch_search, dim3((n + 3) / 4), dim3(256), 0, st, blurred ? blur : pyr, P, xyl, n, ref_patch, radius, excl, min_var, (unsigned)min_zncc_q10, (unsigned)peak_ratio_q10,
+                       dxy_out, sums_out, second_out, status_out, stats_out);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        // the outputs asked for are one contiguous run of the staging buffer unless some are NULL: one copy per output keeps the NULL case simple (4 to 12 bytes per point each)
-        if (dxy_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_dxy, S->d_buf + o_dxy, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        if (sums_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_sums, S->d_buf + o_sums, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-        if (second_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_second, S->d_buf + o_second, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        if (status_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_status, S->d_buf + o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (stats_out) HIP_TRY(ctx, hipMemcpyAsync(S->h_buf + o_stats, S->d_buf + o_stats, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (dxy_out) memcpy(dxy_out, S->h_buf + o_dxy, (size_t)n * 8);
-        if (sums_out) memcpy(sums_out, S->h_buf + o_sums, (size_t)n * 12);
-        if (second_out) memcpy(second_out, S->h_buf + o_second, (size_t)n * 8);
-        if (status_out) memcpy(status_out, S->h_buf + o_status, (size_t)n * 4);
-        if (stats_out) memcpy(stats_out, S->h_buf + o_stats, 5 * sizeof(int32_t));
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

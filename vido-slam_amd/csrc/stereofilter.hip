@@ -17,11 +17,9 @@
 #include <cmath>
 
 struct StereoFilterState {
-    int32_t* d_planes = nullptr;                                  // [2][cap_px]: parent index per pixel (-1 = not valid), area at a root
-    size_t cap_px = 0;
+    int32_t* d_planes = nullptr;                                  // [2][px]: parent index per pixel (-1 = not valid), area at a root
+    size_t cap_bytes = 0;
     int32_t* d_stats = nullptr;                                   // the counters when the caller asks for none
-    uint8_t *d_io = nullptr, *h_io = nullptr;                     // staging of the host form
-    size_t io_cap = 0;
 };
 
 #define SF_T 32                                                   // tile edge
@@ -165,8 +163,6 @@ void stereofilter_state_destroy(vido_ctx* ctx)
     if (!S) return;
     if (S->d_planes) (void)hipFree(S->d_planes);
     if (S->d_stats) (void)hipFree(S->d_stats);
-    if (S->d_io) (void)hipFree(S->d_io);
-    if (S->h_io) (void)hipHostFree(S->h_io);
     delete S; ctx->sfilter = nullptr;
 }
 
@@ -176,29 +172,7 @@ static int sf_prepare(vido_ctx* ctx, hipStream_t st, size_t px)
     if (!ctx->sfilter) ctx->sfilter = new StereoFilterState();
     StereoFilterState* S = ctx->sfilter;
     if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 16));
-    if (px > S->cap_px) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (st != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (S->d_planes) { HIP_TRY(ctx, hipFree(S->d_planes)); S->d_planes = nullptr; }
-        S->cap_px = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_planes, 2 * px * 4));
-        S->cap_px = px;
-    }
-    return VIDO_OK;
-}
-
-static int sf_staging(vido_ctx* ctx, hipStream_t st, size_t io_total)
-{
-    StereoFilterState* S = ctx->sfilter;
-    if (io_total > S->io_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
-        if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
-        S->io_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
-        S->io_cap = io_total;
-    }
-    return VIDO_OK;
+    return vido_grow_device(ctx, st, (void**)&S->d_planes, &S->cap_bytes, 2 * px * 4, GROW_EXACT);
 }
 
 // the launches of one call on device pointers
@@ -240,25 +214,13 @@ extern "C" int vido_stereo_filter(vido_ctx* ctx, const int32_t* q4, const uint8_
     hipStream_t st = on_device && ctx->has_ext_stream ? ctx->ext_stream : ctx->stream;
     if (int rc = sf_prepare(ctx, st, px)) return rc;
     StereoFilterState* S = ctx->sfilter;
-    const size_t o_disp = px * 4, o_depth = 2 * px * 4, o_stats = 3 * px * 4, o_status = o_stats + 16, io_total = o_status + px;      // q4 first; the status image is read and written in place
-    const int32_t* d_q4 = q4; const uint8_t* d_status = status; float *d_disp = disp_out, *d_depth = depth_out; uint8_t* d_status_out = status_out;
-    int32_t* d_stats = stats_out ? stats_out : S->d_stats;
-    if (!on_device) {
-        if (int rc = sf_staging(ctx, st, io_total)) return rc;
-        memcpy(S->h_io, q4, px * 4); memcpy(S->h_io + o_status, status, px);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, px * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io + o_status, S->h_io + o_status, px, hipMemcpyHostToDevice, st));
-        d_q4 = (const int32_t*)S->d_io; d_status = S->d_io + o_status;
-        d_disp = disp_out ? (float*)(S->d_io + o_disp) : nullptr; d_depth = depth_out ? (float*)(S->d_io + o_depth) : nullptr;
-        d_status_out = status_out ? S->d_io + o_status : nullptr; d_stats = (int32_t*)(S->d_io + o_stats);
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;                                     // (the status image is read and written in one slot)
+        T.begin(); T.in(&q4, px * 4); T.out(&disp_out, px * 4); T.out(&depth_out, px * 4); T.keep(&stats_out, 16); T.inout(&status, &status_out, px);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    sf_enqueue(S, st, d_q4, d_status, width, height, max_diff_q4, min_region, bf, d_disp, d_status_out, d_depth, d_stats);
+    sf_enqueue(S, st, q4, status, width, height, max_diff_q4, min_region, bf, disp_out, status_out, depth_out, stats_out ? stats_out : S->d_stats);
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        const struct { void* dst; size_t off, n; } back[4] = {{disp_out, o_disp, px * 4}, {depth_out, o_depth, px * 4}, {stats_out, o_stats, 16}, {status_out, o_status, px}};
-        for (const auto& b : back) if (b.dst) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + b.off, S->d_io + b.off, b.n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        for (const auto& b : back) if (b.dst) memcpy(b.dst, S->h_io + b.off, b.n);
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

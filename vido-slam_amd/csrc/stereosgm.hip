@@ -15,8 +15,6 @@ struct StereoState {
     // scratch of one (w, h, D): [grey left | grey right | census left | census right | S], each 16-byte aligned
     uint8_t* d_scratch = nullptr; size_t scratch_cap = 0;
     int32_t* d_stats = nullptr;                                    // the counters of a call without a caller's stats buffer
-    // host form: device + pinned staging [left | right | disp | q4 | stats | status]
-    uint8_t *d_io = nullptr, *h_io = nullptr; size_t io_cap = 0;
 };
 
 struct SgmGeom { size_t grey_bytes, o_cen, cen_bytes, o_S, S_bytes, total; };
@@ -218,8 +216,6 @@ void stereo_state_destroy(vido_ctx* ctx)
     if (!S) return;
     if (S->d_scratch) (void)hipFree(S->d_scratch);
     if (S->d_stats) (void)hipFree(S->d_stats);
-    if (S->d_io) (void)hipFree(S->d_io);
-    if (S->h_io) (void)hipHostFree(S->h_io);
     delete S; ctx->stereo = nullptr;
 }
 
@@ -229,29 +225,7 @@ static int sg_prepare(vido_ctx* ctx, hipStream_t st, const SgmGeom& G)
     if (!ctx->stereo) ctx->stereo = new StereoState();
     StereoState* S = ctx->stereo;
     if (!S->d_stats) HIP_TRY(ctx, hipMalloc((void**)&S->d_stats, 16));
-    if (G.total > S->scratch_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (st != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (S->d_scratch) { HIP_TRY(ctx, hipFree(S->d_scratch)); S->d_scratch = nullptr; }
-        S->scratch_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_scratch, G.total));
-        S->scratch_cap = G.total;
-    }
-    return VIDO_OK;
-}
-
-static int sg_staging(vido_ctx* ctx, hipStream_t st, size_t io_total)
-{
-    StereoState* S = ctx->stereo;
-    if (io_total > S->io_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (S->d_io) { HIP_TRY(ctx, hipFree(S->d_io)); S->d_io = nullptr; }
-        if (S->h_io) { HIP_TRY(ctx, hipHostFree(S->h_io)); S->h_io = nullptr; }
-        S->io_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&S->d_io, io_total)); HIP_TRY(ctx, hipHostMalloc((void**)&S->h_io, io_total));
-        S->io_cap = io_total;
-    }
-    return VIDO_OK;
+    return vido_grow_device(ctx, st, (void**)&S->d_scratch, &S->scratch_cap, G.total, GROW_EXACT);
 }
 
 // the launches of one call on device pointers
@@ -301,23 +275,14 @@ extern "C" int vido_stereo_sgm(vido_ctx* ctx, const uint8_t* left, const uint8_t
     if (int rc = sg_prepare(ctx, st, G)) return rc;
     StereoState* S = ctx->stereo;
     const size_t img_bytes = (size_t)(height - 1) * stride + (size_t)width * channels, px = (size_t)width * height;
-    const size_t o_right = (img_bytes + 15) & ~(size_t)15, o_disp = 2 * o_right, o_q4 = o_disp + px * 4, o_stats = o_q4 + px * 4, o_status = o_stats + 16, io_total = o_status + px;
-    const uint8_t *d_left = left, *d_right = right; float* d_disp = disp_out; int32_t *d_q4 = q4_out, *d_stats = stats_out ? stats_out : S->d_stats; uint8_t* d_status = status_out;
-    if (!on_device) {
-        if (int rc = sg_staging(ctx, st, io_total)) return rc;
-        memcpy(S->h_io, left, img_bytes); memcpy(S->h_io + o_right, right, img_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(S->d_io, S->h_io, o_right + img_bytes, hipMemcpyHostToDevice, st));
-        d_left = S->d_io; d_right = S->d_io + o_right;
-        d_disp = disp_out ? (float*)(S->d_io + o_disp) : nullptr; d_q4 = q4_out ? (int32_t*)(S->d_io + o_q4) : nullptr;
-        d_status = status_out ? S->d_io + o_status : nullptr; d_stats = (int32_t*)(S->d_io + o_stats);
+    if (!on_device) {                                                      // the host form: from here on the pointers are their slots of the staging buffer
+        HostStaging& T = ctx->staging;
+        T.begin(); T.in(&left, img_bytes); T.in(&right, img_bytes); T.out(&disp_out, px * 4); T.out(&q4_out, px * 4); T.keep(&stats_out, 16); T.out(&status_out, px);
+        if (int rc = staging_upload(ctx, st)) return rc;
     }
-    HIP_TRY(ctx, sg_enqueue(S, st, G, d_left, d_right, channels, rgb_order, stride, width, height, max_disp, p1, p2, uniqueness, lr_tol, d_disp, d_q4, d_status, d_stats));
+    HIP_TRY(ctx, sg_enqueue(S, st, G, left, right, channels, rgb_order, stride, width, height, max_disp, p1, p2, uniqueness, lr_tol, disp_out, q4_out, status_out,
+                            stats_out ? stats_out : S->d_stats));
     HIP_TRY(ctx, hipGetLastError());
-    if (!on_device) {
-        const struct { void* dst; size_t off, n; } back[4] = {{disp_out, o_disp, px * 4}, {q4_out, o_q4, px * 4}, {stats_out, o_stats, 16}, {status_out, o_status, px}};
-        for (const auto& b : back) if (b.dst) HIP_TRY(ctx, hipMemcpyAsync(S->h_io + b.off, S->d_io + b.off, b.n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        for (const auto& b : back) if (b.dst) memcpy(b.dst, S->h_io + b.off, b.n);
-    }
+    if (!on_device) return staging_download(ctx, st);
     return VIDO_OK;
 }

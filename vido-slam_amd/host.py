@@ -122,6 +122,19 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _image_pair(op, a, b):
+    """two u8 host images of one shape, H x W or H x W x C -> (a, b, channels, row stride): the arrays' own stride when both have tight pixels and one stride, else of
+    contiguous copies"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.shape != b.shape or a.ndim not in (2, 3):
+        raise VidoError(-1, "%s: two u8 images of one shape, H x W or H x W x C, expected" % op)
+    cn = 1 if a.ndim == 2 else a.shape[2]
+    rows = lambda x: x.strides[1:] == ((cn, 1) if x.ndim == 3 else (1,)) and x.strides[0] >= x.shape[1] * cn
+    if not rows(a) or not rows(b) or a.strides[0] != b.strides[0]:
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a, b, cn, a.strides[0]
+
+
 class Context:
     """One vido_ctx: one HIP stream + device arena on one GPU."""
 
@@ -307,16 +320,10 @@ class Context:
         stride above the width is taken from the array's strides).  Integer inverse-compositional alignment of every 8 x 8 patch on a factor-2 pyramid of coarsest + 1
         levels, densified by photometric weights.  Returns (flow (H,W,2) f32 in pixels, q8 (H,W,2) i32 = the same in 1/256 px, stats (4,) i32 = patches that kept an
         iterate, flat, rejected, steps taken, over all levels)."""
-        img0, img1 = np.asarray(img0), np.asarray(img1)
-        if img0.dtype != np.uint8 or img1.dtype != np.uint8 or img0.shape != img1.shape or img0.ndim not in (2, 3):
-            raise VidoError(-1, "dis_flow: two u8 images of one shape, H x W or H x W x C, expected")
-        cn = 1 if img0.ndim == 2 else img0.shape[2]
-        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
-        if not rows(img0) or not rows(img1) or img0.strides[0] != img1.strides[0]:
-            img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
+        img0, img1, cn, stride = _image_pair("dis_flow", img0, img1)
         h, w = img0.shape[:2]
         flow = np.empty((h, w, 2), np.float32); q8 = np.empty((h, w, 2), np.int32); stats = np.empty(4, np.int32)
-        self._check(self.lib.vido_dis_flow(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+        self._check(self.lib.vido_dis_flow(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), stride, w, h, int(coarsest), int(iters),
                                            int(max_shift_q8), int(min_eig), _ptr(flow), _ptr(q8), _ptr(stats), 0))
         return flow, q8, stats
 
@@ -347,16 +354,10 @@ class Context:
         """dis_flow in both directions from one pyramid build, and flow_consistency of the two fields (vido_dis_flow_pair): images and flow parameters as for dis_flow, the
         check's as for flow_consistency.  Returns (flow_marked (H,W,2) f32, fwd_q8 (H,W,2) i32 = dis_flow(img0, img1)'s q8, bwd_q8 = dis_flow(img1, img0)'s q8, status
         (H,W) u8, stats (12,) i32 = the forward call's four counters, the backward call's, the check's), each bit-equal to the separate calls."""
-        img0, img1 = np.asarray(img0), np.asarray(img1)
-        if img0.dtype != np.uint8 or img1.dtype != np.uint8 or img0.shape != img1.shape or img0.ndim not in (2, 3):
-            raise VidoError(-1, "dis_flow_pair: two u8 images of one shape, H x W or H x W x C, expected")
-        cn = 1 if img0.ndim == 2 else img0.shape[2]
-        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
-        if not rows(img0) or not rows(img1) or img0.strides[0] != img1.strides[0]:
-            img0, img1 = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
+        img0, img1, cn, stride = _image_pair("dis_flow_pair", img0, img1)
         h, w = img0.shape[:2]
         flow = np.empty((h, w, 2), np.float32); fwd = np.empty((h, w, 2), np.int32); bwd = np.empty((h, w, 2), np.int32); status = np.empty((h, w), np.uint8); stats = np.empty(12, np.int32)
-        self._check(self.lib.vido_dis_flow_pair(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), img0.strides[0], w, h, int(coarsest), int(iters),
+        self._check(self.lib.vido_dis_flow_pair(self.h, img0.ctypes.data, img1.ctypes.data, cn, int(rgb_order), stride, w, h, int(coarsest), int(iters),
                                                 int(max_shift_q8), int(min_eig), int(alpha_q10), int(beta_q16), _ptr(flow), _ptr(fwd), _ptr(bwd), _ptr(status), _ptr(stats), 0))
         return flow, fwd, bwd, status, stats
 
@@ -373,16 +374,10 @@ class Context:
         the status is 0 and -1 elsewhere, q4 (H,W) i32 = the disparity of every pixel in 1/16 px, status (H,W) u8: 0 valid, 1 not unique, 2 left-right, 3 zero disparity,
         stats (4,) i32 = the count of each status).  Metres: depth = fx * baseline / disp; the front end does that division itself when the settings name the KITTI
         ChooseData code (facade.cpp:876), DepthMapFactor: 1 and Camera.bf = fx * baseline, and takes disp as the depth image (-1 is its "no depth")."""
-        left, right = np.asarray(left), np.asarray(right)
-        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.shape != right.shape or left.ndim not in (2, 3):
-            raise VidoError(-1, "stereo_sgm: two u8 images of one shape, H x W or H x W x C, expected")
-        cn = 1 if left.ndim == 2 else left.shape[2]
-        rows = lambda a: a.strides[1:] == ((cn, 1) if a.ndim == 3 else (1,)) and a.strides[0] >= a.shape[1] * cn
-        if not rows(left) or not rows(right) or left.strides[0] != right.strides[0]:
-            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+        left, right, cn, stride = _image_pair("stereo_sgm", left, right)
         h, w = left.shape[:2]
         disp = np.empty((h, w), np.float32); q4 = np.empty((h, w), np.int32); status = np.empty((h, w), np.uint8); stats = np.empty(4, np.int32)
-        self._check(self.lib.vido_stereo_sgm(self.h, left.ctypes.data, right.ctypes.data, cn, int(rgb_order), left.strides[0], w, h, int(max_disp), int(p1), int(p2),
+        self._check(self.lib.vido_stereo_sgm(self.h, left.ctypes.data, right.ctypes.data, cn, int(rgb_order), stride, w, h, int(max_disp), int(p1), int(p2),
                                              int(uniqueness), int(lr_tol), _ptr(disp), _ptr(q4), _ptr(status), _ptr(stats), 0))
         return disp, q4, status, stats
 

@@ -34,6 +34,54 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+def _tensor_args(op, table):
+    """The rules every tensor argument of a standalone op meets.  table: rows of (name, tensor, dtype, required), the first required tensor first: it is the device anchor.
+    A tensor that is given (a required one must be) is a contiguous device tensor of its dtype on the anchor's device.  Returns `bad`, which raises
+    VidoError(-1, "<op>: <why>"), for the op's own rules."""
+    from ..host import VidoError
+    def bad(why):
+        raise VidoError(-1, "%s: %s" % (op, why))
+    anchor_name, anchor = table[0][:2]
+    for name, t, dt, required in table:
+        if t is None and not required:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            bad("%s must be a device tensor; there is no CPU fallback" % name)
+        if t.dtype != dt:
+            bad("%s must be %s, got %s" % (name, dt, t.dtype))
+        if not t.is_contiguous():
+            bad("%s must be contiguous" % name)
+        if t.device != anchor.device:
+            bad("%s is on another device than %s" % (name, anchor_name))
+    return bad
+
+
+def _need(bad, name, t, shape):
+    """a tensor that is given has exactly this shape"""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        bad("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+
+
+def _need_count(bad, name, t, n):
+    """a tensor that is given holds at least n elements"""
+    if t is not None and t.numel() < n:
+        bad("%s needs %d elements" % (name, n))
+
+
+def _overlaps(a, b, nbytes):
+    """the first nbytes of the two tensors share memory"""
+    return a.data_ptr() < b.data_ptr() + nbytes and b.data_ptr() < a.data_ptr() + nbytes
+
+
+def _image_pair(bad, name0, img0, name1, img1):
+    """two images [H, W] or [H, W, 3|4] of one shape -> H, W, channels"""
+    if img0.dim() not in (2, 3) or (img0.dim() == 3 and img0.shape[2] not in (3, 4)):
+        bad("%s must be [H, W] or [H, W, 3|4], got %s" % (name0, tuple(img0.shape)))
+    if tuple(img1.shape) != tuple(img0.shape):
+        bad("%s must have %s's shape %s, got %s" % (name1, name0, tuple(img0.shape), tuple(img1.shape)))
+    return int(img0.shape[0]), int(img0.shape[1]), 1 if img0.dim() == 2 else int(img0.shape[2])
+
+
 def cached_pack(mod, slot, w, device, extra, pack):
     """pack() kept on `mod` as the attribute `slot`: made on first use and again when the weight tensor `w` (its storage or its version: a checkpoint loaded later), the
     device or one of the `extra` key parts differs from the call that made it."""
@@ -677,35 +725,17 @@ class HipOps:
         (x + rint(dx), y + rint(dy)); several on one pixel: the nearer, then the smaller label; an unhit pixel with 5 of 8 neighbours of one label takes it.  stats: an
         int32 tensor of >= 3 elements that receives (sources kept, pixels hit, pixels filled), or None.  Enqueued on torch's current stream, nothing is waited for; the
         first call of a context allocates, so it comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out aliasing mask raise."""
-        from ..host import VidoError
-        def bad(why):
-            raise VidoError(-1, "mask_propagate: " + why)
-        for name, t, dt in (("mask", mask, torch.int32), ("flow", flow, torch.float32), ("depth", depth, torch.float32), ("out", out, torch.int32), ("stats", stats, torch.int32)):
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != mask.device:
-                bad("%s is on another device than mask" % name)
+        bad = _tensor_args("mask_propagate", (("mask", mask, torch.int32, True), ("flow", flow, torch.float32, True), ("depth", depth, torch.float32, False),
+                                              ("out", out, torch.int32, False), ("stats", stats, torch.int32, False)))
         if mask.dim() != 2:
             bad("mask must be [H, W]")
         H, W = int(mask.shape[0]), int(mask.shape[1])
-        if tuple(flow.shape) != (H, W, 2):
-            bad("flow must be [%d, %d, 2], got %s" % (H, W, tuple(flow.shape)))
-        if depth is not None and tuple(depth.shape) != (H, W):
-            bad("depth must be [%d, %d], got %s" % (H, W, tuple(depth.shape)))
         if out is None:
             out = torch.empty((H, W), device=mask.device, dtype=torch.int32)
-        elif tuple(out.shape) != (H, W):
-            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
-        if out.data_ptr() < mask.data_ptr() + 4 * H * W and mask.data_ptr() < out.data_ptr() + 4 * H * W:
+        _need(bad, "flow", flow, (H, W, 2)); _need(bad, "depth", depth, (H, W)); _need(bad, "out", out, (H, W))
+        if _overlaps(out, mask, 4 * H * W):
             bad("out aliases mask")
-        if stats is not None and stats.numel() < 3:
-            bad("stats needs 3 elements")
+        _need_count(bad, "stats", stats, 3)
         self._call(self.ctx.lib.vido_mask_propagate, mask.data_ptr(), flow.data_ptr(), _p(depth), H, W, out.data_ptr(), _p(stats))
         return out
 
@@ -715,32 +745,13 @@ class HipOps:
         (patches that kept an iterate, flat, rejected, steps), or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/dis_flow_np.py.  Enqueued on
         torch's current stream, nothing is waited for; the first call of a size grows the context's scratch, so it comes before a graph capture.  CPU tensors, other
         dtypes or shapes and non-contiguous tensors raise."""
-        from ..host import VidoError
-        def bad(why):
-            raise VidoError(-1, "dis_flow: " + why)
-        for name, t, dt in (("prev", prev, torch.uint8), ("cur", cur, torch.uint8), ("out", out, torch.float32), ("q8", q8, torch.int32), ("stats", stats, torch.int32)):
-            if t is None and name not in ("prev", "cur"):
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != prev.device:
-                bad("%s is on another device than prev" % name)
-        if prev.dim() not in (2, 3) or (prev.dim() == 3 and prev.shape[2] not in (3, 4)):
-            bad("prev must be [H, W] or [H, W, 3|4], got %s" % (tuple(prev.shape),))
-        if tuple(cur.shape) != tuple(prev.shape):
-            bad("cur must have prev's shape %s, got %s" % (tuple(prev.shape), tuple(cur.shape)))
-        H, W = int(prev.shape[0]), int(prev.shape[1]); cn = 1 if prev.dim() == 2 else int(prev.shape[2])
+        bad = _tensor_args("dis_flow", (("prev", prev, torch.uint8, True), ("cur", cur, torch.uint8, True), ("out", out, torch.float32, False), ("q8", q8, torch.int32, False),
+                                        ("stats", stats, torch.int32, False)))
+        H, W, cn = _image_pair(bad, "prev", prev, "cur", cur)
         if out is None:
             out = torch.empty((H, W, 2), device=prev.device, dtype=torch.float32)
-        for name, t in (("out", out), ("q8", q8)):
-            if t is not None and tuple(t.shape) != (H, W, 2):
-                bad("%s must be [%d, %d, 2], got %s" % (name, H, W, tuple(t.shape)))
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need(bad, "out", out, (H, W, 2)); _need(bad, "q8", q8, (H, W, 2))
+        _need_count(bad, "stats", stats, 4)
         self._call(self.ctx.lib.vido_dis_flow, prev.data_ptr(), cur.data_ptr(), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
                    out.data_ptr(), _p(q8), _p(stats), 1)
         return out
@@ -751,33 +762,16 @@ class HipOps:
         elsewhere.  status: a uint8 [H,W] tensor that receives 0 consistent / 1 inconsistent / 2 leaves the image / 3 not a flow, or None; stats: an int32 tensor of >= 4
         elements that receives the four counts, or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/flow_consistency_np.py.  Enqueued on torch's
         current stream, nothing is waited for.  CPU tensors, other dtypes or shapes and non-contiguous tensors raise."""
-        from ..host import VidoError, FLOW_ALPHA_Q10, FLOW_BETA_Q16
-        def bad(why):
-            raise VidoError(-1, "flow_consistency: " + why)
-        for name, t, dt in (("fwd_q8", fwd_q8, torch.int32), ("bwd_q8", bwd_q8, torch.int32), ("status", status, torch.uint8), ("out", out, torch.float32), ("stats", stats, torch.int32)):
-            if t is None and name not in ("fwd_q8", "bwd_q8"):
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != fwd_q8.device:
-                bad("%s is on another device than fwd_q8" % name)
+        from ..host import FLOW_ALPHA_Q10, FLOW_BETA_Q16
+        bad = _tensor_args("flow_consistency", (("fwd_q8", fwd_q8, torch.int32, True), ("bwd_q8", bwd_q8, torch.int32, True), ("status", status, torch.uint8, False),
+                                                ("out", out, torch.float32, False), ("stats", stats, torch.int32, False)))
         if fwd_q8.dim() != 3 or fwd_q8.shape[2] != 2:
             bad("fwd_q8 must be [H, W, 2], got %s" % (tuple(fwd_q8.shape),))
-        if tuple(bwd_q8.shape) != tuple(fwd_q8.shape):
-            bad("bwd_q8 must have fwd_q8's shape %s, got %s" % (tuple(fwd_q8.shape), tuple(bwd_q8.shape)))
         H, W = int(fwd_q8.shape[0]), int(fwd_q8.shape[1])
         if out is None:
             out = torch.empty((H, W, 2), device=fwd_q8.device, dtype=torch.float32)
-        elif tuple(out.shape) != (H, W, 2):
-            bad("out must be [%d, %d, 2], got %s" % (H, W, tuple(out.shape)))
-        if status is not None and tuple(status.shape) != (H, W):
-            bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need(bad, "bwd_q8", bwd_q8, (H, W, 2)); _need(bad, "out", out, (H, W, 2)); _need(bad, "status", status, (H, W))
+        _need_count(bad, "stats", stats, 4)
         self._call(self.ctx.lib.vido_flow_consistency, _p(fwd_q8), _p(bwd_q8), H, W, int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10),
                    int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), _p(status), _p(out), _p(stats), 1)
         return out
@@ -789,35 +783,15 @@ class HipOps:
         tensors that receive the two fields in 1/256 px, or None; status: uint8 [H,W] or None; stats: int32 of >= 12 elements (the forward call's four counters, the
         backward call's, the check's) or None.  Enqueued on torch's current stream, nothing is waited for; the first call of a size grows the context's scratch, so it comes
         before a graph capture.  The argument checks are dis_flow's."""
-        from ..host import VidoError, FLOW_ALPHA_Q10, FLOW_BETA_Q16
-        def bad(why):
-            raise VidoError(-1, "dis_flow_pair: " + why)
-        for name, t, dt in (("prev", prev, torch.uint8), ("cur", cur, torch.uint8), ("out", out, torch.float32), ("fwd_q8", fwd_q8, torch.int32), ("bwd_q8", bwd_q8, torch.int32),
-                            ("status", status, torch.uint8), ("stats", stats, torch.int32)):
-            if t is None and name not in ("prev", "cur"):
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != prev.device:
-                bad("%s is on another device than prev" % name)
-        if prev.dim() not in (2, 3) or (prev.dim() == 3 and prev.shape[2] not in (3, 4)):
-            bad("prev must be [H, W] or [H, W, 3|4], got %s" % (tuple(prev.shape),))
-        if tuple(cur.shape) != tuple(prev.shape):
-            bad("cur must have prev's shape %s, got %s" % (tuple(prev.shape), tuple(cur.shape)))
-        H, W = int(prev.shape[0]), int(prev.shape[1]); cn = 1 if prev.dim() == 2 else int(prev.shape[2])
+        from ..host import FLOW_ALPHA_Q10, FLOW_BETA_Q16
+        bad = _tensor_args("dis_flow_pair", (("prev", prev, torch.uint8, True), ("cur", cur, torch.uint8, True), ("out", out, torch.float32, False),
+                                             ("fwd_q8", fwd_q8, torch.int32, False), ("bwd_q8", bwd_q8, torch.int32, False), ("status", status, torch.uint8, False),
+                                             ("stats", stats, torch.int32, False)))
+        H, W, cn = _image_pair(bad, "prev", prev, "cur", cur)
         if out is None:
             out = torch.empty((H, W, 2), device=prev.device, dtype=torch.float32)
-        for name, t in (("out", out), ("fwd_q8", fwd_q8), ("bwd_q8", bwd_q8)):
-            if t is not None and tuple(t.shape) != (H, W, 2):
-                bad("%s must be [%d, %d, 2], got %s" % (name, H, W, tuple(t.shape)))
-        if status is not None and tuple(status.shape) != (H, W):
-            bad("status must be [%d, %d], got %s" % (H, W, tuple(status.shape)))
-        if stats is not None and stats.numel() < 12:
-            bad("stats needs 12 elements")
+        _need(bad, "out", out, (H, W, 2)); _need(bad, "fwd_q8", fwd_q8, (H, W, 2)); _need(bad, "bwd_q8", bwd_q8, (H, W, 2)); _need(bad, "status", status, (H, W))
+        _need_count(bad, "stats", stats, 12)
         self._call(self.ctx.lib.vido_dis_flow_pair, _p(prev), _p(cur), cn, int(rgb_order), W * cn, W, H, int(coarsest), int(iters), int(max_shift_q8), int(min_eig),
                    int(FLOW_ALPHA_Q10 if alpha_q10 is None else alpha_q10), int(FLOW_BETA_Q16 if beta_q16 is None else beta_q16), _p(out), _p(fwd_q8), _p(bwd_q8), _p(status), _p(stats), 1)
         return out
@@ -829,33 +803,13 @@ class HipOps:
         counts, or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/stereo_sgm_np.py.  Enqueued on torch's current stream, nothing is waited for;
         the first call of a size grows the op's scratch, so it comes before a graph capture.  The argument checks are dis_flow's: CPU tensors, other dtypes or shapes and
         non-contiguous tensors raise."""
-        from ..host import VidoError
-        def bad(why):
-            raise VidoError(-1, "stereo_sgm: " + why)
-        for name, t, dt in (("left", left, torch.uint8), ("right", right, torch.uint8), ("out", out, torch.float32), ("q4", q4, torch.int32), ("status", status, torch.uint8),
-                            ("stats", stats, torch.int32)):
-            if t is None and name not in ("left", "right"):
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != left.device:
-                bad("%s is on another device than left" % name)
-        if left.dim() not in (2, 3) or (left.dim() == 3 and left.shape[2] not in (3, 4)):
-            bad("left must be [H, W] or [H, W, 3|4], got %s" % (tuple(left.shape),))
-        if tuple(right.shape) != tuple(left.shape):
-            bad("right must have left's shape %s, got %s" % (tuple(left.shape), tuple(right.shape)))
-        H, W = int(left.shape[0]), int(left.shape[1]); cn = 1 if left.dim() == 2 else int(left.shape[2])
+        bad = _tensor_args("stereo_sgm", (("left", left, torch.uint8, True), ("right", right, torch.uint8, True), ("out", out, torch.float32, False), ("q4", q4, torch.int32, False),
+                                          ("status", status, torch.uint8, False), ("stats", stats, torch.int32, False)))
+        H, W, cn = _image_pair(bad, "left", left, "right", right)
         if out is None:
             out = torch.empty((H, W), device=left.device, dtype=torch.float32)
-        for name, t in (("out", out), ("q4", q4), ("status", status)):
-            if t is not None and tuple(t.shape) != (H, W):
-                bad("%s must be [%d, %d], got %s" % (name, H, W, tuple(t.shape)))
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need(bad, "out", out, (H, W)); _need(bad, "q4", q4, (H, W)); _need(bad, "status", status, (H, W))
+        _need_count(bad, "stats", stats, 4)
         self._call(self.ctx.lib.vido_stereo_sgm, left.data_ptr(), right.data_ptr(), cn, int(rgb_order), W * cn, W, H, int(max_disp), int(p1), int(p2), int(uniqueness), int(lr_tol),
                    out.data_ptr(), _p(q4), _p(status), _p(stats), 1)
         return out
@@ -868,31 +822,16 @@ class HipOps:
         collision depth; needs bf, a float > 0), or None; stats: an int32 tensor of >= 4 elements that receives valid in / regions removed / pixels removed / valid out,
         or None.  The rule is include/vido_c.h's, the numpy statement tests/refimpl/stereo_filter_np.py.  Enqueued on torch's current stream, nothing is waited for; the
         first call of a size grows the op's scratch, so it comes before a graph capture.  CPU tensors, other dtypes or shapes and non-contiguous tensors raise."""
-        from ..host import VidoError, STEREO_FILTER_MAX_DIFF_Q4, STEREO_FILTER_MIN_REGION
-        def bad(why):
-            raise VidoError(-1, "stereo_filter: " + why)
-        for name, t, dt in (("q4", q4, torch.int32), ("status", status, torch.uint8), ("out", out, torch.float32), ("status_out", status_out, torch.uint8),
-                            ("depth", depth, torch.float32), ("stats", stats, torch.int32)):
-            if t is None and name not in ("q4", "status"):
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != q4.device:
-                bad("%s is on another device than q4" % name)
+        from ..host import STEREO_FILTER_MAX_DIFF_Q4, STEREO_FILTER_MIN_REGION
+        bad = _tensor_args("stereo_filter", (("q4", q4, torch.int32, True), ("status", status, torch.uint8, True), ("out", out, torch.float32, False),
+                                             ("status_out", status_out, torch.uint8, False), ("depth", depth, torch.float32, False), ("stats", stats, torch.int32, False)))
         if q4.dim() != 2:
             bad("q4 must be [H, W], got %s" % (tuple(q4.shape),))
         H, W = int(q4.shape[0]), int(q4.shape[1])
         if out is None:
             out = torch.empty((H, W), device=q4.device, dtype=torch.float32)
-        for name, t in (("status", status), ("out", out), ("status_out", status_out), ("depth", depth)):
-            if t is not None and tuple(t.shape) != (H, W):
-                bad("%s must be [%d, %d], got %s" % (name, H, W, tuple(t.shape)))
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need(bad, "status", status, (H, W)); _need(bad, "out", out, (H, W)); _need(bad, "status_out", status_out, (H, W)); _need(bad, "depth", depth, (H, W))
+        _need_count(bad, "stats", stats, 4)
         if depth is not None and bf is None:
             bad("depth needs bf")
         self._call(self.ctx.lib.vido_stereo_filter, q4.data_ptr(), status.data_ptr(), W, H, int(STEREO_FILTER_MAX_DIFF_Q4 if max_diff_q4 is None else max_diff_q4),
@@ -907,46 +846,27 @@ class HipOps:
         state's cursor; a previous id nothing matched is held in place for `hold` calls, then retired.  lut: int32 [>= 256] that receives slot + 1 -> id; stats: int32
         [>= 4] that receives (matched, fresh, lost, left out).  Enqueued on torch's current stream, nothing is waited for; the first call of a context allocates, so it
         comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out overlapping prev (or cur, other than being cur) raise."""
-        from ..host import VidoError
-        def bad(why):
-            raise VidoError(-1, "mask_associate: " + why)
-        for name, t, dt in (("cur", cur, torch.int32), ("prev", prev, torch.int32), ("state", state, torch.int32), ("classes", classes, torch.int64), ("out", out, torch.int32),
-                            ("lut", lut, torch.int32), ("stats", stats, torch.int32)):
-            if t is None:
-                if name in ("cur", "state"):
-                    bad("%s is required" % name)
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != cur.device:
-                bad("%s is on another device than cur" % name)
+        bad = _tensor_args("mask_associate", (("cur", cur, torch.int32, True), ("prev", prev, torch.int32, False), ("state", state, torch.int32, True),
+                                              ("classes", classes, torch.int64, False), ("out", out, torch.int32, False), ("lut", lut, torch.int32, False),
+                                              ("stats", stats, torch.int32, False)))
         if cur.dim() != 2:
             bad("cur must be [H, W]")
         H, W = int(cur.shape[0]), int(cur.shape[1])
-        if prev is not None and tuple(prev.shape) != (H, W):
-            bad("prev must be [%d, %d], got %s" % (H, W, tuple(prev.shape)))
+        _need(bad, "prev", prev, (H, W))
         if state.numel() != 768:
             bad("state needs 768 elements")
         if n is None:
             n = int(classes.numel()) if classes is not None else 127
         n = int(n)
-        if classes is not None and classes.numel() < n:
-            bad("classes holds %d elements, n = %d" % (classes.numel(), n))
+        _need_count(bad, "classes", classes, n)
         if out is None:
             out = torch.empty((H, W), device=cur.device, dtype=torch.int32)
-        elif tuple(out.shape) != (H, W):
-            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
-        for name, t in (("prev", prev), ("cur", cur)):
-            if t is not None and out.data_ptr() < t.data_ptr() + 4 * H * W and t.data_ptr() < out.data_ptr() + 4 * H * W and not (name == "cur" and out.data_ptr() == t.data_ptr()):
-                bad("out aliases %s" % name)
-        if lut is not None and lut.numel() < 256:
-            bad("lut needs 256 elements")
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need(bad, "out", out, (H, W))
+        if prev is not None and _overlaps(out, prev, 4 * H * W):
+            bad("out aliases prev")
+        if out.data_ptr() != cur.data_ptr() and _overlaps(out, cur, 4 * H * W):      # (out may be cur)
+            bad("out aliases cur")
+        _need_count(bad, "lut", lut, 256); _need_count(bad, "stats", stats, 4)
         self._call(self.ctx.lib.vido_mask_associate, _p(prev), _p(cur), H, W, _p(classes), n, int(hold), _p(state), _p(out), _p(lut), _p(stats))
         return out
 
@@ -957,37 +877,18 @@ class HipOps:
         k (0 behind the kept ones), areas: int32 [>= cap] the pixel counts, stats: int32 [>= 4] (found, dropped for area, left out for cap, kept).  With id_base 0 and
         cap 127 the result and `classes` are mask_associate's cur and classes.  Enqueued on torch's current stream, nothing is waited for; the first call of a context
         allocates, so it comes before a graph capture.  CPU tensors, other dtypes or shapes, non-contiguous tensors and out overlapping mask (other than being mask) raise."""
-        from ..host import VidoError
-        def bad(why):
-            raise VidoError(-1, "mask_components: " + why)
-        for name, t, dt in (("mask", mask, torch.int32), ("out", out, torch.int32), ("classes", classes, torch.int64), ("areas", areas, torch.int32), ("stats", stats, torch.int32)):
-            if t is None:
-                if name == "mask":
-                    bad("mask is required")
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                bad("%s must be a device tensor; there is no CPU fallback" % name)
-            if t.dtype != dt:
-                bad("%s must be %s, got %s" % (name, dt, t.dtype))
-            if not t.is_contiguous():
-                bad("%s must be contiguous" % name)
-            if t.device != mask.device:
-                bad("%s is on another device than mask" % name)
+        bad = _tensor_args("mask_components", (("mask", mask, torch.int32, True), ("out", out, torch.int32, False), ("classes", classes, torch.int64, False),
+                                               ("areas", areas, torch.int32, False), ("stats", stats, torch.int32, False)))
         if mask.dim() != 2:
             bad("mask must be [H, W]")
         H, W = int(mask.shape[0]), int(mask.shape[1])
         if out is None:
             out = torch.empty((H, W), device=mask.device, dtype=torch.int32)
-        elif tuple(out.shape) != (H, W):
-            bad("out must be [%d, %d], got %s" % (H, W, tuple(out.shape)))
-        if out.data_ptr() != mask.data_ptr() and out.data_ptr() < mask.data_ptr() + 4 * H * W and mask.data_ptr() < out.data_ptr() + 4 * H * W:
+        _need(bad, "out", out, (H, W))
+        if out.data_ptr() != mask.data_ptr() and _overlaps(out, mask, 4 * H * W):      # (out may be mask)
             bad("out aliases mask")
         cap = int(cap)
-        for name, t in (("classes", classes), ("areas", areas)):
-            if t is not None and t.numel() < cap:
-                bad("%s holds %d elements, cap = %d" % (name, t.numel(), cap))
-        if stats is not None and stats.numel() < 4:
-            bad("stats needs 4 elements")
+        _need_count(bad, "classes", classes, cap); _need_count(bad, "areas", areas, cap); _need_count(bad, "stats", stats, 4)
         self._call(self.ctx.lib.vido_mask_components, _p(mask), H, W, int(connectivity), int(min_area), int(id_base), cap, _p(out), _p(classes), _p(areas), _p(stats))
         return out
 
