@@ -292,6 +292,28 @@ int vido_stereo_filter(vido_ctx* ctx, const int32_t* q4 /* [h*w], 1/16 px */, co
                        float* disp_out /* [h*w], NULL ok */, uint8_t* status_out /* [h*w], NULL ok; may BE status */, float* depth_out /* [h*w], NULL ok */,
                        int32_t* stats_out /* [4], NULL ok */, int on_device);
 
+/* Rectification of one camera image, or of the two of a stereo rig in one launch: dst(u, v) = the bilinear mean of src at the map's entry for (u, v), entirely in integers
+ * (defined by tests/refimpl/stereo_rectify_np.py, exact to the bit; no reference counterpart: its datasets come rectified).  The maps are vido_rectify_map's (below), or
+ * any int32 [dst_h][dst_w][2] arrays of that form: (mx, my), x first, in 1/256 px of the source.  src: src_w x src_h u8 pixels of 1, 3 or 4 interleaved channels, rows
+ * src_stride bytes apart; dst: dst_w x dst_h pixels of the same channels, rows dst_stride bytes apart; both cameras share the sizes, the channels and the strides.
+ *   inside      0 <= mx <= (src_w - 1) 256 and 0 <= my <= (src_h - 1) 256
+ *   corners     x0 = mx >> 8, ax = mx & 255, x1 = min(x0 + 1, src_w - 1); likewise y0, ay, y1
+ *   value       ((256 - ax)(256 - ay) s[y0][x0][c] + ax (256 - ay) s[y0][x1][c] + (256 - ax) ay s[y1][x0][c] + ax ay s[y1][x1][c] + 32768) >> 16 for every channel c alike,
+ *               a fourth one included; the sum stays below 2^31
+ *   elsewhere   every channel 0.  No source byte is read for a pixel that is not inside, whatever the map holds (INT32_MIN, vido_rectify_map's "no source", included)
+ * insideK_out [dst_h*dst_w] = 1 where inside, 0 elsewhere; NULL ok.  src1 NULL: one camera; then map1, dst1 and inside1_out are NULL too.  VIDO_E_INVALID, with no output
+ * written, for a NULL src0 / map0 / dst0, for src1, map1, dst1 not all given or all NULL, channels outside {1, 3, 4}, a stride below width * channels, sizes outside
+ * 16 .. 4095, a destination (image or inside plane) that overlaps a source image or a map, and device maps that are not 4-byte aligned.  Needs no extractor state and not
+ * the context's configured frame size.  on_device != 0: every pointer is a device pointer and the call only enqueues on the ctx stream (vido_set_stream's when one is
+ * set): one launch for both cameras, no host synchronisation, no scratch, so a call can sit inside a stream capture from the first call on.  Any byte alignment of the
+ * images and any stride work; a thread writes its four pixels in one dword / three dwords / 16 bytes where their address allows it (a 4-byte aligned row; for 4 channels
+ * a 16-byte aligned one) and reads their map entries as two 16-byte loads where the entries' address is 16-byte aligned (a 16-byte aligned map of an even dst_w).
+ * Otherwise the arrays are the caller's host arrays, staged through pinned buffers that grow on demand (the bytes between the destination's rows are kept), and the call
+ * returns when the results are there. */
+int vido_rectify(vido_ctx* ctx, const uint8_t* src0, const uint8_t* src1 /* NULL: one camera */, int channels, int src_stride, int src_w, int src_h,
+                 const int32_t* map0 /* [dst_h*dst_w*2] */, const int32_t* map1, int dst_w, int dst_h, uint8_t* dst0, uint8_t* dst1, int dst_stride,
+                 uint8_t* inside0_out /* [dst_h*dst_w], NULL ok */, uint8_t* inside1_out /* NULL ok */, int on_device);
+
 /* ---- Hamming -------------------------------------------------------------------------------------
  * For each of the na 256-bit descriptors in a: index of the closest descriptor in b (smallest Hamming
  * distance, lowest index on ties) and that distance.  on_device!=0: a, b, idx_out, dist_out are device
@@ -855,6 +877,20 @@ typedef struct vido_host_maps { const int32_t* mask; const float* depth; const f
  * z + gaussian(z*z / (725*0.5) * 0.15); seed 0 = time(NULL) as the reference.  Host function (cv::RNG's multiply-with-carry + ziggurat restated; OpenCV side unpinned). */
 float vido_depth_noise(float z, unsigned seed);
 int vido_undistort_points(const float* xy, int n, const float K[4], const float dist[5], float* xy_out);
+/* The rectification map of one camera for vido_rectify: for every pixel (u, v) of the rectified view, the raw pixel that shows the same ray, in 1/256 px (defined by
+ * tests/refimpl/stereo_rectify_np.py; EXACT equality: the library is built without contraction).  K = (fx, fy, cx, cy) of the raw camera, dist = (k1, k2, p1, p2, k3),
+ * R 3 x 3 row-major from raw-camera to rectified coordinates (OpenCV's R1 / R2, ORB-SLAM's LEFT.R), P = (fx', fy', cx', cy') of the rectified camera.  Each operation is
+ * one IEEE double operation in this order, nothing fused:
+ *   x = (u - cx') / fx';  y = (v - cy') / fy'
+ *   X = R00 x + R10 y + R20;  Y = R01 x + R11 y + R21;  W = R02 x + R12 y + R22                (R transposed times (x, y, 1))
+ *   xn = X / W;  yn = Y / W;  r2 = xn xn + yn yn;  rad = 1 + ((k3 r2 + k2) r2 + k1) r2
+ *   xd = xn rad + (2 p1 xn yn + p2 (r2 + 2 xn xn));  yd = yn rad + (p1 (r2 + 2 yn yn) + 2 p2 xn yn)
+ *   us = fx xd + cx;  vs = fy yd + cy;  mx = floor(us 256 + 0.5);  my = floor(vs 256 + 0.5)
+ * W <= 0, a value that is not finite, or |mx| or |my| >= 2^30: both entries INT32_MIN ("no source").  map_out int32 [dst_h][dst_w][2], x first; inside_out [dst_h*dst_w]
+ * = vido_rectify's inside for a src_w x src_h source, NULL ok; *inside_count_out = their count, NULL ok.  Host only: no context, no GPU call.  VIDO_E_INVALID for a NULL
+ * parameter array or map_out, sizes outside 16 .. 4095, parameters that are not finite and fx, fy, fx', fy' <= 0. */
+int vido_rectify_map(const double K[4], const double dist[5], const double R[9], const double P[4], int src_w, int src_h, int dst_w, int dst_h,
+                     int32_t* map_out, uint8_t* inside_out /* NULL ok */, int32_t* inside_count_out /* NULL ok */);
 /* Tracking::RenewFrameInfo, static part (Tracking.cc:2973-3075): the inliers TM_sta (indices into stat_xy = mvStatKeys, -1 = rejected) that still pass the mask /
  * depth <= 40 / flow tests, then top-up from sample_xy (= mvKeys) in stride-20 passes, skipping samples closer than 1 px to a kept inlier, until max_num.
  * Element k of the result: src_out[k] = index into stat_xy (inlier_out[k] >= 0) or into sample_xy (inlier_out[k] == -1), inlier_out[k] (nStaInlierID),

@@ -75,6 +75,42 @@ int vido_undistort_points(const float* xy, int n, const float K[4], const float 
     return VIDO_OK;
 }
 
+// The rectification map of one camera (the rule: include/vido_c.h; the numpy statement: tests/refimpl/stereo_rectify_np.py).  Every line is one IEEE double operation
+// per operator in the order written — the library is built with -ffp-contract=off, so nothing fuses — and the map equals the statement's exactly.
+int vido_rectify_map(const double K[4], const double dist[5], const double R[9], const double P[4], int src_w, int src_h, int dst_w, int dst_h, int32_t* map_out,
+                     uint8_t* inside_out, int32_t* inside_count_out)
+{
+    if (!K || !dist || !R || !P || !map_out) return VIDO_E_INVALID;
+    if (src_w < 16 || src_h < 16 || dst_w < 16 || dst_h < 16 || src_w > 4095 || src_h > 4095 || dst_w > 4095 || dst_h > 4095) return VIDO_E_INVALID;
+    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i]) || !std::isfinite(P[i])) return VIDO_E_INVALID;
+    for (int i = 0; i < 5; i++) if (!std::isfinite(dist[i])) return VIDO_E_INVALID;
+    for (int i = 0; i < 9; i++) if (!std::isfinite(R[i])) return VIDO_E_INVALID;
+    if (!(K[0] > 0) || !(K[1] > 0) || !(P[0] > 0) || !(P[1] > 0)) return VIDO_E_INVALID;
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], fxp = P[0], fyp = P[1], cxp = P[2], cyp = P[3];
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4];
+    const double lim = 1073741824.0;                                  // 2^30
+    const int ex = (src_w - 1) * 256, ey = (src_h - 1) * 256;
+    int32_t count = 0;
+    for (int v = 0; v < dst_h; v++) for (int u = 0; u < dst_w; u++) {
+        const double x = ((double)u - cxp) / fxp, y = ((double)v - cyp) / fyp;
+        const double X = R[0] * x + R[3] * y + R[6], Y = R[1] * x + R[4] * y + R[7], W = R[2] * x + R[5] * y + R[8];
+        const double xn = X / W, yn = Y / W, r2 = xn * xn + yn * yn;
+        const double rad = 1 + ((k3 * r2 + k2) * r2 + k1) * r2;
+        const double xd = xn * rad + (2 * p1 * xn * yn + p2 * (r2 + 2 * xn * xn)), yd = yn * rad + (p1 * (r2 + 2 * yn * yn) + 2 * p2 * xn * yn);
+        const double us = fx * xd + cx, vs = fy * yd + cy;
+        const double mx = std::floor(us * 256 + 0.5), my = std::floor(vs * 256 + 0.5);
+        const size_t i = (size_t)v * dst_w + u;
+        const bool ok = W > 0 && std::isfinite(mx) && std::isfinite(my) && std::fabs(mx) < lim && std::fabs(my) < lim;
+        const int32_t ix = ok ? (int32_t)mx : INT32_MIN, iy = ok ? (int32_t)my : INT32_MIN;
+        map_out[2 * i] = ix; map_out[2 * i + 1] = iy;
+        const bool in = ix >= 0 && ix <= ex && iy >= 0 && iy <= ey;
+        if (inside_out) inside_out[i] = in ? 1 : 0;
+        count += in;
+    }
+    if (inside_count_out) *inside_count_out = count;
+    return VIDO_OK;
+}
+
 // values of the three maps at ((int)x, (int)y) of every point of a list: what the renew stages read from mSegMap / mDepthMap / mFlowMap.  Points outside the image
 // are never looked at by the stages (their bounds test comes first), so their entries may hold anything.
 static void sample_maps(const vido_host_maps* m, const float* xy, int n, std::vector<int32_t>& mask, std::vector<float>& depth, std::vector<float>& flow)

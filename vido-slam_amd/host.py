@@ -409,6 +409,44 @@ class Context:
         self._check(self.lib.vido_stereo_filter(self.h, q4_ptr, status_ptr, int(width), int(height), int(max_diff_q4), int(min_region), float(bf), disp_ptr, status_out_ptr,
                                                 depth_ptr, stats_ptr, 1))
 
+    def rectify(self, src0, map0, src1=None, map1=None, dst0=None, dst1=None, inside=True):
+        """Rectification of one raw image, or of a rig's two in one launch (vido_rectify; the statement is tests/refimpl/stereo_rectify_np.py): src u8 H x W or H x W x 1|3|4
+        host arrays (both of one shape; a row stride above the width is taken from the arrays' strides), map int32 h x w x 2 from rectify_map, or of that form.  dst0 / dst1:
+        u8 arrays h x w (x C) to write into — their row stride may exceed the row, the bytes in between are kept — or None for new ones.  Returns (dst0, inside0) with one
+        camera and (dst0, dst1, inside0, inside1) with two; inside u8 h x w = 1 where the map entry lies in the source, None with inside=False."""
+        two = src1 is not None
+        if (map1 is not None) != two or (dst1 is not None and not two):
+            raise VidoError(-1, "rectify: src1 and map1 are given together or not at all")
+        if two:
+            src0, src1, cn, sstride = _image_pair("rectify", src0, src1)
+        else:
+            src0, _, cn, sstride = _image_pair("rectify", src0, src0)
+        map0 = np.ascontiguousarray(map0); map1 = np.ascontiguousarray(map1) if two else None
+        if map0.dtype != np.int32 or map0.ndim != 3 or map0.shape[2] != 2 or (two and (map1.dtype != np.int32 or map1.shape != map0.shape)):
+            raise VidoError(-1, "rectify: int32 maps h x w x 2 of one shape expected")
+        sh, sw = src0.shape[:2]; h, w = map0.shape[:2]
+        shape = (h, w) + src0.shape[2:]
+        outs = []
+        for d in (dst0, dst1)[:2 if two else 1]:
+            if d is None:
+                d = np.empty(shape, np.uint8)
+            if not isinstance(d, np.ndarray) or d.dtype != np.uint8 or d.shape != shape or d.strides[1:] != ((cn, 1) if d.ndim == 3 else (1,)) or d.strides[0] < w * cn:
+                raise VidoError(-1, "rectify: dst must be a u8 array %s with tight pixels" % (shape,))
+            outs.append(d)
+        if two and outs[0].strides[0] != outs[1].strides[0]:
+            raise VidoError(-1, "rectify: dst0 and dst1 must share the row stride")
+        ins = [np.empty((h, w), np.uint8) if inside else None for _ in outs]
+        self._check(self.lib.vido_rectify(self.h, src0.ctypes.data, src1.ctypes.data if two else None, cn, sstride, sw, sh, _ptr(map0), _ptr(map1), w, h, outs[0].ctypes.data,
+                                          outs[1].ctypes.data if two else None, outs[0].strides[0], _ptr(ins[0]), _ptr(ins[1]) if two else None, 0))
+        return (outs[0], outs[1], ins[0], ins[1]) if two else (outs[0], ins[0])
+
+    def rectify_device(self, src0_ptr, map0_ptr, dst0_ptr, channels, src_stride, src_w, src_h, dst_w, dst_h, dst_stride, src1_ptr=None, map1_ptr=None, dst1_ptr=None,
+                       inside0_ptr=None, inside1_ptr=None):
+        """Device-pointer form: one launch enqueued on the context's stream, no scratch and no wait, so it can be captured from the first call on; src1 / map1 / dst1 are
+        given together (two cameras) or not at all."""
+        self._check(self.lib.vido_rectify(self.h, src0_ptr, src1_ptr, int(channels), int(src_stride), int(src_w), int(src_h), map0_ptr, map1_ptr, int(dst_w), int(dst_h), dst0_ptr,
+                                          dst1_ptr, int(dst_stride), inside0_ptr, inside1_ptr, 1))
+
     def orb_timing(self):
         t = np.zeros(8, np.float32)
         self._check(self.lib.vido_orb_last_timing(self.h, _ptr(t)))
@@ -955,6 +993,24 @@ def undistort_points(xy, K, dist):
     Kf = np.ascontiguousarray(K, np.float32); d = np.zeros(5, np.float32); d[:len(dist)] = dist
     _rc(load_library().vido_undistort_points(_ptr(xy), len(xy), _ptr(Kf), _ptr(d), _ptr(out)), "undistort_points")
     return out
+
+
+def rectify_map(K, dist, R, P, src_size, dst_size):
+    """The rectification map of one camera (vido_rectify_map; host only, float64, exactly tests/refimpl/stereo_rectify_np.py's): K = (fx, fy, cx, cy) of the raw camera,
+    dist = (k1, k2, p1, p2[, k3]), R 3 x 3 from raw-camera to rectified coordinates (OpenCV's R1 / R2), P = (fx', fy', cx', cy') of the rectified camera, src_size and
+    dst_size = (w, h) -> (map int32 [h, w, 2]: the raw pixel of every rectified pixel in 1/256 px, x first, INT32_MIN where there is none; inside u8 [h, w]: 1 where
+    that pixel lies in the raw image)."""
+    Kd = np.ascontiguousarray(K, np.float64).ravel(); Pd = np.ascontiguousarray(P, np.float64).ravel(); Rd = np.ascontiguousarray(R, np.float64).ravel()
+    d = np.zeros(5, np.float64); dist = np.asarray(dist, np.float64).ravel()
+    if Kd.size != 4 or Pd.size != 4 or Rd.size != 9 or dist.size not in (4, 5):
+        raise VidoError(-1, "rectify_map: K[4], dist[4|5], R[3][3], P[4] expected")
+    d[:dist.size] = dist
+    (sw, sh), (dw, dh) = (int(v) for v in src_size), (int(v) for v in dst_size)
+    if not all(16 <= v <= 4095 for v in (sw, sh, dw, dh)):
+        raise VidoError(-1, "rectify_map: sizes outside 16 .. 4095")
+    m = np.empty((dh, dw, 2), np.int32); inside = np.empty((dh, dw), np.uint8)
+    _rc(load_library().vido_rectify_map(_ptr(Kd), _ptr(d), _ptr(Rd), _ptr(Pd), sw, sh, dw, dh, _ptr(m), _ptr(inside), None), "rectify_map: parameters that are not finite, or a focal length <= 0")
+    return m, inside
 
 
 def renew_static(mask, depth, flow, stat_xy, TM_sta, sample_xy, max_num):

@@ -838,6 +838,34 @@ class HipOps:
                    int(STEREO_FILTER_MIN_REGION if min_region is None else min_region), 0.0 if bf is None else float(bf), out.data_ptr(), _p(status_out), _p(depth), _p(stats), 1)
         return out
 
+    def rectify(self, left, map_left, right=None, map_right=None, out_left=None, out_right=None, inside_left=None, inside_right=None):
+        """vido_rectify on device tensors: left uint8 [H,W] or [H,W,3|4] (a raw camera image) and map_left int32 [h,w,2] (host.rectify_map's, uploaded) -> the rectified
+        image, uint8 [h,w] or [h,w,3|4] (`out_left`, or a new tensor).  right / map_right: the rig's second camera, of left's shape and map_left's shape, rectified in the
+        same launch into `out_right` or a new tensor; the call then returns the pair.  inside_left / inside_right: uint8 [h,w] tensors that receive 1 where the map entry
+        lies in the source and 0 elsewhere, or None.  A pixel outside is 0 in every channel.  The rule is include/vido_c.h's, the numpy statement
+        tests/refimpl/stereo_rectify_np.py.  One launch enqueued on torch's current stream, no scratch, nothing is waited for: it can be captured from the first call on.
+        CPU tensors, other dtypes or shapes, non-contiguous tensors and an output that shares memory with an input raise."""
+        two = right is not None
+        bad = _tensor_args("rectify", (("left", left, torch.uint8, True), ("map_left", map_left, torch.int32, True), ("right", right, torch.uint8, two),
+                                       ("map_right", map_right, torch.int32, two), ("out_left", out_left, torch.uint8, False), ("out_right", out_right, torch.uint8, False),
+                                       ("inside_left", inside_left, torch.uint8, False), ("inside_right", inside_right, torch.uint8, False)))
+        if not two and (map_right is not None or out_right is not None or inside_right is not None):
+            bad("map_right, out_right and inside_right need right")
+        H, W, cn = _image_pair(bad, "left", left, "right", right if two else left)
+        if map_left.dim() != 3 or map_left.shape[2] != 2:
+            bad("map_left must be [h, w, 2], got %s" % (tuple(map_left.shape),))
+        h, w = int(map_left.shape[0]), int(map_left.shape[1])
+        shape = (h, w) if left.dim() == 2 else (h, w, cn)
+        _need(bad, "map_right", map_right, (h, w, 2))
+        if out_left is None:
+            out_left = torch.empty(shape, device=left.device, dtype=torch.uint8)
+        if two and out_right is None:
+            out_right = torch.empty(shape, device=left.device, dtype=torch.uint8)
+        _need(bad, "out_left", out_left, shape); _need(bad, "out_right", out_right, shape); _need(bad, "inside_left", inside_left, (h, w)); _need(bad, "inside_right", inside_right, (h, w))
+        self._call(self.ctx.lib.vido_rectify, left.data_ptr(), _p(right), cn, W * cn, W, H, map_left.data_ptr(), _p(map_right), w, h, out_left.data_ptr(), _p(out_right), w * cn,
+                   _p(inside_left), _p(inside_right), 1)
+        return (out_left, out_right) if two else out_left
+
     def mask_associate(self, prev, cur, state, classes=None, n=None, hold=0, out=None, lut=None, stats=None):
         """vido_mask_associate on device tensors: prev int32 [H,W] (the previous handed-over label image warped into this frame, i.e. mask_propagate's output) or None
         (first frame), cur int32 [H,W] (the detector's instance image at id base 0: value 1 + slot), state int32 [768] (read and written; zeros start a sequence),

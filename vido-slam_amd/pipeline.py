@@ -252,7 +252,17 @@ class NetNodes:
     the collision depth of the frame (bf / disparity metres where the status is 0, FLT_MAX elsewhere; without stereo_filter the op runs with min_region = 1: it makes the
     plane and launches no labelling) into one of two planes the nodes alternate between, and EVERY mask_propagate call of the nodes, the one inside InstanceIds included,
     receives the PREVIOUS frame's plane as its depth — the frame the carried mask belongs to: where two labels land on one pixel the nearer source wins, and a source
-    without a measured depth loses to one with.  On the first frame of a sequence no depth is passed.  Any other combination raises ValueError before anything is built."""
+    without a measured depth loses to one with.  On the first frame of a sequence no depth is passed.  Any other combination raises ValueError before anything is built.
+
+    rectify (default None: off, and nothing anywhere changes) = dict(left=cal, right=cal or None, raw_size=(h, w)) for cameras that deliver RAW frames (lens distortion,
+    a rig that is not aligned): cal = dict(K=(fx, fy, cx, cy) of the raw camera, dist=(k1, k2, p1, p2[, k3]), R=3 x 3 from raw-camera to rectified coordinates, P=(fx',
+    fy', cx', cy') of the rectified camera) as calibration files give them; raw_size defaults to the nodes' size.  The nodes build the maps once (host.rectify_map), keep
+    them on the device and offer rectify_frames(raw_left, raw_right=None, out_left=None, out_right=None) — HipOps.rectify (csrc/stereorectify.hip),
+    one launch for both cameras — and rect_inside, the bool HxW image of the left view's pixels that have a raw source.  infer() still takes RECTIFIED frames;
+    EndToEnd.push() takes the raw ones.  A `right` calibration needs depth_source = "stereo", and depth_source = "stereo" with rectify needs `right`.  With stereo depth,
+    every pixel outside rect_inside leaves infer() with disparity -1, shows stereo_status 5 ("outside the rectified view") and holds FLT_MAX in the collision depth
+    (propagate_bf): the black border of a rectified image matches the other view's border perfectly and must not become depth.  Unknown keys, a missing or malformed
+    calibration and sizes outside 16..4095 raise ValueError before anything is built."""
 
     RANGE_MODES = ("raise", "recompute")
     ID_BASES = (0, 127)                                               # label_mode="instance": the id base of even / odd frames (ids 1..127 / 128..254)
@@ -260,8 +270,10 @@ class NetNodes:
     def __init__(self, ctx, height=480, width=640, optimize=True, graphs=True, streams="flow+depth", miopen_find=False, seed=1,
                  mask_feed=(1088, 800), depth_feed=(192, 640), confidence=0.8, calibrate_scores=True, static_detector=True, on_range="raise", label_mode="class",
                  detect_every=1, stable_ids=False, stable_hold=0, flow_source="net", dis_params=None, dis_consistency=None, depth_source="net", stereo_params=None,
-                 stereo_filter=None, propagate_bf=None):
+                 stereo_filter=None, propagate_bf=None, rectify=None):
         self._check_detect_every(detect_every, on_range)              # (first: nothing is built for a bad argument)
+        self.rectify = self._check_rectify(rectify, depth_source, height, width)
+        self.rect_inside = None; self._rect_maps = None; self._rect_outside = None
         self.depth_source, self.stereo_params = self._check_depth_source(depth_source, stereo_params)
         self.stereo_filter, self.propagate_bf = self._check_stereo_filter(stereo_filter, propagate_bf, depth_source, detect_every, stable_ids)
         self.stereo_status = None
@@ -347,6 +359,13 @@ class NetNodes:
             self._flow_fn = lambda a, b: _nets.analyse_flow(self.flow_net, a, b)
         self._depth_fn = lambda a: _nets.analyse_depth(self.depth_net, a, feed=self.depth_feed, ops=ops).to(torch.float32)
         dex = [ex]
+        if self.rectify is not None:                                  # the maps, once: host code in float64, then device tensors for every rectify_frames call
+            from .host import rectify_map as _rectify_map
+            rh, rw = self.rectify["raw_size"]
+            maps = [None if c is None else _rectify_map(c["K"], c["dist"], c["R"], c["P"], (rw, rh), (width, height)) for c in (self.rectify["left"], self.rectify["right"])]
+            self._rect_maps = [None if m is None else torch.from_numpy(m[0]).to(dev) for m in maps]
+            self.rect_inside = torch.from_numpy(maps[0][1]).to(dev).bool()
+            self._rect_outside = ~self.rect_inside
         if self.depth_source == "stereo":                             # the op on (left, right); the status image is the nodes' own buffer, written by eager calls and replays alike
             self.stereo_status = torch.zeros((height, width), dtype=torch.uint8, device=dev)
             self._depth_fn = lambda a, b: ops.stereo_sgm(a, b, status=self.stereo_status, **self.stereo_params)
@@ -360,6 +379,15 @@ class NetNodes:
                     disp = ops.stereo_sgm(a, b, q4=self._stereo_q4, status=self.stereo_status, **self.stereo_params)
                     return ops.stereo_filter(self._stereo_q4, self.stereo_status, out=disp, status_out=self.stereo_status, depth=self._coll_static, bf=self.propagate_bf, **filt)
                 self._depth_fn = _stereo_fn
+            if self.rectify is not None:                              # no depth outside the rectified view: the verdicts of the op(s) above, then the border's own
+                _inner = self._depth_fn
+                def _inside_fn(a, b):
+                    disp = _inner(a, b)
+                    disp.masked_fill_(self._rect_outside, -1.0); self.stereo_status.masked_fill_(self._rect_outside, 5)
+                    if self._coll_static is not None:
+                        self._coll_static.masked_fill_(self._rect_outside, torch.finfo(torch.float32).max)
+                    return disp
+                self._depth_fn = _inside_fn
             dex = [ex, ex]                                            # (its first call of the size, below, grows the op's scratch: before any capture)
         self._trunk_fn = lambda a: self.mask_net.trunk(_nets.maskrcnn.image_to_feed(a, dev, self.mask_feed, ops=ops))
         # the whole detector with static shapes (nets/maskrcnn.py: heads_static / analyse_image_static): trunk + device-side RPN selection + box head + fixed-slot
@@ -491,6 +519,64 @@ class NetNodes:
             range_words.zero_()
             self.ops_flow.range_latch(range_words[0:1]); self.ops.range_latch(range_words[1:2])
         return flow, depth, mask, labels, (e0, e1, e2)
+
+    @torch.no_grad()
+    def rectify_frames(self, raw_left, raw_right=None, out_left=None, out_right=None):
+        """NetNodes(rectify=...): raw_left (and raw_right, when a right calibration was given: then required) u8 raw_h x raw_w x 3 device tensors -> the rectified frame, or
+        the pair, u8 HxWx3 (out_left / out_right, or new tensors): what infer() takes.  One launch on the caller's stream, nothing is waited for."""
+        if self.rectify is None:
+            raise ValueError("rectify_frames: these nodes were built without rectify=")
+        if (raw_right is None) != (self._rect_maps[1] is None):
+            raise ValueError("rectify_frames: raw_right goes with a right calibration (rectify['right'] %s, raw_right %s)" % (
+                "missing" if self._rect_maps[1] is None else "given", "missing" if raw_right is None else "given"))
+        rh, rw = self.rectify["raw_size"]
+        for name, t in (("raw_left", raw_left), ("raw_right", raw_right)):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (rh, rw, 3)):
+                raise ValueError("rectify_frames: %s must be a u8 device tensor [%d, %d, 3]" % (name, rh, rw))
+        return self.ops.rectify(raw_left, self._rect_maps[0], raw_right, self._rect_maps[1], out_left=out_left, out_right=out_right)
+
+    RECTIFY_KEYS = ("left", "right", "raw_size")
+    CAL_SIZES = {"K": (4,), "dist": (4, 5), "R": (9,), "P": (4,)}
+
+    @classmethod
+    def _check_rectify(cls, rectify, depth_source, height, width):
+        """-> None, or dict(left=cal, right=cal or None, raw_size=(h, w)) with every calibration as float64 arrays (dist padded to five)"""
+        if rectify is None:
+            return None
+        import numpy as _np
+        if not isinstance(rectify, dict) or any(k not in cls.RECTIFY_KEYS for k in rectify) or rectify.get("left") is None:
+            raise ValueError("rectify: None or a dict with `left` and keys among %s, not %r" % (cls.RECTIFY_KEYS, rectify))
+        def cal(name, c):
+            if not isinstance(c, dict) or set(c) != set(cls.CAL_SIZES):
+                raise ValueError("rectify[%r]: a dict with exactly the keys %s, not %r" % (name, tuple(cls.CAL_SIZES), c))
+            out = {}
+            for k, sizes in cls.CAL_SIZES.items():
+                try:
+                    a = _np.asarray(c[k], _np.float64).ravel()
+                except (TypeError, ValueError):
+                    a = _np.zeros(0)
+                if a.size not in sizes or not _np.isfinite(a).all():
+                    raise ValueError("rectify[%r][%r]: %s finite numbers expected, not %r" % (name, k, " or ".join(str(n) for n in sizes), c[k]))
+                out[k] = a
+            out["dist"] = _np.concatenate([out["dist"], _np.zeros(5 - out["dist"].size)])
+            if not (out["K"][0] > 0 and out["K"][1] > 0 and out["P"][0] > 0 and out["P"][1] > 0):
+                raise ValueError("rectify[%r]: focal lengths > 0 expected" % name)
+            return out
+        left = cal("left", rectify["left"])
+        right = None if rectify.get("right") is None else cal("right", rectify["right"])
+        if right is not None and depth_source != "stereo":
+            raise ValueError("rectify: a `right` calibration needs depth_source='stereo' (nothing else reads a right view)")
+        if right is None and depth_source == "stereo":
+            raise ValueError("rectify: depth_source='stereo' needs the `right` calibration too (SGM matches two rectified views)")
+        raw = rectify.get("raw_size", (height, width))
+        try:
+            rh, rw = (int(v) for v in raw)
+            ok = tuple(raw) == (rh, rw)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or not all(16 <= v <= 4095 for v in (rh, rw, int(height), int(width))):
+            raise ValueError("rectify: raw_size = (h, w) with sizes in 16..4095 expected, not %r (nodes %r x %r)" % (raw, height, width))
+        return dict(left=left, right=right, raw_size=(rh, rw))
 
     DEPTH_SOURCES = ("net", "stereo")
     STEREO_PARAMS = ("max_disp", "p1", "p2", "uniqueness", "lr_tol")
@@ -731,6 +817,13 @@ class EndToEnd:
         if getattr(nodes, "depth_source", "net") == "stereo":          # the right view of every frame in flight: a pinned and a device buffer per ring slot
             for hb, db in zip(self.host, self.dev):
                 hb["right"] = pin((h, w, 3), torch.uint8); db["right"] = mk((h, w, 3), torch.uint8)
+        self.rectify = getattr(nodes, "rectify", None) is not None      # raw frames in: a pinned and a device buffer of the raw size per camera and ring slot
+        if self.rectify:
+            rh, rw = nodes.rectify["raw_size"]
+            for hb, db in zip(self.host, self.dev):
+                hb["raw"] = pin((rh, rw, 3), torch.uint8); db["raw"] = mk((rh, rw, 3), torch.uint8)
+                if "right" in db:
+                    hb["raw_right"] = pin((rh, rw, 3), torch.uint8); db["raw_right"] = mk((rh, rw, 3), torch.uint8)
         self.copy_stream = torch.cuda.Stream(device=dev)
         self.q = _queue.Queue(maxsize=1)      # the networks run at most one frame ahead of the tracker (+ the one in flight)
         self.poses, self.stats, self.err = [], [], None
@@ -832,7 +925,9 @@ class EndToEnd:
 
     @torch.no_grad()
     def push(self, bgr, given=None, right=None):
-        """bgr: HxWx3 u8 numpy.  right: HxWx3 u8 numpy, the rectified right view of bgr — with NetNodes(depth_source="stereo") only, where it is required: it is uploaded next
+        """bgr: HxWx3 u8 numpy; over NetNodes(rectify=...) the RAW frame, raw_h x raw_w x 3 (and `right` the raw right frame): both go up to raw ring buffers and one
+        rectify launch writes the slot's frame (and right) buffers before the event the networks and the tracker wait for, so the tracker, ORB, the flow, the detector and
+        SGM all see the rectified left view; the tracker's settings then hold P's intrinsics and zero distortion.  right: HxWx3 u8 numpy, the rectified right view of bgr — with NetNodes(depth_source="stereo") only, where it is required: it is uploaded next
         to the frame and the depth parked in the ring is the stereo op's disparity image (metres in the tracker through the KITTI ChooseData code, DepthMapFactor: 1 and
         Camera.bf = fx * baseline: NetNodes' docstring).  given = (depth f32 HxW raw sensor units, flow f32 HxWx2, mask i32 HxW) for feed == "given" (copied: the caller's arrays are not modified,
         although the tracker rescales the depth map it is handed in place)."""
@@ -845,11 +940,22 @@ class EndToEnd:
         self.net_stream = torch.cuda.current_stream()
         slot = self.k % self.RING
         hb, db = self.host[slot], self.dev[slot]
-        hb["bgr"].numpy()[...] = bgr
         cur = db["bgr"]
-        cur.copy_(hb["bgr"], non_blocking=True)                          # the only upload of the frame on the network side
+        if self.rectify:                                                 # raw frames go up; ONE launch writes the rectified frame(s) into the slot's frame and right buffers
+            hb["raw"].numpy()[...] = bgr
+            db["raw"].copy_(hb["raw"], non_blocking=True)
+            if stereo:
+                hb["raw_right"].numpy()[...] = right
+                db["raw_right"].copy_(hb["raw_right"], non_blocking=True)
+            with self.net_lock:
+                self.nodes.rectify_frames(db["raw"], db["raw_right"] if stereo else None, out_left=cur, out_right=db["right"] if stereo else None)
+            if self.handover != "device":                                # the host hand-over gives the tracker the host frame: the rectified one comes back
+                hb["bgr"].copy_(cur, non_blocking=True)
+        else:
+            hb["bgr"].numpy()[...] = bgr
+            cur.copy_(hb["bgr"], non_blocking=True)                      # the only upload of the frame on the network side
         img_ev = torch.cuda.Event(); img_ev.record()                     # the image is on the device: all the tracker's ORB extraction needs (prefetched in _track_loop)
-        if stereo:
+        if stereo and not self.rectify:
             hb["right"].numpy()[...] = right
             db["right"].copy_(hb["right"], non_blocking=True)
         if given is not None:

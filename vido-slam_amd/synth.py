@@ -166,6 +166,31 @@ class Scene3D:
         other.poses = [P @ Tb for P in self.poses]
         return left, other.frame(k)[0], depth, mask
 
+    def raw_stereo_frame(self, k, baseline, K_raw, dist, R_left, R_right):
+        """The pair of stereo_frame(k, baseline) as a raw rig sees it: (raw left u8, raw right u8), each w x h.  The scene's own camera (K, poses) is the RECTIFIED left
+        camera; a raw camera sits at the same centre (the right one `baseline` metres along the rectified x), has intrinsics K_raw = (fx, fy, cx, cy), Brown distortion
+        dist = (k1, k2, p1, p2, k3), and is turned so that R (3 x 3) takes its coordinates to rectified ones.  The ray of a raw pixel is its undistorted normalised point
+        (fixed-point iteration, 30 rounds), rotated by R and scaled to z = 1: the inverse direction of the rectification map's formula, which goes from a rectified pixel
+        through R transposed and the forward distortion to a raw pixel."""
+        import copy
+        fx, fy, cx, cy = (float(v) for v in K_raw); k1, k2, p1, p2, k3 = (float(v) for v in dist)
+        x0 = (self.uv[..., 0] - cx) / fx; y0 = (self.uv[..., 1] - cy) / fy
+        x, y = x0.copy(), y0.copy()
+        for _ in range(30):
+            r2 = x * x + y * y; rad = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+            dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x); dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+            x = (x0 - dx) / rad; y = (y0 - dy) / rad
+        n = np.stack([x, y, np.ones_like(x)], -1)
+        out = []
+        for R, shift in ((R_left, 0.0), (R_right, float(baseline))):
+            d = n @ np.asarray(R, np.float64).reshape(3, 3).T                           # rectified coordinates of the raw ray
+            Tb = np.eye(4); Tb[0, 3] = shift
+            other = copy.copy(self)
+            other.rays = d / d[..., 2:3]
+            other.poses = [P @ Tb for P in self.poses]
+            out.append(other.frame(k)[0])
+        return out[0], out[1]
+
 
 def convoy_scene(n_frames, w=640, h=480, seed=5, step=0.25):
     """BASELINE configs[1]-[3] chained: a 640x480 Scene3D with FIVE dynamic objects that drive ahead of the camera at roughly its own
